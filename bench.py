@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — simplicial edges/sec (forward + backward) of one shared simplicial
-message-passing layer (EGCL) on MI355X, with its HBM-roofline fraction and the
+message-passing layer (EGCL) on MI355X; with --full also its HBM-roofline fraction (per-stage kernel times) and the
 reference CPU path timed beside it.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5                       # the headline line only
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                # + CSR build, roofline, CPU baselines
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR    # + what the last timed step computed, as .npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -53,6 +55,7 @@ WORKLOADS = {
     "M32": ((1.0, 1.0, 1.0), 32, 10_000, 100_000),
 }
 WORKLOAD_AGGR = {"M32": "sum"}   # every other workload: mean (hulls_cssmpnn.py)
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this many bytes of .npy data in all
 
 
 def algorithmic_bytes(C, D, A=6, T=3):
@@ -213,6 +216,25 @@ def cpu_baseline(metric, C, state, cpu_inputs, budget_s=20.0, aggr="mean"):
                       f"{torch.__version__} CPU threads={cores} of {os.cpu_count()} host cores"}
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every (name, tensor) pair as out_dir/<name>.npy in float32. When the whole set exceeds DUMP_BYTES,
+    every array over 1 MB is cut to the same fraction of its rows, a fixed sample (torch generator seeded 0, rows in
+    ascending order), so that two runs with the same arguments write the same rows; smaller arrays stay whole."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [(name, t.detach().float().cpu()) for name, t in arrays]
+    large = lambda t: 4 * t.numel() > (1 << 20) and t.dim() > 0 and t.shape[0] > 1
+    small_bytes = sum(4 * t.numel() + 4096 for _, t in arrays if not large(t))
+    large_bytes = sum(4 * t.numel() + 4096 for _, t in arrays if large(t))
+    keep = min(1.0, (DUMP_BYTES - small_bytes) / max(large_bytes, 1))
+    for name, t in arrays:
+        if keep < 1.0 and large(t):
+            n = max(1, int(t.shape[0] * keep))
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values
+            t = t.index_select(0, rows)
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nproc-per-node N bench.py
     <the same arguments>` as a child process on a free loopback port. Every line the ranks print is relayed as it comes;
@@ -268,6 +290,13 @@ def main():
                          "'rehearsal' and its value is NOT a measurement")
     ap.add_argument("--rehearse-size", default="64,512", metavar="NODES,EDGES",
                     help="with --rehearse-backend: nodes, edges per rank instead of the workload's")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: CSR build time, per-stage "
+                         "kernel times and the rooflines, the compute-only rate of N > 1 partition B, the CPU baselines "
+                         "(unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (layer output y, d/dh, d/dparam) as DIR/<name>.npy, "
+                         "float32; arrays over a %d MB total are cut to a fixed seeded sample of rows" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
 
     if args.partition == "auto":
@@ -337,18 +366,18 @@ def main():
 
         def step():
             y = sl(h, plan, ea, na)
-            return torch.autograd.grad(y, [h] + params, gout)
+            return (y,) + torch.autograd.grad(y, [h] + params, gout)
     elif world > 1 or args.segments or rehearsal:
         sl = sharded.ShardedEGCL(layer, backend=backend)
         plan = sl.plan(ei, N)
 
         def step():
             y = sl(h, plan, ea, na)
-            return torch.autograd.grad(y, [h] + params, gout)
+            return (y,) + torch.autograd.grad(y, [h] + params, gout)
     else:
         def step():
             y = layer(h, ei, ea, na)
-            return torch.autograd.grad(y, [h] + params, gout)
+            return (y,) + torch.autograd.grad(y, [h] + params, gout)
 
     # warm-up (builds the CSR once, sets kernel attributes)
     for _ in range(max(args.warmup, 1)):
@@ -379,7 +408,12 @@ def main():
                   file=sys.stderr)
             graph = None
             sync()
-    run = graph.replay if graph is not None else (segments.run if segments is not None else step)
+    last = [None]   # eager launches: what the most recent step returned
+
+    def run_eager():
+        last[0] = step()
+
+    run = graph.replay if graph is not None else (segments.run if segments is not None else run_eager)
     for _ in range(2):
         run()
 
@@ -406,9 +440,19 @@ def main():
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / args.steps
     value = E_total * args.steps / elapsed
+    if args.dump_outputs is not None and rank == 0:
+        if graph is not None:
+            outs = graph_out
+        elif segments is not None:   # rank 0's slice: out, d/dh of its rows, the flat all-reduced parameter gradients
+            outs = (segments.out, getattr(segments, "gh_loc", getattr(segments, "gh", None)), getattr(segments, "flat", None))
+        else:
+            outs = last[0]
+        names = ["y", "grad_h"] + (["grad_params_flat"] if segments is not None else
+                                   ["grad_" + k for k, _ in layer.named_parameters()])
+        dump_outputs(args.dump_outputs, [(k, t) for k, t in zip(names, outs) if t is not None])
     # N > 1, partitioning B: the same steps without the collectives (compute-only rate, bus bandwidth)
     compute_only = None
-    if part_b and segments is not None:
+    if args.full and part_b and segments is not None:
         dist.barrier()
         sync()
         t1 = time.perf_counter()
@@ -438,6 +482,31 @@ def main():
                              "backend": args.rehearse_backend, "dist_backend": args.dist_backend},
                   "roofline": None, "cpu_baseline": None}
     elif rank == 0:
+        result = {
+            "metric": "simplicial edges/sec (fwd+bwd) on Cl(3,0) 8-ch multivectors; % HBM roofline"
+                      if args.workload == "S1" else f"simplicial edges/sec (fwd+bwd), workload {args.workload}",
+            "value": round(value, 1), "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.workload}: EGCL layer fwd+bwd, Cl{tuple(int(m) for m in metric)}, "
+                                   f"{C} channels, {N} nodes, "
+                                   + (f"{E_per} edges/GPU x {world} GPU" if args.scaling == "weak" else
+                                      f"{E_total} edges sharded over {world} GPU")
+                                   + f", aggr={aggr}, edge_attr 6ch, node_attr 3ch",
+                       "host_cores": os.cpu_count(),
+                       "aggregation": "deterministic (row table + fixed-order segmented sums)" if args.deterministic else "float atomics",
+                       "launch": ("hip-graph replay" if graph is not None else
+                                  "hip-graph segments + eager collectives" if segments is not None else "eager"),
+                       "sharding": ("none" if world == 1 else
+                                    "B: nodes partitioned, edges by target; all-gather(out) fwd, reduce-scatter(d/dh) + "
+                                    "all-reduce(param grads) bwd" if part_b else
+                                    "A: edge list sharded, all-reduce(agg) fwd + all-reduce([dh|edge grads]) bwd"),
+                       "edges_per_rank": edges_per_rank,
+                       "partition": None if world == 1 else args.partition,
+                       "pad_ratio": round(plan.pad_ratio, 4) if part_b else None,
+                       "local_share": round(plan.local_share, 4) if part_b else None},
+        }
+    if rank == 0 and not rehearsal and args.full:
         # ---- per-stage kernel time (HIP events on the launch stream, weights pre-packed)
         be = ops.HipBackend
         spec = layer.spec()
@@ -500,39 +569,16 @@ def main():
         mac_per_edge = mac_edge + (N / E_per) * mac_node
         roofline["fp32_alu"] = {"mac_per_edge": round(mac_per_edge, 1), "peak_tflops": FP32_PEAK_TFLOPS,
                                 "layer_frac_of_fp32_peak": round(value / world * 2 * mac_per_edge / (FP32_PEAK_TFLOPS * 1e12), 5)}
-        result = {
-            "metric": "simplicial edges/sec (fwd+bwd) on Cl(3,0) 8-ch multivectors; % HBM roofline"
-                      if args.workload == "S1" else f"simplicial edges/sec (fwd+bwd), workload {args.workload}",
-            "value": round(value, 1), "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.workload}: EGCL layer fwd+bwd, Cl{tuple(int(m) for m in metric)}, "
-                                   f"{C} channels, {N} nodes, "
-                                   + (f"{E_per} edges/GPU x {world} GPU" if args.scaling == "weak" else
-                                      f"{E_total} edges sharded over {world} GPU")
-                                   + f", aggr={aggr}, edge_attr 6ch, node_attr 3ch",
-                       "csr_build_ms": None if csr_build_ms is None else round(csr_build_ms, 3),
-                       "csr_first_build_ms": None if csr_first_ms is None else round(csr_first_ms, 3),
-                       "host_cores": os.cpu_count(),
-                       "aggregation": "deterministic (row table + fixed-order segmented sums)" if args.deterministic else "float atomics",
-                       "launch": ("hip-graph replay" if graph is not None else
-                                  "hip-graph segments + eager collectives" if segments is not None else "eager"),
-                       "sharding": ("none" if world == 1 else
-                                    "B: nodes partitioned, edges by target; all-gather(out) fwd, reduce-scatter(d/dh) + "
-                                    "all-reduce(param grads) bwd" if part_b else
-                                    "A: edge list sharded, all-reduce(agg) fwd + all-reduce([dh|edge grads]) bwd"),
-                       "edges_per_rank": edges_per_rank,
-                       "partition": None if world == 1 else args.partition,
-                       "pad_ratio": round(plan.pad_ratio, 4) if part_b else None,
-                       "local_share": round(plan.local_share, 4) if part_b else None,
-                       "compute_only": compute_only},
-            "roofline": roofline,
-        }
+        result["config"].update({
+            "csr_build_ms": None if csr_build_ms is None else round(csr_build_ms, 3),
+            "csr_first_build_ms": None if csr_first_ms is None else round(csr_first_ms, 3),
+            "compute_only": compute_only})
+        result["roofline"] = roofline
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not rehearsal:
+        if world == 1 and args.full and not args.no_cpu_baseline and not rehearsal:
             result["cpu_baseline"] = cpu_baseline(metric, C, state, cpu_inputs, args.cpu_budget, aggr=aggr)
         print(json.dumps(result))
 

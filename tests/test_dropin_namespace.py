@@ -1,37 +1,45 @@
-"""CPU, build container only (skipped where /root/reference is absent): with this package's
-directory in front of the reference on sys.path, the reference's OWN task model builds on the
-HIP-backed layers (namespace-package shadowing)."""
+"""CPU: with this package's directory in front on sys.path, the `csmpn` import paths the reference's task models use
+(`csmpn.models.cegnn_utils`: MVLinear, EGCL, CEMLP; `csmpn.algebra.cliffordalgebra`: CliffordAlgebra) resolve to the
+HIP-backed layers (namespace-package shadowing), and the hulls task model built from them has exactly
+the reference model's parameters: the key set and shapes of the state_dict recorded from the imported reference
+(tests/golden/model_hulls.npz, make_model_golden.py) and its parameter count (254329)."""
 import os
 import subprocess
 import sys
 
-import pytest
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG_DIR = os.path.join(ROOT, "clifford-group-equivariant-simplicial-message-passing-networks_amd")
-REF = "/root/reference"
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 SCRIPT = r"""
 import sys
 sys.dont_write_bytecode = True
-sys.path.insert(0, {golden!r}); import pyg_standin; pyg_standin.install()
-sys.path.insert(0, {ref!r}); sys.path.insert(0, {pkg!r})
-from csmpn.models.hulls_cssmpnn import HullsCliffordSharedSimplicialMPNN      # reference file
+sys.path.insert(0, {pkg!r})
+import numpy as np
+from csmpn.algebra.cliffordalgebra import CliffordAlgebra
+from csmpn.models.cegnn_utils import MVLinear, EGCL, CEMLP
 import csmpn.models.cegnn_utils as ours, csmpn.algebra.cliffordalgebra as alg
 assert ours.__file__.startswith({pkg!r}), ours.__file__
 assert alg.__file__.startswith({pkg!r}), alg.__file__
-import csmpn.models.hulls_cssmpnn as hm
-assert hm.__file__.startswith({ref!r}), hm.__file__
-m = HullsCliffordSharedSimplicialMPNN()
-assert all(type(l) is ours.EGCL for l in m.layers)
+from csmpn.models.simplicial_mpnn import HullsSimplicialMPNN
+m = HullsSimplicialMPNN()
+assert len(m.layers) == 3 and all(type(l) is ours.EGCL for l in m.layers)
 assert type(m.algebra) is alg.CliffordAlgebra and m.algebra.hip_supported
+g = np.load({fixture!r})
+want = {{k[2:]: tuple(g[k].shape) for k in g.files if k.startswith("p/")}}
+have = {{k: tuple(v.shape) for k, v in m.state_dict().items() if "algebra." not in k}}
+assert want == have, (sorted(set(want) ^ set(have))[:5], [k for k in want if k in have and want[k] != have[k]][:5])
 print(sum(p.numel() for p in m.parameters()))
 """
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference not present (GPU box)")
 def test_reference_model_builds_on_hip_layers():
-    code = SCRIPT.format(golden=os.path.join(ROOT, "tests", "golden"), ref=REF, pkg=PKG_DIR)
+    fixture = os.path.join(GOLDEN, "model_hulls.npz")
+    g = np.load(fixture)
+    assert sum(g[k].size for k in g.files if k.startswith("p/")) == 254329
+    code = SCRIPT.format(pkg=PKG_DIR, fixture=fixture)
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
                          env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
     assert out.returncode == 0, out.stderr[-2000:]

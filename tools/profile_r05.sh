@@ -12,7 +12,7 @@ OUT=gpurun_out/prof_$TAG
 rm -rf $OUT
 mkdir -p $OUT
 WL=${2:-S1}
-B="python3 bench.py --no-cpu-baseline --no-graph --workload $WL"
+B="python3 bench.py --full --no-cpu-baseline --no-graph --workload $WL"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $B --steps 20 --warmup 5 > $OUT/bench_trace.log 2>&1
 if [ "$3" != "quick" ]; then
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS --output-format csv -d $OUT/pmc1 -- $B --steps 3 --warmup 2 > $OUT/bench_pmc1.log 2>&1
