@@ -15,6 +15,7 @@
 #include "../../include/csmpn_hip.h"
 #include "capi_common.hpp"
 #include "cemlp_kernel.hpp"
+#include "cemlp_wide.hpp"
 #include "launch.hpp"
 #include "cl_launch.hpp"
 #include "cm_launch.hpp"
@@ -186,6 +187,19 @@ hipError_t launch_cemlp(AlgId id, int mode, int var, int h, bool bwd, unsigned g
     }
 }
 
+hipError_t launch_cemlp_wide(AlgId id, int mode, bool bwd, unsigned grid, unsigned block, size_t lds, hipStream_t st,
+                             const DevCemlp& C, const RowIO& io) {
+    switch (id) {
+        case ALG_N2: return launch_cemlp_wide_n2(mode, bwd, grid, block, lds, st, C, io);
+        case ALG_N3: return launch_cemlp_wide_n3(mode, bwd, grid, block, lds, st, C, io);
+        case ALG_N4: return launch_cemlp_wide_n4(mode, bwd, grid, block, lds, st, C, io);
+        case ALG_N5: return launch_cemlp_wide_n5(mode, bwd, grid, block, lds, st, C, io);
+        case ALG_N5M: return launch_cemlp_wide_n5m(mode, bwd, grid, block, lds, st, C, io);
+        case ALG_N4M: return launch_cemlp_wide_n4m(mode, bwd, grid, block, lds, st, C, io);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_gp(AlgId id, bool bwd, const float* a, const float* b, const float* gout, float* out, float* ga,
                      float* gb, long rows, hipStream_t st) {
     switch (id) {
@@ -242,12 +256,13 @@ struct Plan {
     int H;                // row halves per tile
     bool ps;              // parity-split kernels (cemlp_ps.hpp): 16-row tiles, 8 channels x 2 blade parities
     bool det_general;     // deterministic mode on the general row-tile kernels: one row tile per workgroup, mirror slices
+    bool wide;            // 65..256 output channels: the wide row-tile kernel (cemlp_wide.hpp), CT channel tiles on MT waves
     void* workspace;      // the caller's workspace (the row-per-lane backward keeps its partial sums at its end)
     size_t workspace_bytes;
 };
 
 // floats of one row tile's buffers; tiles are [channel][D][R] with channel stride R*D + 4
-struct TileLayout { int off_in, off_p0, off_p1, off_z, off_g, off_red, off_idx, total; };
+struct TileLayout { int off_in, off_p0, off_p1, off_z, off_g, off_red, off_idx, total; int off_park = 0; };
 TileLayout tile_layout(int D, int H, const csmpn_block_params* blocks, int nblk, bool bwd, int stage_rowlen,
                        bool use_saved = false, bool ps = false, bool share_inz = false) {
     int maxO = 0, maxCPo = 0;
@@ -302,6 +317,38 @@ TileLayout tile_layout(int D, int H, const csmpn_block_params* blocks, int nblk,
     L.total = off;
     return L;
 }
+// Wide plans (65..256 output channels, cemlp_wide.hpp): one row tile per workgroup, H = 1, CT = ceil(max O / 16) channel
+// tiles. As tile_layout, but the forward's block outputs always replace the input tile (z is a buffer of its own: several
+// waves), the LayerNorm scratch has CT entries and a parking region of kWideSlots* x CT lane-layout tensors follows.
+constexpr int kWideMaxChannels = 256;
+TileLayout wide_layout(int D, const csmpn_block_params* blocks, int nblk, bool bwd, int stage_rowlen, bool use_saved) {
+    int maxCPo = 0;
+    for (int k = 0; k < nblk; ++k) maxCPo = rup(blocks[k].out_features, 4) > maxCPo ? rup(blocks[k].out_features, 4) : maxCPo;
+    const int R = 16, CS = R * D + 4, CT = cdiv(maxCPo, 16);
+    int sz_in = rup(blocks[0].in_features, 4) * CS;
+    const int sz_o = maxCPo * CS;
+    const bool single_in = !bwd || (use_saved && nblk > 1);
+    if (single_in && sz_o > sz_in) sz_in = sz_o;
+    int sz_g = sz_o;
+    if (stage_rowlen > 0 && R * stage_rowlen > sz_g) sz_g = rup(R * stage_rowlen, 4);
+    TileLayout L;
+    int off = 0;
+    L.off_in = off; off += sz_in;
+    L.off_p0 = single_in ? L.off_in : off; off += (!single_in && nblk >= 2) ? sz_o : 0;
+    L.off_p1 = single_in ? L.off_in : off; off += (!single_in && nblk >= 3) ? sz_o : 0;
+    if (!bwd) {   // forward: the edge staging reuses the z tile, dead by then
+        L.off_z = off; L.off_g = off; off += sz_g;
+    } else {
+        L.off_z = off; off += sz_o;
+        L.off_g = off; off += sz_g;
+    }
+    L.off_red = off; off += rup(CT * 16, 4);
+    L.off_idx = off; off += rup(3 * R, 4);
+    L.off_park = off; off += (bwd ? kWideSlotsBwd : kWideSlotsFwd) * CT * D * 256;
+    L.total = off;
+    return L;
+}
+
 struct Choice { int var, rt, wgs; bool mirror; };
 // backward kernels are built for 256 threads (512 VGPRs), forward for 512 threads
 Choice choose_variant(int MT, size_t tile_bytes, size_t mirror_bytes, size_t wstore_bytes, bool bwd, bool ps = false) {
@@ -451,7 +498,10 @@ int make_plan(AlgId id, int n, const csmpn_block_params* blocks, const csmpn_blo
     const int NW = ps ? 8 : 16 / H;
     const int MT = ps ? 1 : cdiv(maxO, NW);
     plan.ps = ps;
-    if (MT > 4) return fail(CSMPN_ERR_UNSUPPORTED, "out_features %d > 64 not supported", maxO);
+    // more than 4 channel tiles (64 channels): the wide kernel, up to kWideMaxChannels
+    if (MT > 4 && maxO > kWideMaxChannels)
+        return fail(CSMPN_ERR_UNSUPPORTED, "out_features %d > %d not supported", maxO, kWideMaxChannels);
+    plan.wide = MT > 4;
     C.MT = MT;
     C.H = H;
     plan.H = H;
@@ -505,6 +555,35 @@ int make_plan(AlgId id, int n, const csmpn_block_params* blocks, const csmpn_blo
         }
     }
     plan.pack_f4 = cursor;
+
+    if (plan.wide) {
+        // CT channel tiles on MT waves: 4 in the backward (one wave per SIMD at ~500 VGPRs), 8 in the forward; one row tile
+        // per workgroup, in LDS when its buffers and parking region fit, else in the global scratch behind the packed weights
+        const int CT = cdiv(maxO, 16), cap = bwd ? 4 : 8;
+        const TileLayout L = wide_layout(D, blocks, nblk, bwd, stage_rowlen, use_saved);
+        C.CT = CT; C.MT = CT < cap ? CT : cap; C.RT = 1;
+        C.share_inz = 0; C.phased = 0; C.mirror_floats = 0; C.wstore_floats = 0;
+        C.off_in = L.off_in; C.off_p0 = L.off_p0; C.off_p1 = L.off_p1; C.off_z = L.off_z; C.off_g = L.off_g;
+        C.off_red = L.off_red; C.off_idx = L.off_idx; C.off_park = L.off_park; C.tile_floats = L.total;
+        // deterministic mode (n <= 3): one row tile per workgroup already; every gradient word has one writing wave
+        plan.det_general = deterministic && n <= 3;
+        const size_t tile_bytes = (size_t)L.total * 4;
+        if (tile_bytes <= (size_t)kMaxLdsBytes) {
+            C.gtiles = nullptr;
+            plan.lds_bytes = tile_bytes;
+            plan.var = VAR_GROUP_NM;
+        } else {
+            const size_t scratch = (size_t)kGlobalTileGrid * tile_bytes;
+            if (workspace_bytes < need + scratch)
+                return fail(CSMPN_ERR_INVALID, "workspace too small: %zu < %zu", workspace_bytes, need + scratch);
+            C.gtiles = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + need);
+            plan.lds_bytes = 0;
+            plan.var = VAR_GLOBAL;
+        }
+        plan.grid_cap = kGlobalTileGrid;
+        plan.threads = (unsigned)(C.MT * 64);
+        return CSMPN_OK;
+    }
 
     // buffers of one row tile (floats)
     TileLayout L = tile_layout(D, H, blocks, nblk, bwd, stage_rowlen, use_saved, ps);
@@ -595,6 +674,19 @@ int make_plan(AlgId id, int n, const csmpn_block_params* blocks, const csmpn_blo
 // the gradient tensors ([kDetGroups, slice] floats at the end of the workspace, reference layouts back to back);
 // det_reduce_kernel adds the copies in a fixed order.
 constexpr int kDetGroups = 512;
+// Wide plans: a copy grows with O^2 (a 128-channel Cl(3,0) node model: ~1 MB), so the number of copies (= workgroups of
+// the deterministic launch) shrinks with it: as many as fit in kWideDetBudget, at least kWideDetMinGroups, at most kDetGroups.
+constexpr size_t kWideDetBudget = (size_t)128 << 20;
+constexpr int kWideDetMinGroups = 16;
+int wide_det_groups(size_t slice_floats) {
+    const size_t g = kWideDetBudget / (slice_floats * sizeof(float) > 0 ? slice_floats * sizeof(float) : 1);
+    return g < (size_t)kWideDetMinGroups ? kWideDetMinGroups : (g > (size_t)kDetGroups ? kDetGroups : (int)g);
+}
+// bytes reserved for them: max(budget, kWideDetMinGroups copies) covers every slice up to slice_floats
+size_t wide_det_reserve(size_t slice_floats) {
+    const size_t floor_bytes = (size_t)kWideDetMinGroups * slice_floats * sizeof(float);
+    return (floor_bytes > kWideDetBudget ? floor_bytes : kWideDetBudget) + 256;
+}
 int det_slice_floats_of(const csmpn_block_params* blocks, int nblk, int G, int P) {
     int m = 0;
     for (int k = 0; k < nblk; ++k)
@@ -605,7 +697,11 @@ size_t det_slice_bytes(int n, const csmpn_block_params* blocks, int nblk) {
     if (n > 3 || nblk < 1) return 0;
     // upper bound over the algebras with n generators: paths <= (n + 1)^3 (Cl(3,0): 20 of 64, Cl(2,0): 10 of 27)
     const int G = n + 1, P = n == 3 ? 20 : (n == 2 ? 10 : (n + 1) * (n + 1) * (n + 1));
-    return (size_t)det_slice_floats_of(blocks, nblk, G, P) * sizeof(float) * kDetGroups + 256;
+    const size_t slice = (size_t)det_slice_floats_of(blocks, nblk, G, P);
+    int maxO = 0;
+    for (int k = 0; k < nblk; ++k) maxO = blocks[k].out_features > maxO ? blocks[k].out_features : maxO;
+    if (maxO > 64) return wide_det_reserve(slice);
+    return slice * sizeof(float) * kDetGroups + 256;
 }
 struct DetMap {
     int n;
@@ -705,6 +801,8 @@ bool cl_shape(int n, const csmpn_block_params* blocks, int nblk) {
 // than one block, no lane-kernel family of their own. They get a hand-over region as large as the saved inputs behind them.
 bool general_phased_shape(int n, const csmpn_block_params* blocks, int nblk) {
     if (n > 3 || nblk < 2 || nblk > CSMPN_MAX_BLOCKS) return false;
+    for (int k = 0; k < nblk; ++k)
+        if (blocks[k].out_features > 64) return false;   // the wide kernel has no LDS mirror to shrink: no phased form
     if (n == 3 && nblk == 2) {
         const int ch = blocks[0].out_features, i0 = blocks[0].in_features;
         if (blocks[1].out_features == ch && blocks[1].in_features == ch) {
@@ -1088,7 +1186,8 @@ int run_rows(AlgId id, const Plan& plan, int mode, bool bwd, const RowIO& io_in,
     // for every backward of the small algebras - the parameter-gradient atomics of ALL row tiles onto one copy were the
     // bulk of the md17-width backward (M32 node stage 1.04 -> 0.53 ms with private copies); CSMPN_NO_SLICED_GRADS=1: off.
     const bool no_sliced = sw().no_sliced;
-    const bool sliced = bwd && (io.row_store || (!no_sliced && (id == ALG_N2 || id == ALG_N3) && !plan.ps && plan.var != VAR_GLOBAL));
+    const bool sliced = bwd && (io.row_store || (!no_sliced && (id == ALG_N2 || id == ALG_N3) && !plan.ps && plan.var != VAR_GLOBAL && !plan.wide));
+    int det_groups = kDetGroups;
     if (sliced) {
         const int G = (id == ALG_N2) ? 3 : 4, P = n_paths(id);   // det_general: n <= 3
         det_map.n = 0;
@@ -1104,7 +1203,8 @@ int run_rows(AlgId id, const Plan& plan, int mode, bool bwd, const RowIO& io_in,
             det_total = rup(det_total, 4);
         }
         det_map.total = det_total;
-        det_bytes = (size_t)det_total * sizeof(float) * kDetGroups + 256;
+        if (plan.wide) det_groups = wide_det_groups((size_t)det_total);
+        det_bytes = (size_t)det_total * sizeof(float) * det_groups + 256;
         if (!plan.workspace || plan.workspace_bytes < det_bytes) {
             if (io.row_store)
                 return fail(CSMPN_ERR_INVALID, "workspace too small for the deterministic backward: %zu < %zu", plan.workspace_bytes, det_bytes);
@@ -1142,9 +1242,12 @@ int run_rows(AlgId id, const Plan& plan, int mode, bool bwd, const RowIO& io_in,
     }
     long grid = (ntiles + Cd.RT - 1) / Cd.RT;
     if (grid > (long)plan.grid_cap) grid = plan.grid_cap;
-    if (det_bytes && grid > kDetGroups) grid = kDetGroups;
+    if (det_bytes && grid > det_groups) grid = det_groups;
     const bool debug = sw().debug;
-    if (debug)
+    if (debug && plan.wide)
+        fprintf(stderr, "[csmpn] wide mode=%d bwd=%d CT=%d MT=%d threads=%u lds=%zu grid=%ld tile_floats=%d rows=%ld\n", mode, (int)bwd,
+                Cd.CT, Cd.MT, threads, lds_bytes, grid, Cd.tile_floats, io.rows);
+    else if (debug)
         fprintf(stderr, "[csmpn] mode=%d bwd=%d var=%d ps=%d share=%d phased=%d H=%d MT=%d RT=%d threads=%u lds=%zu grid=%ld tile_floats=%d mirror=%d rows=%ld\n",
                 mode, (int)bwd, plan.var, (int)plan.ps, Cd.share_inz, (int)(bwd && Cd.phased), plan.H, Cd.MT, Cd.RT, threads, lds_bytes, grid,
                 Cd.tile_floats, Cd.mirror_floats, io.rows);
@@ -1166,9 +1269,12 @@ int run_rows(AlgId id, const Plan& plan, int mode, bool bwd, const RowIO& io_in,
             (void)i;
         }
     }
-    if (plan.ps) HIP_TRY(launch_cemlp_ps(id, mode, bwd, (unsigned)grid, threads, lds_bytes, st, Cd, io));
+    if (plan.wide) HIP_TRY(launch_cemlp_wide(id, mode, bwd, (unsigned)grid, threads, lds_bytes, st, Cd, io));
+    else if (plan.ps) HIP_TRY(launch_cemlp_ps(id, mode, bwd, (unsigned)grid, threads, lds_bytes, st, Cd, io));
     else HIP_TRY(launch_cemlp(id, mode, plan.var, plan.H, bwd, (unsigned)grid, threads, lds_bytes, st, Cd, io));
-    if (plan.ps) note_kernel("csmpn::cemlp_ps_kernel<%s, %d, %s>", alg_name(id), mode, bwd ? "true" : "false");
+    if (plan.wide) note_kernel("csmpn::cemlp_wide_kernel<%s, %d, %s> (%d channel tiles on %d waves, tiles in %s)", alg_name(id), mode,
+                               bwd ? "true" : "false", Cd.CT, Cd.MT, Cd.gtiles ? "global scratch" : "LDS");
+    else if (plan.ps) note_kernel("csmpn::cemlp_ps_kernel<%s, %d, %s>", alg_name(id), mode, bwd ? "true" : "false");
     else note_kernel("csmpn::cemlp_kernel<%s, %d, %d, %d, %s>", alg_name(id), mode, plan.var, plan.H, bwd ? "true" : "false");
     if (det_bytes) {
         hipLaunchKernelGGL(det_reduce_kernel, dim3((det_total + 255) / 256), dim3(256), 0, st, det_map, (const float*)det_slices, (int)grid);
@@ -1418,6 +1524,16 @@ size_t csmpn_cemlp_workspace_bytes(int n, const csmpn_block_params* blocks, int 
         bytes = b2 > bytes ? b2 : bytes;
     }
     const int D = 1 << n, MT = cdiv(maxO, 16);
+    if (maxO > 64 && maxO <= kWideMaxChannels) {
+        // wide kernel (cemlp_wide.hpp): packed weights (H = 1), the global tile scratch of the largest layout (backward without
+        // saved inputs, forward with the edge staging row; reserved even where the tile fits the LDS: the choice needs no
+        // metric, but the scratch is cheap to reserve and keeps the sizing simple), the deterministic copies (n <= 3)
+        const TileLayout Lb = wide_layout(D, blocks, n_blocks, true, 0, false);
+        const TileLayout Lf = wide_layout(D, blocks, n_blocks, false, blocks[n_blocks - 1].out_features * D, false);
+        const size_t tile = (size_t)(Lb.total > Lf.total ? Lb.total : Lf.total) * 4;
+        const size_t scratch = (size_t)kGlobalTileGrid * tile;
+        return ((bytes + scratch + 15) & ~(size_t)15) + det_slice_bytes(n, blocks, n_blocks) + 16 + 256;
+    }
     // worst case over the entry points (H = 1): backward layout / forward layout with the
     // edge-forward staging row
     const TileLayout Lb = tile_layout(D, 1, blocks, n_blocks, true, 0);

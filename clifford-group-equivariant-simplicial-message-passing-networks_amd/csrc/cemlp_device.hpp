@@ -66,7 +66,7 @@ struct DevBlock {
 
 struct DevCemlp {
     int nblk;
-    int MT;              // waves cooperating on one row tile = ceil(max O / NW)
+    int MT;              // waves cooperating on one row tile = ceil(max O / NW) (wide kernel: min(CT, 4 / 8))
     int RT;              // row tiles per workgroup
     int H;               // row halves per tile (1 or 2)
     int off_in, off_p0, off_p1, off_z, off_g, off_red, off_idx;  // float offsets inside one row tile's buffers
@@ -79,6 +79,8 @@ struct DevCemlp {
     float* gtiles;       // non-null: row-tile buffers live in this global scratch (too big for LDS)
     int det_slice_floats;  // > 0: deterministic mode of the general kernels - the g* pointers are slice 0 of a per-workgroup region
     int phased;            // 1: backward block by block (outer loop over blocks, last first): mirror of ONE block in LDS, d/d(block input) rows through io.plw_g1
+    int CT;                // wide kernel (cemlp_wide.hpp): 16-channel tiles of a row tile = ceil(max O / 16); MT waves run them
+    int off_park;          // ... float offset of the parking region inside one row tile's buffers
     DevBlock b[4];
 };
 

@@ -1,0 +1,5 @@
+// Wide row-tile kernels (65..256 channels) for the algebra with 5 generators, negative-signature mask 0u.
+#define CSMPN_ALG_N 5
+#define CSMPN_ALG_NEG 0u
+#define CSMPN_ALG_TAG n5
+#include "wide_inst.inc"

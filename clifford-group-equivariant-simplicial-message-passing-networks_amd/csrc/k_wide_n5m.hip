@@ -1,0 +1,5 @@
+// Wide row-tile kernels (65..256 channels) for the algebra with 5 generators, negative-signature mask 0x10u.
+#define CSMPN_ALG_N 5
+#define CSMPN_ALG_NEG 0x10u
+#define CSMPN_ALG_TAG n5m
+#include "wide_inst.inc"

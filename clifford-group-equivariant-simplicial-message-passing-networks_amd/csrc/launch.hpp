@@ -14,6 +14,8 @@ constexpr int kMaxLdsBytes = 160 * 1024;
                                      hipStream_t st, const DevCemlp& C, const RowIO& io);                      \
     hipError_t launch_cemlp_##tag(int mode, int var, int h, bool bwd, unsigned grid, unsigned block, size_t lds,   \
                                   hipStream_t st, const DevCemlp& C, const RowIO& io);                          \
+    hipError_t launch_cemlp_wide_##tag(int mode, bool bwd, unsigned grid, unsigned block, size_t lds, hipStream_t st, \
+                                       const DevCemlp& C, const RowIO& io);                                    \
     hipError_t launch_gp_##tag(bool bwd, const float* a, const float* b, const float* gout, float* out,        \
                                float* ga, float* gb, long rows, hipStream_t st);
 

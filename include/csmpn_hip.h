@@ -67,7 +67,8 @@ extern "C" {
                                        8 / 16 / 24 / 28 / 32 channels (two blocks, saved block inputs) and, since round 3,
                                        every Cl(2,0) / Cl(3,0) shape on the general kernels (one row tile per workgroup,
                                        per-workgroup copies of the gradient tensors + fixed-order sums; slower than the
-                                       default). Every other shape returns CSMPN_ERR_UNSUPPORTED. Also accepted by
+                                       default), 65..256 channels included (at most max(128 MiB, 16 copies) of them).
+                                       Every other shape returns CSMPN_ERR_UNSUPPORTED. Also accepted by
                                        csmpn_egcl_node_forward/backward and csmpn_cemlp_forward/backward, where it only
                                        selects the atomic-free parameter sums. */
 #define CSMPN_FLAG_SAVE_STATE 8u     /* csmpn_egcl_{edge,node}_{forward,backward}, csmpn_embed_cemlp_{forward,backward} (two-block
@@ -91,7 +92,9 @@ extern "C" {
                                       * regions are addressed by the call's row count. */
 
 /* One CEMLP block = Sequential(MVLinear, MVSiLU, SteerableGeometricProductLayer,
- * MVLayerNorm) (cegnn_utils.py:177-207). Pointers in reference layouts. */
+ * MVLayerNorm) (cegnn_utils.py:177-207). Pointers in reference layouts.
+ * Limits of every CEMLP / EGCL entry point: 1..CSMPN_MAX_BLOCKS blocks, out_features 1..256 (65..256: the wide
+ * row-tile kernel), in_features unbounded; out_features > 256 returns CSMPN_ERR_UNSUPPORTED. */
 typedef struct csmpn_block_params {
     int32_t in_features;
     int32_t out_features;
@@ -143,7 +146,8 @@ int csmpn_geometric_product_backward(const float* metric_host, int n, const floa
                                      const float* gout, float* ga, float* gb, int64_t rows, void* stream);
 
 /* Workspace (bytes) for a CEMLP of these blocks; covers packed weights and
- * per-launch scratch for any entry point below that takes this CEMLP. */
+ * per-launch scratch for any entry point below that takes this CEMLP (65..256 output channels: the wide kernel's
+ * global row-tile scratch with its parking region and, for n <= 3, the deterministic gradient copies). */
 size_t csmpn_cemlp_workspace_bytes(int n, const csmpn_block_params* blocks, int n_blocks);
 
 /* Saved block inputs (optional, every forward/backward pair below): the forward writes the

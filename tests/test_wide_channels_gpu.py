@@ -1,0 +1,277 @@
+"""GPU tests of the wide row-tile kernel (cemlp_wide.hpp): CEMLP / EGCL widths of 65..256 output channels.
+
+HIP against the float64 oracle (oracle/ref_path.py) with the bound of the parity suite: every tensor within
+max(1e-5, slack x the oracle's own float32 error) of the float64 truth, slack 4 on the definite metrics and 10 on the
+indefinite ones (well-conditioned inputs there), plus the element-wise bound. Also: the reference's own EGCL at 96 channels
+(tests/golden/egcl_wide_cl30.npz), the deterministic mode (n <= 3), the dispatch (csmpn_last_kernel) and one graph-captured
+training step of an md17 model at 96 channels.
+"""
+import copy
+import importlib
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import ref_path as O
+
+pytestmark = pytest.mark.gpu
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+TOL = 1e-5
+WIDE = "cemlp_wide_kernel"
+
+
+def relmax(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+def check(name, hip, truth, yard, slack):
+    """Per-tensor bound max(1e-5, slack x yardstick) and the element-wise bound of tests/test_hip_parity.py (restated)."""
+    err = relmax(hip, truth)
+    bound = max(TOL, slack * yard)
+    assert err <= bound, f"{name}: rel err {err:.3e} > {bound:.3e}"
+    a, b = np.asarray(hip, dtype=np.float64), np.asarray(truth, dtype=np.float64)
+    scale = max(np.abs(b).max(), 1e-30)
+    worst = float((np.abs(a - b) / (np.abs(b) + 0.1 * scale)).max())
+    assert worst <= 10 * bound, f"{name}: element-wise rel err {worst:.3e} > {10 * bound:.3e}"
+    return err
+
+
+def dev():
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    return torch.device("cuda:0")
+
+
+def _pkg():
+    return importlib.import_module("clifford-group-equivariant-simplicial-message-passing-networks_amd")
+
+
+class deterministic_aggregation:
+    def __enter__(self):
+        from csmpn_hip import ops
+        self.ops = ops
+        ops.set_deterministic(True)
+
+    def __exit__(self, *exc):
+        self.ops.set_deterministic(None)
+
+
+def _egcl_case(metric, N, E, C, hidden, aggr, seed, residual=True, attrs=True, neg_scale=None):
+    """Restatement of tests/test_hip_parity.py::_oracle_egcl_case, with or without the edge / node attributes.
+    Returns the HIP results (y, d/dh, parameter gradients) for the reproducibility check."""
+    slack = 4.0 if min(metric) > 0 else 10.0
+    pkg = _pkg()
+    oa, o32 = O.Algebra(metric, torch.float64), O.Algebra(metric, torch.float32)
+    h, ei, ea, na = O.synthetic_complex(o32, N, E, C, seed=seed)
+    if neg_scale is not None:
+        neg_bits = sum(1 << i for i, m in enumerate(metric) if m < 0)
+        mask = torch.from_numpy(((np.asarray(o32.t.index_to_bitmap) & neg_bits) != 0).astype(np.float32))
+        h = h * (1.0 - mask + neg_scale * mask)
+    ea_f, na_f = (ea.shape[1], na.shape[1]) if attrs else (0, 0)
+    if not attrs:
+        ea = na = None
+    gen = torch.Generator().manual_seed(seed + 1)
+    p = O.init_egcl_params(o32, C, hidden, C, ea_f, na_f, gen=gen, randomize=True)
+    layer = pkg.EGCL(pkg.CliffordAlgebra(tuple(metric)), C, hidden, C, edge_attr_features=ea_f, node_attr_features=na_f,
+                     residual=residual, aggr=aggr)
+    sd = layer.state_dict()
+    for k, v in p.items():
+        sd[k] = v
+    layer.load_state_dict(sd, strict=True)
+    layer = layer.to(dev())
+    hd = h.to(dev()).requires_grad_(True)
+    args = (ea.to(dev()), na.to(dev())) if attrs else ()
+    y = layer(hd, ei.to(dev()), *args)
+    gout = torch.randn(y.shape, generator=gen)
+    (y * gout.to(dev())).sum().backward()
+
+    def oracle(dtype):
+        q = {k: v.to(dtype).requires_grad_(True) for k, v in p.items()}
+        hh = h.to(dtype).requires_grad_(True)
+        yo = O.egcl(O.Algebra(metric, dtype), hh, ei, ea.to(dtype) if attrs else None, na.to(dtype) if attrs else None, q,
+                    aggr=aggr, residual=residual)
+        (yo * gout.to(dtype)).sum().backward()
+        return yo.detach(), hh.grad, {k: v.grad for k, v in q.items()}
+
+    y64, gh64, g64 = oracle(torch.float64)
+    y32, gh32, g32 = oracle(torch.float32)
+    got = {"y": y.detach().cpu().numpy(), "gh": hd.grad.cpu().numpy()}
+    check("y", got["y"], y64.numpy(), relmax(y32.numpy(), y64.numpy()), slack)
+    check("gh", got["gh"], gh64.numpy(), relmax(gh32.numpy(), gh64.numpy()), slack)
+    for k, prm in layer.named_parameters():
+        got[k] = prm.grad.cpu().numpy()
+        check("g." + k, got[k], g64[k].numpy(), relmax(g32[k].numpy(), g64[k].numpy()), slack)
+    return got
+
+
+# (metric, N, E, C, hidden, aggr, residual, attrs): ragged last channel tile (65), 96 / 128 / 256 channels, hidden != out
+# (48 -> 96 -> 48: blocks of different widths), every supported metric, with / without attributes, mean / sum, residual on / off
+CASES = [
+    ((1.0, 1.0, 1.0), 40, 150, 65, 65, "mean", True, True),
+    ((1.0, 1.0, 1.0), 30, 100, 96, 96, "sum", False, False),
+    ((1.0, 1.0, 1.0), 24, 80, 128, 128, "mean", True, True),
+    ((1.0, 1.0, 1.0), 10, 24, 256, 256, "sum", True, False),
+    ((1.0, 1.0, 1.0), 30, 90, 48, 96, "mean", False, True),
+    ((1.0, 1.0), 40, 120, 80, 80, "sum", True, True),
+    ((1.0, 1.0, 1.0, 1.0), 16, 40, 72, 72, "mean", True, False),
+    ((1.0, 1.0, 1.0, -1.0), 16, 40, 72, 72, "sum", False, True),
+    ((1.0,) * 5, 10, 24, 80, 80, "mean", True, True),
+    ((1.0, 1.0, 1.0, 1.0, -1.0), 10, 24, 80, 80, "sum", True, False),
+]
+
+
+@pytest.mark.parametrize("metric,N,E,C,hidden,aggr,residual,attrs", CASES,
+                         ids=[f"n{len(c[0])}{'m' if min(c[0]) < 0 else ''}-{c[3]}-{c[4]}-{c[5]}" for c in CASES])
+def test_wide_egcl_against_oracle(metric, N, E, C, hidden, aggr, residual, attrs):
+    _egcl_case(list(metric), N, E, C, hidden, aggr, seed=N + E + C, residual=residual, attrs=attrs,
+               neg_scale=0.02 if min(metric) < 0 else None)
+
+
+@pytest.mark.parametrize("C", [96, 128])
+@pytest.mark.parametrize("metric", [(1.0, 1.0, 1.0), (1.0, 1.0)], ids=["cl30", "cl20"])
+def test_wide_egcl_deterministic(metric, C):
+    """CSMPN_FLAG_DETERMINISTIC (n <= 3): the same bound, and two runs bit-identical."""
+    with deterministic_aggregation():
+        a = _egcl_case(list(metric), 20, 70, C, C, "mean", seed=C + 3)
+        b = _egcl_case(list(metric), 20, 70, C, C, "mean", seed=C + 3)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+@pytest.mark.parametrize("nl", [1, 2, 3, 4])
+def test_wide_standalone_cemlp(nl):
+    """Standalone CEMLP, 1..4 blocks, 200 input channels -> 96: output, d/dx and every parameter gradient."""
+    pkg = _pkg()
+    metric = [1.0, 1.0, 1.0]
+    in_f, hid, out_f, rows = 200, 96, 96, 150
+    oa, o32 = O.Algebra(metric, torch.float64), O.Algebra(metric, torch.float32)
+    gen = torch.Generator().manual_seed(70 + nl)
+    p = O.init_cemlp_params(o32, in_f, hid, out_f, n_layers=nl, gen=gen, randomize=True)
+    m = pkg.CEMLP(pkg.CliffordAlgebra(tuple(metric)), in_f, hid, out_f, n_layers=nl)
+    sd = m.state_dict()
+    for k, v in p.items():
+        sd[k] = v
+    m.load_state_dict(sd, strict=True)
+    m = m.to(dev())
+    x = torch.randn(rows, in_f, 8, generator=gen)
+    gout = torch.randn(rows, out_f, 8, generator=gen)
+    xd = x.to(dev()).requires_grad_(True)
+    y = m(xd)
+    (y * gout.to(dev())).sum().backward()
+
+    def oracle(alg, dtype):
+        q = {k: v.to(dtype).requires_grad_(True) for k, v in p.items()}
+        xx = x.to(dtype).requires_grad_(True)
+        yo = O.cemlp(alg, xx, q)
+        (yo * gout.to(dtype)).sum().backward()
+        return yo.detach().numpy(), xx.grad.numpy(), {k: v.grad.numpy() for k, v in q.items()}
+
+    y64, gx64, g64 = oracle(oa, torch.float64)
+    y32, gx32, g32 = oracle(o32, torch.float32)
+    check("y", y.detach().cpu().numpy(), y64, relmax(y32, y64), 4.0)
+    check("gx", xd.grad.cpu().numpy(), gx64, relmax(gx32, gx64), 4.0)
+    for k, prm in m.named_parameters():
+        check("g." + k, prm.grad.cpu().numpy(), g64[k], relmax(g32[k], g64[k]), 4.0)
+
+
+def test_wide_dispatch_names_the_wide_kernel():
+    """The four stages of a 96-channel EGCL run on this thread: every one names the wide kernel (csmpn_last_kernel)."""
+    from csmpn_hip import native, ops
+    pkg = _pkg()
+    C, N, E = 96, 30, 90
+    torch.manual_seed(3)
+    layer = pkg.EGCL(pkg.CliffordAlgebra((1.0, 1.0, 1.0)), C, C, C, edge_attr_features=6, node_attr_features=3).to(dev())
+    h, ei, ea, na = (t.to(dev()) for t in O.synthetic_complex(O.Algebra([1.0, 1.0, 1.0]), N, E, C, seed=4))
+    be, spec = ops.HipBackend, layer.spec()
+    csr = ops.get_csr(ei, N)
+    pe, pn = layer.edge_model.flat_params(), layer.node_model.flat_params()
+    names = []
+    agg, st_e = be.edge_forward(spec, csr, h, ea, pe)
+    names.append(native.lib().csmpn_last_kernel().decode())
+    out, st_n = be.node_forward(spec, csr.deg, h, agg, na, pn)
+    names.append(native.lib().csmpn_last_kernel().decode())
+    gh, g_agg, _, _ = be.node_backward(spec, csr.deg, h, agg, na, pn, torch.ones_like(out), False, st_n)
+    names.append(native.lib().csmpn_last_kernel().decode())
+    be.edge_backward(spec, csr, h, ea, pe, g_agg, gh, False, st_e)
+    names.append(native.lib().csmpn_last_kernel().decode())
+    torch.cuda.synchronize()
+    assert all(WIDE in n for n in names), names
+    assert "false>" in names[0] and "6 channel tiles on 6 waves" in names[0], names
+    assert "true>" in names[3] and "6 channel tiles on 4 waves" in names[3], names
+
+
+def _wide_fixture_param(name, shape):
+    """tests/golden/make_wide_golden.py::param_value (restated)."""
+    g = torch.Generator().manual_seed(sum((i + 1) * ord(c) for i, c in enumerate(name)) % (2 ** 31))
+    r = torch.randn(shape, generator=g, dtype=torch.float32)
+    leaf = name.split(".")[-1]
+    if leaf == "weight":
+        v = r / (float(shape[1]) ** 0.5) if len(shape) == 3 else 0.5 * r
+    elif leaf == "a" and "normalization" not in name:
+        v = 1.0 + 0.3 * r
+    else:
+        v = 0.3 * r
+    return v.half().float()
+
+
+def test_wide_egcl_against_reference_fixture():
+    """The reference's own EGCL at Cl(3,0), 96 channels (tests/golden/egcl_wide_cl30.npz, make_wide_golden.py): y, d/dh and
+    the parameter gradients (the weight matrices on the stored output-channel rows) within max(1e-5, 4 x the reference's
+    own float32 error)."""
+    pkg = _pkg()
+    g = np.load(os.path.join(GOLD, "egcl_wide_cl30.npz"))
+    C = 96
+    layer = pkg.EGCL(pkg.CliffordAlgebra((1.0, 1.0, 1.0)), C, C, C, edge_attr_features=6, node_attr_features=3, aggr="mean")
+    sd = layer.state_dict()
+    for k, prm in layer.named_parameters():
+        v = _wide_fixture_param(k, tuple(prm.shape))
+        assert float(v.double().sum()) == float(g["psum/" + k]), k
+        sd[k] = v
+    layer.load_state_dict(sd, strict=True)
+    layer = layer.to(dev())
+    t = lambda k: torch.from_numpy(g[k]).to(dev())
+    h = t("h").requires_grad_(True)
+    y = layer(h, t("edge_index"), t("edge_attr"), t("node_attr"))
+    (y * t("gout")).sum().backward()
+    rows = g["rows"]
+    got = {"y": y.detach().cpu().numpy(), "gh": h.grad.cpu().numpy()}
+    for k, prm in layer.named_parameters():
+        a = prm.grad.cpu().numpy()
+        got["g/" + k] = a[rows] if a.ndim == 3 and a.shape[0] == C else a
+    assert set(got) == {k[4:] for k in g.files if k.startswith("f64/")}
+    for k, v in got.items():
+        check(k, v, g["f64/" + k], float(g["yard/" + k]), 4.0)
+
+
+def test_wide_md17_graphed_step_matches_eager():
+    """An md17 model at num_hidden = 96 (every EGCL, the embeddings' CEMLPs and the head's CEMLP on the wide kernel): one
+    training step replayed from a captured graph gives the loss and the parameter gradients of the eager step."""
+    from csmpn.data.complexes import SimplicialBatch
+    from csmpn.models import simplicial_mpnn as M
+    from csmpn_hip.graphed import GraphedTrainStep
+    g = np.load(os.path.join(GOLD, "model_md17.npz"))
+    batch = SimplicialBatch(**{k[2:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("b/")}).to(dev())
+    torch.manual_seed(11)
+    model_e = M.MD17SimplicialMPNN(num_hidden=96, num_layers=2).to(dev())
+    model_g = copy.deepcopy(model_e)
+    lr = 1e-2
+    opt_e = torch.optim.SGD(model_e.parameters(), lr=lr)
+    opt_g = torch.optim.SGD(model_g.parameters(), lr=lr)
+    before = [p.detach().clone() for p in model_e.parameters()]
+    loss_e, _ = model_e(batch)
+    opt_e.zero_grad(set_to_none=True)
+    loss_e.backward()
+    grads_e = [p.grad.detach().clone() for p in model_e.parameters()]
+    gs = GraphedTrainStep(model_g, opt_g, batch, ["loc", "vel", "y"])
+    loss_g = gs.step({"loc": batch.loc.clone(), "vel": batch.vel.clone(), "y": batch.y.clone()})
+    torch.cuda.synchronize()
+    le, lg = float(loss_e.detach()), float(loss_g.detach())
+    assert abs(le - lg) <= 1e-4 * max(abs(le), 1e-3), (le, lg)
+    # SGD: the graphed step moved every parameter by -lr x its gradient
+    for b, pg, ge in zip(before, model_g.parameters(), grads_e):
+        gg = (b - pg.detach()) / lr
+        scale = max(float(ge.abs().max()), 1e-6)
+        assert float((gg - ge).abs().max()) <= 1e-3 * scale + 1e-5, float((gg - ge).abs().max()) / scale
