@@ -2,8 +2,11 @@
 
 csmpn_cemlp_workspace_bytes and csmpn_cemlp_saved_floats cover the wide bindings and grow with the width; the deterministic
 copies of the gradient tensors (n <= 3) are bounded instead of 512 copies of a slice that grows with O^2; widths above 256
-still report no workspace-free plan (the launch returns CSMPN_ERR_UNSUPPORTED, checked on the GPU)."""
+still report no workspace-free plan (the launch returns CSMPN_ERR_UNSUPPORTED: tests/test_wide_channels_gpu.py::
+test_wide_width_boundaries_and_refusal_above_256_channels)."""
 import pytest
+
+from wide_helpers import slice_bytes
 
 
 def _node_binding(n, C, attr=3, nblk=2):
@@ -22,12 +25,8 @@ def _sizes(n, C, rows=1000):
 
 
 def _slice_bytes(n, C, attr=3):
-    """Floats of one copy of the two blocks' gradient tensors (mirror_floats_of in csrc/capi.hip), in bytes."""
-    G, P = n + 1, {2: 10, 3: 20}[n]
-    tot = 0
-    for I in (2 * C + attr, C):
-        tot += (G * C * I + 2 * G * C * C + 3 * C + 3 * C * G + C * P + 3) // 4 * 4
-    return 4 * tot
+    """Bytes of one copy of the gradient tensors of a node model's two blocks (tests/wide_helpers.py::slice_bytes)."""
+    return slice_bytes(n, [(2 * C + attr, C), (C, C)])
 
 
 @pytest.mark.parametrize("n", [2, 3, 4, 5])

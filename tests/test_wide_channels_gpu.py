@@ -3,8 +3,9 @@
 HIP against the float64 oracle (oracle/ref_path.py) with the bound of the parity suite: every tensor within
 max(1e-5, slack x the oracle's own float32 error) of the float64 truth, slack 4 on the definite metrics and 10 on the
 indefinite ones (well-conditioned inputs there), plus the element-wise bound. Also: the reference's own EGCL at 96 channels
-(tests/golden/egcl_wide_cl30.npz), the deterministic mode (n <= 3), the dispatch (csmpn_last_kernel) and one graph-captured
-training step of an md17 model at 96 channels.
+(tests/golden/egcl_wide_cl30.npz), the deterministic mode (n <= 3), the dispatch (csmpn_last_kernel: kernel, waves, tile placement), the
+boundaries of the width range (64 / 65 / 256 / 257 channels) and one graph-captured training step of an md17 model at 96
+channels. Sizes at which a workgroup walks many row tiles: tests/test_wide_multitile_gpu.py.
 """
 import copy
 import importlib
@@ -15,6 +16,7 @@ import pytest
 import torch
 
 from oracle import ref_path as O
+from wide_helpers import LDS_BYTES, egcl_widths, wide_fixture_param, wide_tile_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -179,8 +181,8 @@ def test_wide_standalone_cemlp(nl):
 
 def test_wide_dispatch_names_the_wide_kernel():
     """The four stages of a 96-channel EGCL run on this thread: every one names the wide kernel (csmpn_last_kernel)."""
+    pkg = _pkg()   # first: importing the package puts csmpn_hip on the path
     from csmpn_hip import native, ops
-    pkg = _pkg()
     C, N, E = 96, 30, 90
     torch.manual_seed(3)
     layer = pkg.EGCL(pkg.CliffordAlgebra((1.0, 1.0, 1.0)), C, C, C, edge_attr_features=6, node_attr_features=3).to(dev())
@@ -203,18 +205,72 @@ def test_wide_dispatch_names_the_wide_kernel():
     assert "true>" in names[3] and "6 channel tiles on 4 waves" in names[3], names
 
 
-def _wide_fixture_param(name, shape):
-    """tests/golden/make_wide_golden.py::param_value (restated)."""
-    g = torch.Generator().manual_seed(sum((i + 1) * ord(c) for i, c in enumerate(name)) % (2 ** 31))
-    r = torch.randn(shape, generator=g, dtype=torch.float32)
-    leaf = name.split(".")[-1]
-    if leaf == "weight":
-        v = r / (float(shape[1]) ** 0.5) if len(shape) == 3 else 0.5 * r
-    elif leaf == "a" and "normalization" not in name:
-        v = 1.0 + 0.3 * r
-    else:
-        v = 0.3 * r
-    return v.half().float()
+def _stage_names(metric, C, N=30, E=90):
+    """csmpn_last_kernel after each of the four stages of one EGCL layer, run on this thread."""
+    pkg = _pkg()   # first: importing the package puts csmpn_hip on the path
+    from csmpn_hip import native, ops
+    torch.manual_seed(3)
+    layer = pkg.EGCL(pkg.CliffordAlgebra(tuple(metric)), C, C, C, edge_attr_features=6, node_attr_features=3).to(dev())
+    h, ei, ea, na = (t.to(dev()) for t in O.synthetic_complex(O.Algebra(list(metric)), N, E, C, seed=4))
+    be, spec = ops.HipBackend, layer.spec()
+    csr = ops.get_csr(ei, N)
+    pe, pn = layer.edge_model.flat_params(), layer.node_model.flat_params()
+    last = lambda: native.lib().csmpn_last_kernel().decode()
+    names = {}
+    agg, st_e = be.edge_forward(spec, csr, h, ea, pe)
+    names["edge_fwd"] = last()
+    out, st_n = be.node_forward(spec, csr.deg, h, agg, na, pn)
+    names["node_fwd"] = last()
+    gh, g_agg, _, _ = be.node_backward(spec, csr.deg, h, agg, na, pn, torch.ones_like(out), False, st_n)
+    names["node_bwd"] = last()
+    be.edge_backward(spec, csr, h, ea, pe, g_agg, gh, False, st_e)
+    names["edge_bwd"] = last()
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(gh).all())
+    return names
+
+
+@pytest.mark.parametrize("metric,C", [((1.0, 1.0, 1.0), 96), ((1.0, 1.0), 80), ((1.0, 1.0), 128), ((1.0, 1.0, 1.0), 65)],
+                         ids=["cl30-96", "cl20-80", "cl20-128", "cl30-65"])
+def test_wide_dispatch_names_the_tile_placement(metric, C):
+    """The row tile lives in LDS exactly when its footprint (wide_layout, restated in tests/wide_helpers.py) fits in 160 KB,
+    otherwise in the per-workgroup global scratch; both go through one flat-pointer instantiation, so only the name
+    tells. Cl(3,0) at 96 channels: edge forward 155 328 bytes (LDS), node forward 203 904 (global scratch)."""
+    n = len(metric)
+    we, wn = egcl_widths(C, C, C)
+    foot = {"edge_fwd": wide_tile_bytes(n, we, False, stage_rowlen=C * (1 << n)), "node_fwd": wide_tile_bytes(n, wn, False),
+            "node_bwd": wide_tile_bytes(n, wn, True), "edge_bwd": wide_tile_bytes(n, we, True)}
+    names = _stage_names(metric, C)
+    for stage, name in names.items():
+        assert WIDE in name, names
+        where = "tiles in LDS)" if foot[stage] <= LDS_BYTES else "tiles in global scratch)"
+        assert name.endswith(where), (stage, foot[stage], name)
+    if C == 96:
+        assert foot["edge_fwd"] <= LDS_BYTES < foot["node_fwd"], foot   # one shape on each side in one layer
+
+
+def test_wide_width_boundaries_and_refusal_above_256_channels():
+    """64 output channels stay on the general row-tile kernel, 65 take the wide one, 256 work, 257 make the launch return
+    CSMPN_ERR_UNSUPPORTED - and the refusal leaves the device usable: a 96-channel case runs (and matches the oracle) in the
+    same process afterwards."""
+    pkg = _pkg()
+    from csmpn_hip import native
+    n64, n65 = _stage_names((1.0, 1.0, 1.0), 64), _stage_names((1.0, 1.0, 1.0), 65)
+    assert all("cemlp_kernel<" in v and WIDE not in v for v in n64.values()), n64
+    assert all(WIDE in v for v in n65.values()), n65
+    n256 = _stage_names((1.0, 1.0, 1.0), 256, N=10, E=24)
+    assert all(WIDE in v and "16 channel tiles" in v for v in n256.values()), n256
+    m = pkg.CEMLP(pkg.CliffordAlgebra((1.0, 1.0, 1.0)), 40, 257, 257, n_layers=1).to(dev())
+    x = torch.randn(20, 40, 8, generator=torch.Generator().manual_seed(1)).to(dev())
+    with pytest.raises(native.CsmpnError, match=f"error {native.ERR_UNSUPPORTED}: .*257"):
+        m(x)
+    torch.cuda.synchronize()
+    layer = pkg.EGCL(pkg.CliffordAlgebra((1.0, 1.0, 1.0)), 257, 257, 257, edge_attr_features=6, node_attr_features=3).to(dev())
+    h, ei, ea, na = (t.to(dev()) for t in O.synthetic_complex(O.Algebra([1.0, 1.0, 1.0]), 10, 24, 257, seed=2))
+    with pytest.raises(native.CsmpnError, match=f"error {native.ERR_UNSUPPORTED}: "):
+        layer(h, ei, ea, na)
+    torch.cuda.synchronize()
+    _egcl_case([1.0, 1.0, 1.0], 30, 100, 96, 96, "mean", seed=9)
 
 
 def test_wide_egcl_against_reference_fixture():
@@ -227,7 +283,7 @@ def test_wide_egcl_against_reference_fixture():
     layer = pkg.EGCL(pkg.CliffordAlgebra((1.0, 1.0, 1.0)), C, C, C, edge_attr_features=6, node_attr_features=3, aggr="mean")
     sd = layer.state_dict()
     for k, prm in layer.named_parameters():
-        v = _wide_fixture_param(k, tuple(prm.shape))
+        v = wide_fixture_param(k, tuple(prm.shape))
         assert float(v.double().sum()) == float(g["psum/" + k]), k
         sd[k] = v
     layer.load_state_dict(sd, strict=True)
