@@ -1,7 +1,7 @@
 // (row, channel)-per-lane kernel instantiations (cemlp_cl.hpp) for one algebra. Included by k_cl_<tag>.hip
 // with CSMPN_ALG_N, CSMPN_ALG_NEG and CSMPN_ALG_TAG defined.
 #include "cemlp_cl.hpp"
-#include "cl_launch.hpp"
+#include "launch.hpp"
 
 namespace csmpn {
 namespace {

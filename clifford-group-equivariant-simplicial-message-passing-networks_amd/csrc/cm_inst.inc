@@ -3,7 +3,7 @@
 #include "cemlp_cm.hpp"
 #include "cemlp_cmb.hpp"
 #include "cemlp_cmp.hpp"
-#include "cm_launch.hpp"
+#include "launch.hpp"
 
 namespace csmpn {
 namespace {

@@ -1,7 +1,7 @@
 // 16-row-tile MFMA-mixing kernels for Cl(3,0), 32 channels (cemlp_pq.hpp): EGCL edge (6 attribute channels) and node (3) programs and
 // the standalone CEMLPs of the md17 model (simplex embeddings 60 -> 32 and 90 -> 32 -> 32, head 32 -> 32: md17_cssmpnn.py:85-120,165-176).
 #include "cemlp_pq.hpp"
-#include "pq_launch.hpp"
+#include "launch.hpp"
 
 namespace csmpn {
 namespace {

@@ -1,9 +1,10 @@
-// Standalone forms of the four small Clifford layers (C-ABI in include/csmpn_hip.h):
+// Standalone forms of the small Clifford layers (C-ABI in include/csmpn_hip.h):
 //   csmpn_mvsilu_forward / _backward        MVSiLU, invariant "mag2"          cegnn_utils.py:53-83
 //   csmpn_mvnorm_forward / _backward        NormalizationLayer                cegnn_utils.py:34-51
 //   csmpn_mvlayernorm_forward / _backward   MVLayerNorm                       cegnn_utils.py:86-96
 //   csmpn_wgp_forward / _backward           the path-weighted geometric product of
 //                                           SteerableGeometricProductLayer    cegnn_utils.py:126-152
+//   csmpn_mvlinear_forward / _backward      MVLinear                          cegnn_utils.py:287-338
 // Inside a CEMLP these steps are fused into the row programs (cemlp_*.hpp); no reference model calls
 // the layers on their own, so these kernels are the plain HBM-bound form: one thread per (row,
 // channel) with the channel's D blades in registers (compile-time sign tables, algebra.hpp), rows of a
@@ -12,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 
 #include "../../include/csmpn_hip.h"
 #include "algebra.hpp"
@@ -368,6 +370,108 @@ int run(const float* metric, int n, Op op, bool bwd, const Args& A, void* stream
     if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "standalone layer launch: %s", hipGetErrorString(e));
     return CSMPN_OK;
 }
+
+// ----------------------------------------------------------------------------- standalone MVLinear
+// (cegnn_utils.py:287-338) for callers outside a CEMLP (projection heads, feature embeddings):
+//   y[b,o,d] = sum_i W[o,i,grade(d)] x[b,i,d]  (+ bias[o] on blade 0);  W [O,I,G] or [O,I].
+// HBM-bound ([rows, I, D] in, [rows, O, D] out); one thread per output element, blade index
+// fastest so that a wave reads / writes whole rows; the grade table depends on n only.
+struct MvLinDesc {
+    const float *x, *w, *b, *gy;
+    float *y, *gx, *gw, *gb;
+    long rows;
+    int I, O, D, G, sub;
+    unsigned char grade[32];
+};
+
+__global__ void mvlinear_fwd_kernel(const MvLinDesc P) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long total = P.rows * P.O * P.D;
+    if (e >= total) return;
+    const int d = (int)(e % P.D);
+    const int o = (int)((e / P.D) % P.O);
+    const long r = e / ((long)P.D * P.O);
+    const int g = P.sub ? P.grade[d] : 0, ws = P.sub ? P.G : 1;
+    const float* xr = P.x + r * P.I * P.D + d;
+    const float* wr = P.w + (long)o * P.I * ws + g;
+    float acc = (P.b && d == 0) ? P.b[o] : 0.f;
+    for (int i = 0; i < P.I; ++i) acc = fmaf(wr[i * ws], xr[(long)i * P.D], acc);
+    P.y[e] = acc;
+}
+
+// d/dx[b,i,d] = sum_o gy[b,o,d] W[o,i,grade(d)]
+__global__ void mvlinear_bwd_x_kernel(const MvLinDesc P) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long total = P.rows * P.I * P.D;
+    if (e >= total) return;
+    const int d = (int)(e % P.D);
+    const int i = (int)((e / P.D) % P.I);
+    const long r = e / ((long)P.D * P.I);
+    const int g = P.sub ? P.grade[d] : 0, ws = P.sub ? P.G : 1;
+    const float* gr = P.gy + r * P.O * P.D + d;
+    const float* wc = P.w + (long)i * ws + g;
+    float acc = 0.f;
+    for (int o = 0; o < P.O; ++o) acc = fmaf(wc[(long)o * P.I * ws], gr[(long)o * P.D], acc);
+    P.gx[e] = acc;
+}
+
+// d/dW[o,i,g] += sum_{rows, d in g} gy[b,o,d] x[b,i,d];  d/dbias[o] += sum_rows gy[b,o,0].
+// Thread = one weight (or bias) element, blockIdx.y = a slab of rows it walks (x / gy rows of a slab are L1 / L2 hits:
+// a wave's 64 elements share o or neighbour it); one atomic per element and slab. The slab is sized so that the launch
+// has ~512 workgroups (8..64 rows): the first version gave every workgroup ALL elements of a 4-row slab - 235 workgroups x 1 152
+// atomics onto the same 1 152 addresses took 28 us on the 940 rows of an md17 batch.
+inline int mvlinear_slab(long rows, int elem_blocks) {
+    long slabs = 512 / elem_blocks;
+    if (slabs < 1) slabs = 1;
+    long s = (rows + slabs - 1) / slabs;
+    return (int)(s < 8 ? 8 : (s > 64 ? 64 : s));
+}
+__global__ void mvlinear_bwd_w_kernel(const MvLinDesc P, int slab) {
+    const long r0 = (long)blockIdx.y * slab;
+    const long r1 = r0 + slab < P.rows ? r0 + slab : P.rows;
+    const int ws = P.sub ? P.G : 1;
+    const int nw = P.O * P.I * ws;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nw + P.O) return;
+    float acc = 0.f;
+    if (e < nw) {
+        if (!P.gw) return;
+        const int g = e % ws, i = (e / ws) % P.I, o = e / (ws * P.I);
+        // blades of grade g are contiguous (blade order: by grade): [d0, d1)
+        int d0 = 0, d1 = P.D;
+        if (P.sub) {
+            while (P.grade[d0] != g) ++d0;
+            d1 = d0;
+            while (d1 < P.D && P.grade[d1] == g) ++d1;
+        }
+        for (long r = r0; r < r1; ++r) {
+            const float* gr = P.gy + (r * P.O + o) * P.D;
+            const float* xr = P.x + (r * P.I + i) * P.D;
+            for (int d = d0; d < d1; ++d) acc = fmaf(gr[d], xr[d], acc);
+        }
+        atomicAdd(P.gw + e, acc);
+    } else if (P.gb) {
+        const int o = e - nw;
+        for (long r = r0; r < r1; ++r) acc += P.gy[(r * P.O + o) * P.D];
+        atomicAdd(P.gb + o, acc);
+    }
+}
+
+int mvlinear_desc(int n, long rows, int I, int O, int sub, MvLinDesc& P) {
+    if (n < 1 || n > 5) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "MVLinear: n=%d not in 1..5", n);
+    if (I < 1 || O < 1 || rows < 0) return csmpn_fail(CSMPN_ERR_INVALID, "MVLinear: bad sizes rows=%ld I=%d O=%d", rows, I, O);
+    memset(&P, 0, sizeof(P));
+    P.rows = rows; P.I = I; P.O = O; P.D = 1 << n; P.G = n + 1; P.sub = sub ? 1 : 0;
+    // blade order: by grade, then lexicographic (metric.py:18-29): the grade of index d is the
+    // grade whose cumulative binomial range contains d
+    int d = 0, c = 1;   // c = C(n, g)
+    for (int g = 0; g <= n; ++g) {
+        for (int k = 0; k < c; ++k) P.grade[d++] = (unsigned char)g;
+        c = c * (n - g) / (g + 1);
+    }
+    return CSMPN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -420,5 +524,49 @@ int csmpn_wgp_backward(const float* metric_host, int n, const float* z, const fl
     Args A{z, r, weight, nullptr, gy, (long)rows, channels, gz, gr, g_weight, nullptr};
     return run(metric_host, n, OP_WGP, true, A, stream);
 }
+
+int csmpn_mvlinear_forward(int n, const float* x, const float* weight, const float* bias, int64_t rows,
+                           int32_t in_features, int32_t out_features, int32_t subspaces, float* y, void* stream) {
+    MvLinDesc P;
+    int rc = mvlinear_desc(n, (long)rows, in_features, out_features, subspaces, P);
+    if (rc) return rc;
+    if (rows == 0) return CSMPN_OK;
+    if (!x || !weight || !y) return csmpn_fail(CSMPN_ERR_INVALID, "MVLinear: null pointer");
+    P.x = x; P.w = weight; P.b = bias; P.y = y;
+    const long total = (long)rows * out_features * P.D;
+    const unsigned block = 256, grid = (unsigned)((total + block - 1) / block);
+    hipLaunchKernelGGL(mvlinear_fwd_kernel, dim3(grid), dim3(block), 0, (hipStream_t)stream, P);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "hipGetLastError(): %s", hipGetErrorString(e));
+    return CSMPN_OK;
+}
+
+int csmpn_mvlinear_backward(int n, const float* x, const float* weight, const float* gy, int64_t rows,
+                            int32_t in_features, int32_t out_features, int32_t subspaces, float* gx, float* g_weight,
+                            float* g_bias, void* stream) {
+    MvLinDesc P;
+    int rc = mvlinear_desc(n, (long)rows, in_features, out_features, subspaces, P);
+    if (rc) return rc;
+    if (rows == 0) return CSMPN_OK;
+    if (!x || !weight || !gy) return csmpn_fail(CSMPN_ERR_INVALID, "MVLinear: null pointer");
+    P.x = x; P.w = weight; P.gy = gy; P.gx = gx; P.gw = g_weight; P.gb = g_bias;
+    const unsigned block = 256;
+    if (gx) {
+        const long total = (long)rows * in_features * P.D;
+        hipLaunchKernelGGL(mvlinear_bwd_x_kernel, dim3((unsigned)((total + block - 1) / block)), dim3(block), 0,
+                           (hipStream_t)stream, P);
+    }
+    if (g_weight || g_bias) {   // the bias gradient comes from the same kernel: a frozen weight must not silence it
+        const int nelem = out_features * in_features * (P.sub ? P.G : 1) + out_features;
+        const unsigned eb = (unsigned)((nelem + block - 1) / block);
+        const int slab = mvlinear_slab(rows, (int)eb);
+        hipLaunchKernelGGL(mvlinear_bwd_w_kernel, dim3(eb, (unsigned)((rows + slab - 1) / slab)), dim3(block), 0,
+                           (hipStream_t)stream, P, slab);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "hipGetLastError(): %s", hipGetErrorString(e));
+    return CSMPN_OK;
+}
+
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // 16-row-tile MFMA-mixing kernel instantiations (cemlp_pg.hpp) for one algebra. Included by k_pg_<tag>.hip with
 // CSMPN_ALG_N, CSMPN_ALG_NEG and CSMPN_ALG_TAG defined.
 #include "cemlp_pg.hpp"
-#include "pg_launch.hpp"
+#include "launch.hpp"
 
 namespace csmpn {
 namespace {

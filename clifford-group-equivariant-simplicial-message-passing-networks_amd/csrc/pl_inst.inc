@@ -1,7 +1,7 @@
 // Parity-lane kernel instantiations (cemlp_pl.hpp) for one algebra. Included by k_pl_<tag>.hip
 // with CSMPN_ALG_N, CSMPN_ALG_NEG and CSMPN_ALG_TAG defined.
 #include "cemlp_pl.hpp"
-#include "pl_launch.hpp"
+#include "launch.hpp"
 
 namespace csmpn {
 namespace {

@@ -1,7 +1,7 @@
 // Wide parity-lane kernel instantiations (cemlp_plw.hpp) for one algebra. Included by k_plw_<tag>.hip
 // with CSMPN_ALG_N, CSMPN_ALG_NEG and CSMPN_ALG_TAG defined.
 #include "cemlp_plw.hpp"
-#include "plw_launch.hpp"
+#include "launch.hpp"
 
 namespace csmpn {
 namespace {

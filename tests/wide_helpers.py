@@ -5,7 +5,7 @@ can say what the library should have chosen without asking the library."""
 import torch
 
 LDS_BYTES = 160 * 1024      # launch.hpp: kMaxLdsBytes
-GRID_CAP = 256              # capi.hip: kGlobalTileGrid (plan.grid_cap of every wide plan)
+GRID_CAP = 256              # plan.hip: kGlobalTileGrid (plan.grid_cap of every wide plan)
 ROWS_PER_TILE = 16
 
 
@@ -25,7 +25,7 @@ def wide_fixture_param(name, shape):
 
 def slice_bytes(n, widths):
     """Bytes of one copy of the gradient tensors of a CEMLP with blocks `widths` = [(in, out), ...] over an algebra with
-    n <= 3 generators (mirror_floats_of in csrc/capi.hip): W1 [O, I, G], WR and WL [O, O, G], b1, bL, ln_a [O], the MVSiLU
+    n <= 3 generators (mirror_floats_of in csrc/plan.hip): W1 [O, I, G], WR and WL [O, O, G], b1, bL, ln_a [O], the MVSiLU
     a / b and the normalization a [O, G], the path weights [O, P]; every block rounded up to 4 floats."""
     G, P = n + 1, {2: 10, 3: 20}[n]
     tot = 0
@@ -40,7 +40,7 @@ def wide_det_groups(n, widths):
 
 
 def wide_tile_bytes(n, widths, bwd, stage_rowlen=0, use_saved=True):
-    """Footprint of one row tile of the wide kernel (wide_layout in csrc/capi.hip): 16 rows, channel stride 16 D + 4 floats;
+    """Footprint of one row tile of the wide kernel (wide_layout in csrc/plan.hip): 16 rows, channel stride 16 D + 4 floats;
     the input tile (the forward's block outputs replace it, so it is as large as the widest of them; the backward without
     saved inputs adds up to two block-output tiles), the z tile, the gradient tile (forward: one buffer for both, at least the
     dense [16, stage_rowlen] staging of the edge stage), the LayerNorm scratch, the row indices and the parking region of

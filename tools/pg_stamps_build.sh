@@ -9,5 +9,5 @@ F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=fast -Wno-unused-val
 hipcc $F -fno-slp-vectorize -DCSMPN_STAMPS -c k_pg_n5.hip -o $B/k_pg_n5_stamps.o &
 [ $B/capi_stamps.o -nt capi.hip ] || hipcc $F -DCSMPN_STAMPS -c capi.hip -o $B/capi_stamps.o &
 wait
-hipcc -shared -fPIC --offload-arch=gfx950 $B/capi_stamps.o $B/csr.o $B/k_n2.o $B/k_n3.o $B/k_n4.o $B/k_n4m.o $B/k_n5.o $B/k_n5m.o $B/glue.o $B/layers.o $B/k_cl_n3.o $B/k_cm_n3.o $B/k_pl_n5.o $B/k_pl_n5m.o $B/k_plw_n5.o $B/k_plw_n5m.o $B/k_pg_n5_stamps.o $B/k_pg_n5m.o -o ../../tools/_bin/libcsmpn_hip_stamps.so
+hipcc -shared -fPIC --offload-arch=gfx950 $B/capi_stamps.o $B/plan.o $B/dispatch.o $B/csr.o $B/k_n2.o $B/k_n3.o $B/k_n4.o $B/k_n4m.o $B/k_n5.o $B/k_n5m.o $B/glue.o $B/layers.o $B/k_cl_n3.o $B/k_cm_n3.o $B/k_pl_n5.o $B/k_pl_n5m.o $B/k_plw_n5.o $B/k_plw_n5m.o $B/k_pg_n5_stamps.o $B/k_pg_n5m.o -o ../../tools/_bin/libcsmpn_hip_stamps.so
 echo built tools/_bin/libcsmpn_hip_stamps.so
