@@ -84,6 +84,32 @@ def test_geometric_product(pkg, golden_dir, name):
     check("gp.gb", b.grad.cpu().numpy(), b64.grad.numpy())
 
 
+N4_METRICS = {"cl40": (1.0, 1.0, 1.0, 1.0), "cl31": (1.0, 1.0, 1.0, -1.0)}
+
+
+@pytest.mark.parametrize("rows", [1, 63, 1031])
+@pytest.mark.parametrize("name", list(N4_METRICS))
+def test_geometric_product_n4(pkg, name, rows):
+    """csmpn_geometric_product_forward / _backward on Cl(4,0) and Cl(3,1) (launch_gp_n4 / launch_gp_n4m; no fixture of the
+    reference exists for n = 4): one row, a partial wave, several workgroups with a row tail, against the dense Cayley einsum
+    of the oracle in float64."""
+    metric = N4_METRICS[name]
+    alg = pkg.CliffordAlgebra(metric).to(dev())
+    assert alg.hip_supported
+    gen = torch.Generator().manual_seed(40 + rows)
+    a, b, w = (torch.randn(rows, 16, generator=gen) for _ in range(3))
+    ad, bd = a.to(dev()).requires_grad_(True), b.to(dev()).requires_grad_(True)
+    out = alg.geometric_product(ad, bd)
+    (out * w.to(dev())).sum().backward()
+    oa = O.Algebra(list(metric), torch.float64)
+    a64, b64 = a.double().requires_grad_(True), b.double().requires_grad_(True)
+    out64 = O.geometric_product(oa, a64, b64)
+    (out64 * w.double()).sum().backward()
+    check(f"gp.{name}", out.detach().cpu().numpy(), out64.detach().numpy())
+    check(f"gp.{name}.ga", ad.grad.cpu().numpy(), a64.grad.numpy())
+    check(f"gp.{name}.gb", bd.grad.cpu().numpy(), b64.grad.numpy())
+
+
 def _set_block_params(seq, p, prefix):
     m = {"0.weight": seq[0].weight, "0.bias": seq[0].bias, "1.a": seq[1].a, "1.b": seq[1].b, "2.weight": seq[2].weight,
          "2.normalization.a": seq[2].normalization.a, "2.linear_right.weight": seq[2].linear_right.weight,
@@ -174,6 +200,37 @@ def test_mvlinear_standalone_large(pkg):
     check("big.gx", x.grad.cpu().numpy(), x64.grad.numpy())
     check("big.gW", m.weight.grad.cpu().numpy(), w64.grad.numpy())
     check("big.gb", m.bias.grad.cpu().numpy(), b64.grad.numpy())
+
+
+@pytest.mark.parametrize("subspaces,bias", [(True, True), (False, True), (True, False)], ids=["sub-bias", "nosub", "nobias"])
+@pytest.mark.parametrize("name", list(N4_METRICS))
+def test_mvlinear_standalone_n4(pkg, name, subspaces, bias):
+    """csmpn_mvlinear_* at D = 16 (five grades: 1, 4, 6, 4, 1 blades), 13 -> 7 channels, 1031 rows, per-grade and shared
+    weights, with and without the bias: the float64 einsum form of test_mvlinear_standalone_large."""
+    alg = pkg.CliffordAlgebra(N4_METRICS[name])
+    m = pkg.MVLinear(alg, 13, 7, subspaces=subspaces, bias=bias).to(dev())
+    gen = torch.Generator().manual_seed(7)
+    with torch.no_grad():   # away from the initialiser's zeros
+        for p in m.parameters():
+            p.copy_(torch.randn(p.shape, generator=gen))
+    x = torch.randn(1031, 13, 16, generator=gen).to(dev()).requires_grad_(True)
+    gout = torch.randn(1031, 7, 16, generator=gen).to(dev())
+    y = m(x)
+    (y * gout).sum().backward()
+    grades = torch.tensor([0] + [1] * 4 + [2] * 6 + [3] * 4 + [4])
+    w64 = m.weight.detach().cpu().double().requires_grad_(True)
+    x64 = x.detach().cpu().double().requires_grad_(True)
+    wfull = w64[..., grades] if subspaces else w64[..., None].expand(-1, -1, 16)
+    y64 = torch.einsum("bmi,nmi->bni", x64, wfull)
+    if bias:
+        b64 = m.bias.detach().cpu().double().requires_grad_(True)
+        y64 = y64 + torch.nn.functional.pad(b64, (0, 15))
+    (y64 * gout.cpu().double()).sum().backward()
+    check("n4.y", y.detach().cpu().numpy(), y64.detach().numpy())
+    check("n4.gx", x.grad.cpu().numpy(), x64.grad.numpy())
+    check("n4.gW", m.weight.grad.cpu().numpy(), w64.grad.numpy())
+    if bias:
+        check("n4.gb", m.bias.grad.cpu().numpy(), b64.grad.numpy())
 
 
 def test_mvlinear_frozen_weight_still_gets_bias_grad(pkg):

@@ -79,15 +79,28 @@ def test_small_layers_hip(pkg, golden_dir, name, C, layer):
     assert ops.small_layer_launches() > before, "the standalone HIP entry point did not run"
 
 
+# no tables_*.npz was recorded for n = 4: the metric is given directly
+N4_METRICS = {"cl40": (1.0, 1.0, 1.0, 1.0), "cl31": (1.0, 1.0, 1.0, -1.0)}
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,C,rows", [("cl30", 28, 1000), ("cl50", 28, 257), ("cl41", 8, 1031), ("cl20", 40, 513)])
+@pytest.mark.parametrize("name,C,rows", [("cl30", 28, 1000), ("cl50", 28, 257), ("cl41", 8, 1031), ("cl20", 40, 513),
+                                         # Cl(4,0) / Cl(3,1): Alg<4,0u> / Alg<4,0x8u> of layers.hip
+                                         ("cl40", 12, 513), ("cl31", 20, 257),
+                                         # the documented maximum of 256 channels (one row per MVLayerNorm workgroup), and 129:
+                                         # one row per workgroup with 127 idle lanes; 37 x 129 elements leave the last
+                                         # workgroup of the other three kernels ragged
+                                         ("cl30", 256, 37), ("cl40", 256, 21), ("cl20", 129, 37), ("cl40", 129, 37)])
 @pytest.mark.parametrize("layer", LAYERS)
 def test_small_layers_hip_vs_host_fp64(pkg, golden_dir, name, C, rows, layer):
-    """Shapes beyond the fixtures (many workgroups, row tails, the hulls width): the HIP entry points against the host
-    formulation of the same module in float64 on the CPU (forward, d/dx, parameter gradients)."""
+    """Shapes beyond the fixtures (many workgroups, row tails, the hulls width, n = 4, the channel limit): the HIP entry
+    points against the host formulation of the same module in float64 on the CPU (forward, d/dx, parameter gradients)."""
     import copy
-    t = np.load(os.path.join(golden_dir, f"tables_{name}.npz"))
-    metric = tuple(t["metric"].tolist())
+    if name in N4_METRICS:
+        metric = N4_METRICS[name]
+    else:
+        t = np.load(os.path.join(golden_dir, f"tables_{name}.npz"))
+        metric = tuple(t["metric"].tolist())
     torch.manual_seed(1234)
     alg = pkg.CliffordAlgebra(metric)
     mod = _build(pkg, layer, alg, C)
@@ -126,3 +139,33 @@ def test_small_layers_hip_vs_host_fp64(pkg, golden_dir, name, C, rows, layer):
     close(xd.grad, xh.grad, xr.grad, "gx")
     for (k, p), (_, h), (_, q) in zip(mod.named_parameters(), host32.named_parameters(), ref.named_parameters()):
         close(p.grad, h.grad, q.grad, k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cl30", "cl40"])
+def test_small_layers_refuse_257_channels(pkg, name):
+    """One channel past the documented maximum: every standalone entry point returns CSMPN_ERR_INVALID (the per-workgroup
+    parameter sums are sized for 256 channels) and launches nothing. Through the library directly: the modules route a
+    257-channel input to their host formulation."""
+    from csmpn_hip import native, ops
+    metric = N4_METRICS.get(name, (1.0, 1.0, 1.0))
+    n, D, rows, C = len(metric), 1 << len(metric), 5, 257
+    dev = torch.device("cuda:0")
+    assert not ops.small_layer_on_hip(pkg.CliffordAlgebra(metric).to(dev), torch.zeros(rows, C, D, device=dev))
+    x, y = torch.randn(rows, C, D, device=dev), torch.full((rows, C, D), 7.0, device=dev)
+    p = torch.zeros(C, 64, device=dev)     # room for any per-channel parameter tensor
+    lib, m, st = native.lib(), native.metric_array(metric), ops._stream(dev)
+    rcs = {"mvsilu": lib.csmpn_mvsilu_forward(m, n, x.data_ptr(), p.data_ptr(), p.data_ptr(), rows, C, y.data_ptr(), st),
+           "mvnorm": lib.csmpn_mvnorm_forward(m, n, x.data_ptr(), p.data_ptr(), rows, C, y.data_ptr(), st),
+           "mvlayernorm": lib.csmpn_mvlayernorm_forward(m, n, x.data_ptr(), p.data_ptr(), rows, C, y.data_ptr(), st),
+           "wgp": lib.csmpn_wgp_forward(m, n, x.data_ptr(), x.data_ptr(), p.data_ptr(), rows, C, y.data_ptr(), st)}
+    assert rcs == dict.fromkeys(rcs, native.ERR_INVALID), rcs
+    assert "1..256" in lib.csmpn_last_error().decode()
+    gx, gp = torch.full_like(x, 7.0), torch.zeros_like(p)
+    rcb = {"mvsilu": lib.csmpn_mvsilu_backward(m, n, x.data_ptr(), p.data_ptr(), p.data_ptr(), x.data_ptr(), rows, C,
+                                               gx.data_ptr(), gp.data_ptr(), gp.data_ptr(), st),
+           "mvlayernorm": lib.csmpn_mvlayernorm_backward(m, n, x.data_ptr(), p.data_ptr(), x.data_ptr(), rows, C, gx.data_ptr(),
+                                                         gp.data_ptr(), st)}
+    assert rcb == dict.fromkeys(rcb, native.ERR_INVALID), rcb
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all()) and bool((gx == 7.0).all()) and bool((gp == 0.0).all())
