@@ -32,7 +32,7 @@
 //  * gathers: a lane loads its own 32 bytes of a row (2 x 16 bytes); scatters go through a per-wave LDS tile so that
 //    one atomic instruction covers whole 256-byte rows, equal consecutive targets summed first.
 #pragma once
-#include "cemlp_device.hpp"
+#include "cemlp_lane.hpp"
 
 namespace csmpn {
 
@@ -46,8 +46,6 @@ constexpr int kClParStride = 36;     // floats per channel in the per-channel pa
 // them across each other (cemlp_cm.hpp met exactly that). A compiler barrier + the wave-barrier intrinsic (a scheduling
 // barrier, no instruction) state the contract at every such hand-over.
 #define CL_LDS_ORDER() do { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
-CSMPN_DEV f4 cl_ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
-CSMPN_DEV void cl_st4(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
 
 // diagnostic build only (-DCSMPN_STAMPS, never shipped, never timed): shader-clock cycles per phase, summed per wave.
 // The scheduling barriers at a stamp forbid overlaps across phases (memory operations stay in flight: a phase is
@@ -150,20 +148,20 @@ template <int C, int NROT, int TOFF, int BATCH = 4>
 CSMPN_DEV void cl_mix(float (&acc)[8], const float (&x)[8], const float* ldsw) {
     static_assert(NROT % BATCH == 0, "whole batches");
 #ifdef CL_X_NOMIX   // timing experiment only (results wrong): rotation 0 alone
-    cl_fmac8<0>(acc, x, cl_ld4(ldsw + TOFF));
+    cl_fmac8<0>(acc, x, ld4(ldsw + TOFF));
     return;
 #endif
     constexpr int NB = NROT / BATCH;
     f4 w[BATCH];
 #pragma unroll
-    for (int i = 0; i < BATCH; ++i) w[i] = cl_ld4(ldsw + (TOFF + 4 * C * i));
+    for (int i = 0; i < BATCH; ++i) w[i] = ld4(ldsw + (TOFF + 4 * C * i));
     cl_pin<BATCH>(w);
     static_for<0, NB>([&](auto b) {
         // the next batch travels while this one is used
         f4 wn[BATCH];
         if constexpr (b + 1 < NB) {
 #pragma unroll
-            for (int i = 0; i < BATCH; ++i) wn[i] = cl_ld4(ldsw + (TOFF + 4 * C * (BATCH * (b + 1) + i)));
+            for (int i = 0; i < BATCH; ++i) wn[i] = ld4(ldsw + (TOFF + 4 * C * (BATCH * (b + 1) + i)));
         }
         static_for<0, BATCH>([&](auto i) { cl_fmac8<ClMap<C>::ROTL * (BATCH * b + i)>(acc, x, w[i]); });
         if constexpr (b + 1 < NB) {
@@ -258,7 +256,7 @@ __device__ void cl_stage_block(const DevBlock& B, float* base, int tid, int dir)
     }
     f4 v[NIT];
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) v[it] = src[it] ? cl_ld4(src[it]) : f4{0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < NIT; ++it) v[it] = src[it] ? ld4(src[it]) : f4{0.f, 0.f, 0.f, 0.f};
     // per-channel parameters: [b1, bL, la, 0 | sa[4] | sb[4] | sigmoid(an)[4] | w[P]] per channel
     constexpr int NPAR = C * kClParStride, NITP = (NPAR + 64 * kClWaves - 1) / (64 * kClWaves);
     static_assert(16 + P <= kClParStride, "parameter stride");
@@ -288,7 +286,7 @@ __device__ void cl_stage_block(const DevBlock& B, float* base, int tid, int dir)
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int e = tid + it * 64 * kClWaves;
-        if (e < NE) cl_st4(base + 4 * e, v[it]);
+        if (e < NE) st4(base + 4 * e, v[it]);
     }
 #pragma unroll
     for (int it = 0; it < NITP; ++it) {
@@ -306,7 +304,7 @@ CSMPN_DEV void cl_weighted_gp(float (&out)[8], const float (&z)[8], const float 
     constexpr int P = ALG::P;
     f4 wv[(P + 3) / 4];
 #pragma unroll
-    for (int q = 0; q < (P + 3) / 4; ++q) wv[q] = cl_ld4(wp + 4 * q);
+    for (int q = 0; q < (P + 3) / 4; ++q) wv[q] = ld4(wp + 4 * q);
     static_for<0, P>([&](auto p) {
         constexpr int gi = ALG::t.path_g[p][0], gj = ALG::t.path_g[p][1], gk = ALG::t.path_g[p][2];
         constexpr int i0 = ALG::gstart(gi), ni = ALG::gsize(gi);
@@ -336,8 +334,8 @@ template <class ALG, int C, class TB, int BATCH>
 CSMPN_DEV void cl_block_tail(const float* ldsw, const float* ldsp, ClFwd& S, float (&out)[8], ClStamp& stamp, int sid, bool have_s = false) {
     constexpr int D = ALG::D, G = ALG::G;
     static_assert(D == 8 && G == 4, "Cl(3,0)-shaped algebra");
-    const f4 p0 = cl_ld4(ldsp + TB::par);   // b1, bL, la
-    const f4 sa = cl_ld4(ldsp + (TB::par + 4)), sb = cl_ld4(ldsp + (TB::par + 8));
+    const f4 p0 = ld4(ldsp + TB::par);   // b1, bL, la
+    const f4 sa = ld4(ldsp + (TB::par + 4)), sb = ld4(ldsp + (TB::par + 8));
     S.y[0] += p0.x;
     // MVSiLU, invariant "mag2" (cegnn_utils.py:76-83)
     float z[D];
@@ -366,7 +364,7 @@ CSMPN_DEV void cl_block_tail(const float* ldsw, const float* ldsp, ClFwd& S, flo
     // CSMPN_FLAG_SAVE_STATE: with s given (have_s: the forward saved it) the backward's recompute stops behind linear_right
     // and the normalisation denominators - no linear_left mix, no geometric product
     if (have_s) {
-        const f4 sg = cl_ld4(ldsp + (TB::par + 12));
+        const f4 sg = ld4(ldsp + (TB::par + 12));
         static_for<0, G>([&](auto g) {
             constexpr int d0 = ALG::gstart(g), nd = ALG::gsize(g);
             float qq = 0.f;
@@ -391,7 +389,7 @@ CSMPN_DEV void cl_block_tail(const float* ldsw, const float* ldsp, ClFwd& S, flo
     stamp(sid + 1);
     L[0] += p0.y;
     // NormalizationLayer on the right operand (cegnn_utils.py:42-51)
-    const f4 sg = cl_ld4(ldsp + (TB::par + 12));
+    const f4 sg = ld4(ldsp + (TB::par + 12));
     float r[D];
     static_for<0, G>([&](auto g) {
         constexpr int d0 = ALG::gstart(g), nd = ALG::gsize(g);
@@ -474,7 +472,7 @@ struct ClSums {
     CSMPN_DEV explicit ClSums(float* b) : base(b), pend{0.f, 0.f, 0.f, 0.f} {}
     CSMPN_DEV void zero() {
 #pragma unroll
-        for (int g = 0; g < kGroups; ++g) cl_st4(base + g * (4 * 64 * kClWaves), f4{0.f, 0.f, 0.f, 0.f});
+        for (int g = 0; g < kGroups; ++g) st4(base + g * (4 * 64 * kClWaves), f4{0.f, 0.f, 0.f, 0.f});
     }
     template <int IDX>
     CSMPN_DEV void add(float v) {
@@ -485,7 +483,7 @@ struct ClSums {
                 for (int i = IDX % 4 + 1; i < 4; ++i) pend[i] = 0.f;
             }
             float* p = base + (IDX / 4) * (4 * 64 * kClWaves);
-            cl_st4(p, cl_ld4(p) + pend);
+            st4(p, ld4(p) + pend);
         }
     }
     template <int IDX>
@@ -501,7 +499,7 @@ CSMPN_DEV void cl_block_backward(const float* ldsw, const float* ldsp, const ClF
                                  ClSums<ClRed<ALG>::n>& sm, f4 (&accR)[ALG::G], f4 (&accL)[ALG::G], ClStamp& stamp, int sid) {
     constexpr int D = ALG::D, G = ALG::G, P = ALG::P;
     using RM = ClRed<ALG>;
-    const f4 p0 = cl_ld4(ldsp + TB::par);
+    const f4 p0 = ld4(ldsp + TB::par);
     // ---- MVLayerNorm backward
     const float la = p0.z;
     float dot = 0.f;
@@ -539,7 +537,7 @@ CSMPN_DEV void cl_block_backward(const float* ldsw, const float* ldsp, const ClF
     {
         f4 wv[(P + 3) / 4];
 #pragma unroll
-        for (int q = 0; q < (P + 3) / 4; ++q) wv[q] = cl_ld4(ldsp + (TB::par + 16 + 4 * q));
+        for (int q = 0; q < (P + 3) / 4; ++q) wv[q] = ld4(ldsp + (TB::par + 16 + 4 * q));
         static_for<0, P>([&](auto p) {
             constexpr int gi = ALG::t.path_g[p][0], gj = ALG::t.path_g[p][1], gk = ALG::t.path_g[p][2];
             constexpr int i0 = ALG::gstart(gi), ni = ALG::gsize(gi);
@@ -573,7 +571,7 @@ CSMPN_DEV void cl_block_backward(const float* ldsw, const float* ldsp, const ClF
     }
     stamp(sid + 2);
     // ---- NormalizationLayer backward -> gR
-    const f4 sgv = cl_ld4(ldsp + (TB::par + 12));
+    const f4 sgv = ld4(ldsp + (TB::par + 12));
     float gR[D];
     static_for<0, G>([&](auto g) {
         constexpr int d0 = ALG::gstart(g), nd = ALG::gsize(g);
@@ -609,7 +607,7 @@ CSMPN_DEV void cl_block_backward(const float* ldsw, const float* ldsp, const ClF
 #endif
     stamp(sid + 5);
     // ---- MVSiLU backward -> gy
-    const f4 sa = cl_ld4(ldsp + (TB::par + 4));
+    const f4 sa = ld4(ldsp + (TB::par + 4));
     static_for<0, G>([&](auto g) {
         constexpr int d0 = ALG::gstart(g), nd = ALG::gsize(g);
         float ggate = 0.f;
@@ -644,12 +642,12 @@ CSMPN_DEV void cl_block_backward(const float* ldsw, const float* ldsp, const ClF
 // ---------------------------------------------------------------------------------
 // per-lane row access: the lane's 8 blades = 32 contiguous bytes
 CSMPN_DEV void cl_ld8(float (&x)[8], const float* p) {
-    const f4 a = cl_ld4(p), b = cl_ld4(p + 4);
+    const f4 a = ld4(p), b = ld4(p + 4);
     x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
 }
 CSMPN_DEV void cl_st8(float* p, const float (&x)[8]) {
-    cl_st4(p, f4{x[0], x[1], x[2], x[3]});
-    cl_st4(p + 4, f4{x[4], x[5], x[6], x[7]});
+    st4(p, f4{x[0], x[1], x[2], x[3]});
+    st4(p + 4, f4{x[4], x[5], x[6], x[7]});
 }
 #ifdef CL_X_NOOUT   // timing experiment only (results wrong): row stores go to the wave's LDS scratch
 #define CL_GST8(gp, lp, x) cl_st8(lp, x)
@@ -750,9 +748,9 @@ struct ClRaw {
                 p2 = io.seg[2].a + (size_t)T.lrow * (NA * D) + (ca < NA ? ca : NA - 1) * D;
             }
         }
-        v[0] = cl_ld4(p0); v[1] = cl_ld4(p0 + 4);
-        v[2] = cl_ld4(p1); v[3] = cl_ld4(p1 + 4);
-        if constexpr (NA > 0) { v[4] = cl_ld4(p2); v[5] = cl_ld4(p2 + 4); }
+        v[0] = ld4(p0); v[1] = ld4(p0 + 4);
+        v[2] = ld4(p1); v[3] = ld4(p1 + 4);
+        if constexpr (NA > 0) { v[4] = ld4(p2); v[5] = ld4(p2 + 4); }
     }
     // all of them requested before the first is used
     CSMPN_DEV void pin() {
@@ -786,12 +784,7 @@ CSMPN_DEV int cl_probe_dir(int c) {
 // forward kernel: NBLK blocks (1 or 2), all C channels wide. Tile t (64 / C rows) belongs to wave t mod (4 gridDim).
 template <class ALG, int C, int MODE, int NBLK, int NA>
 __global__ void __launch_bounds__(64 * kClWaves, 4) cemlp_cl_fwd_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     using MP = ClMap<C>;
     using T0 = ClTab<C, MODE, NA, 0, false>;
     using T1 = ClTab<C, MODE, NA, 1, false>;
@@ -945,7 +938,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
         const float* gsrc = (kLast ? io.gy + (size_t)(MODE == MODE_EDGE ? (long)Tl.i_dst : Tl.lrow) * ROW
                                    : io.plw_g1 + (size_t)Tl.lrow * ROW) + c * D;
         if (kLast || !single) {
-            g0 = cl_ld4(gsrc); g1 = cl_ld4(gsrc + 4);
+            g0 = ld4(gsrc); g1 = ld4(gsrc + 4);
         } else {   // one tile per wave: d/d(out) of this block stayed in registers
             g0 = carry_a; g1 = carry_b;
         }
@@ -953,7 +946,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
             raw.template issue<TB>(io, Tl, c);
         } else {
             const float* sp = io.saved + (size_t)Tl.lrow * ROW + c * D;
-            s0 = cl_ld4(sp); s1 = cl_ld4(sp + 4);
+            s0 = ld4(sp); s1 = ld4(sp + 4);
         }
     };
     const long tile0 = (long)blockIdx.x * kClWaves + wave;
@@ -1092,7 +1085,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
         for (int g = 0; g < G; ++g) { t += accR[g] + accL[g];
 #pragma unroll
             for (int p = 0; p < NP; ++p) t += accW1[p][g]; }
-        cl_st4(sc + 4 * lane, t);
+        st4(sc + 4 * lane, t);
     }
     if (false)
 #endif
@@ -1114,15 +1107,15 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
                 const int cc = j >> 1;
                 if ((j & 1) == 0 && cc < width) {
                     float* p0 = img + base + ((2 * q) * I + coff + cc) * G;
-                    cl_st4(p0, f4{lo[0], lo[1], lo[2], lo[3]});
-                    cl_st4(p0 + I * G, f4{hi[0], hi[1], hi[2], hi[3]});
+                    st4(p0, f4{lo[0], lo[1], lo[2], lo[3]});
+                    st4(p0 + I * G, f4{hi[0], hi[1], hi[2], hi[3]});
                 }
             } else {
                 if (j < width) {
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
                         float* p0 = img + base + ((4 * q + v) * I + coff + j) * G;
-                        cl_st4(p0, f4{acc[0][v], acc[1][v], acc[2][v], acc[3][v]});
+                        st4(p0, f4{acc[0][v], acc[1][v], acc[2][v], acc[3][v]});
                     }
                 }
             }
@@ -1134,7 +1127,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
         // its column's sum), one DPP add the interleaved row pair (C = 8)
         f4 sv[ClSums<RM::n>::kGroups];
 #pragma unroll
-        for (int gq = 0; gq < ClSums<RM::n>::kGroups; ++gq) sv[gq] = cl_ld4(sm.base + gq * (4 * 64 * kClWaves));
+        for (int gq = 0; gq < ClSums<RM::n>::kGroups; ++gq) sv[gq] = ld4(sm.base + gq * (4 * 64 * kClWaves));
         static_for<0, RM::n>([&](auto idx) {
             const f4 t = __builtin_amdgcn_mfma_f32_16x16x4f32(1.0f, sv[idx / 4][idx % 4], f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
             float s = t[0];
@@ -1148,10 +1141,10 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
         const float* img0 = work;
         static_assert(PT::total % 4 == 0, "slice length");
         for (int e = 4 * threadIdx.x; e < PT::total; e += 4 * 64 * kClWaves) {
-            f4 v = cl_ld4(img0 + e);
+            f4 v = ld4(img0 + e);
 #pragma unroll
-            for (int w = 1; w < kClWaves; ++w) v += cl_ld4(img0 + w * scratch + e);
-            cl_st4(part + e, v);
+            for (int w = 1; w < kClWaves; ++w) v += ld4(img0 + w * scratch + e);
+            st4(part + e, v);
         }
     }
     stamp(17);
@@ -1174,12 +1167,7 @@ constexpr size_t cl_bwd_lds_bytes() {
 // (one tile per wave) is a single launch.
 template <class ALG, int C, int MODE, int NBLK, int NA, bool SAVES = false>
 __global__ void __launch_bounds__(64 * kClWaves, 2) cemlp_cl_bwd_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     ClStamp stamp(0);
     using TB0 = ClTab<C, MODE, NA, 0, true>;

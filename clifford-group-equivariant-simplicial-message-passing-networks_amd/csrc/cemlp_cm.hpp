@@ -125,7 +125,7 @@ __device__ void cm_stage_tables(const DevBlock& B, float* base, int tid) {
     }
     f4 val[NIT];
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) val[it] = src[it] ? cl_ld4(src[it]) : f4{0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < NIT; ++it) val[it] = src[it] ? ld4(src[it]) : f4{0.f, 0.f, 0.f, 0.f};
     constexpr int NPAR = C * kClParStride, NITP = (NPAR + NT - 1) / NT;
     static_assert(16 + P <= kClParStride, "parameter stride");
     const float *pb1 = B.b1, *pbL = B.bL, *pla = B.la, *psa = B.sa, *psb = B.sb, *pan = B.an, *pw = B.w;
@@ -179,7 +179,7 @@ CSMPN_DEV void cm_mix_chunk(f4 (&acc)[MB][8], const f4 (&x)[8], const float* lds
     static_for<0, MB>([&](auto mp) {
         f4 a[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) a[g] = cl_ld4(ldsa + (g * GS + mp * MS));
+        for (int g = 0; g < 4; ++g) a[g] = ld4(ldsa + (g * GS + mp * MS));
         static_for<0, 8>([&](auto d) {
             constexpr int g = ALG::grade(d);
             static_for<0, NSTEP>([&](auto v) { acc[mp][d] = mfma16(a[g][int(v)], x[d][int(v)], acc[mp][d]); });
@@ -191,7 +191,7 @@ CSMPN_DEV void cm_mix_chunk(f4 (&acc)[MB][8], const f4 (&x)[8], const float* lds
 template <class ALG>
 CSMPN_DEV void cm_silu(float (&y)[8], float (&z)[8], float (&gate)[4], const float* pp) {
     constexpr int G = ALG::G;
-    const f4 p0 = cl_ld4(pp), sa = cl_ld4(pp + 4), sb = cl_ld4(pp + 8);
+    const f4 p0 = ld4(pp), sa = ld4(pp + 4), sb = ld4(pp + 8);
     y[0] += p0.x;
     static_for<0, G>([&](auto g) {
         constexpr int d0 = ALG::gstart(g), nd = ALG::gsize(g);
@@ -217,7 +217,7 @@ template <class ALG>
 CSMPN_DEV float cm_gp_tail(const float (&z)[8], const float (&R)[8], float (&L)[8], float (&invden)[4], const float* pp) {
     constexpr int D = ALG::D, G = ALG::G;
     L[0] += pp[1];
-    const f4 sg = cl_ld4(pp + 12);
+    const f4 sg = ld4(pp + 12);
     float r[D];
     static_for<0, G>([&](auto g) {
         constexpr int d0 = ALG::gstart(g), nd = ALG::gsize(g);
@@ -374,7 +374,7 @@ struct CmPiece {
     f4 v[4][2];
     CSMPN_DEV void load(const float* p) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { v[c][0] = cl_ld4(p + 32 * c); v[c][1] = cl_ld4(p + 32 * c + 4); }
+        for (int c = 0; c < 4; ++c) { v[c][0] = ld4(p + 32 * c); v[c][1] = ld4(p + 32 * c + 4); }
     }
 };
 // t[d][v] <-> memory [v][d]
@@ -387,8 +387,8 @@ CSMPN_DEV void cm_unpack(f4 (&t)[8], const CmPiece& a) {
 CSMPN_DEV void cm_store_piece(float* p, const f4 (&t)[8]) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        cl_st4(p + 32 * c, f4{t[0][c], t[1][c], t[2][c], t[3][c]});
-        cl_st4(p + 32 * c + 4, f4{t[4][c], t[5][c], t[6][c], t[7][c]});
+        st4(p + 32 * c, f4{t[0][c], t[1][c], t[2][c], t[3][c]});
+        st4(p + 32 * c + 4, f4{t[4][c], t[5][c], t[6][c], t[7][c]});
     }
 }
 
@@ -416,7 +416,7 @@ struct CmRaw {
             for (int v = 0; v < NSTEP; ++v) {
                 const int ca = q + 4 * v;   // slot (q, v) = attribute channel q + 4 v; an empty slot reads a valid one (its weights are 0)
                 const float* p = pt + (ca < NA ? ca : NA - 1) * D;
-                t[v][0] = cl_ld4(p); t[v][1] = cl_ld4(p + 4);
+                t[v][0] = ld4(p); t[v][1] = ld4(p + 4);
             }
         }
     }
@@ -494,12 +494,7 @@ CSMPN_DEV void cm_scatter(const float* sc, int t_add, int t_sub, float* table, i
 // forward kernel: NBLK blocks (1 or 2), all C channels wide. Tile t (16 rows) belongs to wave t mod (4 gridDim).
 template <class ALG, int C, int MODE, int NBLK, int NA>
 __global__ void __launch_bounds__(64 * kCmWaves, C == 16 ? CM_FWD_OCC : 1) cemlp_cm_fwd_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     using T0 = CmTab<C, MODE, NA, 0>;
     using T1 = CmTab<C, MODE, NA, 1>;
     constexpr int D = ALG::D, ROW = C * D, MB = C / 16, SS = ROW + 4;
@@ -623,7 +618,7 @@ template <class ALG, int NSTEP, int GS>
 CSMPN_DEV void cm_mix_one(f4 (&acc)[8], const f4 (&x)[8], const float* ldsa) {
     f4 a[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) a[g] = cl_ld4(ldsa + g * GS);
+    for (int g = 0; g < 4; ++g) a[g] = ld4(ldsa + g * GS);
     static_for<0, 8>([&](auto d) {
         constexpr int g = ALG::grade(d);
         static_for<0, NSTEP>([&](auto v) { acc[d] = mfma16(a[g][int(v)], x[d][int(v)], acc[d]); });
@@ -633,7 +628,7 @@ CSMPN_DEV void cm_mix_one(f4 (&acc)[8], const f4 (&x)[8], const float* ldsa) {
 // the gates of MVSiLU from the (biased) MVLinear output of one channel
 template <class ALG>
 CSMPN_DEV void cm_gate(const float (&y)[8], float (&gate)[4], const float* pp) {
-    const f4 sa = cl_ld4(pp + 4), sb = cl_ld4(pp + 8);
+    const f4 sa = ld4(pp + 4), sb = ld4(pp + 8);
     static_for<0, ALG::G>([&](auto g) {
         constexpr int d0 = ALG::gstart(g), nd = ALG::gsize(g);
         float u;
@@ -656,7 +651,7 @@ CSMPN_DEV void cm_silu_bwd(const float (&gz)[8], const float (&y)[8], float (&gy
     constexpr int G = ALG::G;
     float gate[4];
     cm_gate<ALG>(y, gate, pp);
-    const f4 sa = cl_ld4(pp + 4);
+    const f4 sa = ld4(pp + 4);
     static_for<0, G>([&](auto g) {
         constexpr int d0 = ALG::gstart(g), nd = ALG::gsize(g);
         float ggate = 0.f;

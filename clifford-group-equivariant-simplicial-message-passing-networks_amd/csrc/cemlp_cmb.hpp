@@ -237,7 +237,7 @@ CSMPN_DEV void cb_gp_bwd(const float (&ggp_in)[8], const float (&zf_in)[8], cons
         asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]));
     };
     constexpr int D = ALG::D, G = ALG::G, P = ALG::P;
-    const f4 sgv = cl_ld4(pp + 12);
+    const f4 sgv = ld4(pp + 12);
     float rf[D], invden[G], nu[G], qR[G];
     static_for<0, G>([&](auto g) {
         constexpr int d0 = ALG::gstart(g), nd = ALG::gsize(g);
@@ -608,8 +608,8 @@ __device__ void cb_block(const RowIO& io, float* tab, float* work, int* ctr, ClS
                     static_for<0, (NA + 3) / 4>([&](auto v) {
                         if (Tc.valid && q + 4 * v < NA) {
                             float* p = io.gx[1] + (size_t)Tc.i_perm * (NA * D) + (q + 4 * v) * D;
-                            cl_st4(p, f4{gx[0][int(v)], gx[1][int(v)], gx[2][int(v)], gx[3][int(v)]});
-                            cl_st4(p + 4, f4{gx[4][int(v)], gx[5][int(v)], gx[6][int(v)], gx[7][int(v)]});
+                            st4(p, f4{gx[0][int(v)], gx[1][int(v)], gx[2][int(v)], gx[3][int(v)]});
+                            st4(p + 4, f4{gx[4][int(v)], gx[5][int(v)], gx[6][int(v)], gx[7][int(v)]});
                         }
                     });
                 }
@@ -663,8 +663,8 @@ __device__ void cb_block(const RowIO& io, float* tab, float* work, int* ctr, ClS
                     static_for<0, (NA + 3) / 4>([&](auto v) {
                         if (Tc.valid && q + 4 * v < NA) {
                             float* p = io.gx[2] + (size_t)Tc.row * (NA * D) + (q + 4 * v) * D;
-                            cl_st4(p, f4{gx[0][int(v)], gx[1][int(v)], gx[2][int(v)], gx[3][int(v)]});
-                            cl_st4(p + 4, f4{gx[4][int(v)], gx[5][int(v)], gx[6][int(v)], gx[7][int(v)]});
+                            st4(p, f4{gx[0][int(v)], gx[1][int(v)], gx[2][int(v)], gx[3][int(v)]});
+                            st4(p + 4, f4{gx[4][int(v)], gx[5][int(v)], gx[6][int(v)], gx[7][int(v)]});
                         }
                     });
                 }
@@ -700,8 +700,8 @@ __device__ void cb_block(const RowIO& io, float* tab, float* work, int* ctr, ClS
                     for (int v = 0; v < 4; ++v) {
                         float* p0 = img + base + (TF::orow(4 * qq + v) * I + coff + c) * G;
                         const f4 val = f4{acc[0][v], acc[1][v], acc[2][v], acc[3][v]};
-                        const f4 old = cl_ld4(p0);
-                        cl_st4(p0, add ? old + val : val);
+                        const f4 old = ld4(p0);
+                        st4(p0, add ? old + val : val);
                     }
                 }
             };
@@ -728,7 +728,7 @@ __device__ void cb_block(const RowIO& io, float* tab, float* work, int* ctr, ClS
                   (size_t)blockIdx.x * PT::total;
     static_assert(PT::total % 4 == 0, "slice length");
     for (int e = 4 * threadIdx.x; e < PT::total; e += 4 * 64 * kCbWaves)
-        cl_st4(part + e, (cl_ld4(work + e) + cl_ld4(work + IMG + e)) + (cl_ld4(work + 2 * IMG + e) + cl_ld4(work + 3 * IMG + e)));
+        st4(part + e, (ld4(work + e) + ld4(work + IMG + e)) + (ld4(work + 2 * IMG + e) + ld4(work + 3 * IMG + e)));
     stamp(17);
         CB_MARK(17);
 }
@@ -745,12 +745,7 @@ constexpr size_t cb_lds_bytes() {
 // k - 1 are the ones it wrote itself in block k (through L2; drained before the barrier) - no grid-wide synchronisation.
 template <class ALG, int C, int MODE, int NBLK, int NA>
 __global__ void __launch_bounds__(64 * kCbWaves) cemlp_cmb_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     ClStamp stamp(0);
     constexpr int tabs0 = CmTab<C, MODE, NA, 0>::total, tabs1 = NBLK > 1 ? CmTab<C, MODE, NA, 1>::total : 0;

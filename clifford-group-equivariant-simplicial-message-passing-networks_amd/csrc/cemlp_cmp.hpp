@@ -41,11 +41,11 @@ CSMPN_DEV void cp_pin8(float (&x)[8]) {
 
 CSMPN_DEV void cp_put(float* slot, int lane, const f4 (&t)[8]) {
 #pragma unroll
-    for (int d = 0; d < 8; ++d) cl_st4(slot + d * 256 + (lane & 15) * 16 + 4 * (lane >> 4), t[d]);
+    for (int d = 0; d < 8; ++d) st4(slot + d * 256 + (lane & 15) * 16 + 4 * (lane >> 4), t[d]);
 }
 CSMPN_DEV void cp_get(const float* slot, int lane, f4 (&t)[8]) {
 #pragma unroll
-    for (int d = 0; d < 8; ++d) t[d] = cl_ld4(slot + d * 256 + (lane & 15) * 16 + 4 * (lane >> 4));
+    for (int d = 0; d < 8; ++d) t[d] = ld4(slot + d * 256 + (lane & 15) * 16 + 4 * (lane >> 4));
 }
 // acc[grade] += sum over the 16 rows and the blades of the grade of a^T b (operands in slots, see cb_wgrad)
 template <class ALG>
@@ -132,7 +132,7 @@ struct CpIn {
                     for (int v = 0; v < NSTEP; ++v) {
                         const int ca = q + 4 * v;
                         const float* pp = pt + (ca < NA ? ca : NA - 1) * D;
-                        t[v][0] = cl_ld4(pp); t[v][1] = cl_ld4(pp + 4);
+                        t[v][0] = ld4(pp); t[v][1] = ld4(pp + 4);
                     }
                 }
             }
@@ -533,8 +533,8 @@ __device__ void cp_block(const RowIO& io, float* tab, float* slots, float* red, 
                     static_for<0, (NA + 3) / 4>([&](auto v) {
                         if (Tc.valid && q + 4 * v < NA) {
                             float* pg = io.gx[1] + (size_t)Tc.i_perm * (NA * D) + (q + 4 * v) * D;
-                            cl_st4(pg, f4{gx[0][int(v)], gx[1][int(v)], gx[2][int(v)], gx[3][int(v)]});
-                            cl_st4(pg + 4, f4{gx[4][int(v)], gx[5][int(v)], gx[6][int(v)], gx[7][int(v)]});
+                            st4(pg, f4{gx[0][int(v)], gx[1][int(v)], gx[2][int(v)], gx[3][int(v)]});
+                            st4(pg + 4, f4{gx[4][int(v)], gx[5][int(v)], gx[6][int(v)], gx[7][int(v)]});
                         }
                     });
                 }
@@ -578,8 +578,8 @@ __device__ void cp_block(const RowIO& io, float* tab, float* slots, float* red, 
                     static_for<0, (NA + 3) / 4>([&](auto v) {
                         if (Tc.valid && q + 4 * v < NA) {
                             float* pg = io.gx[2] + (size_t)Tc.row * (NA * D) + (q + 4 * v) * D;
-                            cl_st4(pg, f4{gx[0][int(v)], gx[1][int(v)], gx[2][int(v)], gx[3][int(v)]});
-                            cl_st4(pg + 4, f4{gx[4][int(v)], gx[5][int(v)], gx[6][int(v)], gx[7][int(v)]});
+                            st4(pg, f4{gx[0][int(v)], gx[1][int(v)], gx[2][int(v)], gx[3][int(v)]});
+                            st4(pg + 4, f4{gx[4][int(v)], gx[5][int(v)], gx[6][int(v)], gx[7][int(v)]});
                         }
                     });
                 }
@@ -607,8 +607,8 @@ __device__ void cp_block(const RowIO& io, float* tab, float* slots, float* red, 
                     for (int v = 0; v < 4; ++v) {
                         float* p0 = img + base + ((16 * p + TF::orow(4 * qq + v)) * I + coff + c) * G;
                         const f4 val = f4{acc[0][v], acc[1][v], acc[2][v], acc[3][v]};
-                        const f4 old = cl_ld4(p0);
-                        cl_st4(p0, add ? old + val : val);
+                        const f4 old = ld4(p0);
+                        st4(p0, add ? old + val : val);
                     }
                 }
             };
@@ -636,7 +636,7 @@ __device__ void cp_block(const RowIO& io, float* tab, float* slots, float* red, 
     float* part = io.rl_partials + (K == 0 ? 0 : (size_t)kClSliceCap * ClPart<ALG, C, CmTab<C, MODE, NA, 0>::I>::total) +
                   (size_t)blockIdx.x * PT::total;
     static_assert(PT::total % 4 == 0, "slice length");
-    for (int e = 4 * threadIdx.x; e < PT::total; e += 4 * 64 * kCpWaves) cl_st4(part + e, cl_ld4(img + e));
+    for (int e = 4 * threadIdx.x; e < PT::total; e += 4 * 64 * kCpWaves) st4(part + e, ld4(img + e));
     stamp(17); CB_MARK(17);
     CM_FENCE();
 }
@@ -650,12 +650,7 @@ constexpr size_t cp_lds_bytes() {
 
 template <class ALG, int C, int MODE, int NBLK, int NA, bool SAVES = false>
 __global__ void __launch_bounds__(64 * kCpWaves, CP_OCC) cemlp_cmp_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     ClStamp stamp(0);
     constexpr int tabs0 = CmTab<C, MODE, NA, 0>::total, tabs1 = NBLK > 1 ? CmTab<C, MODE, NA, 1>::total : 0;

@@ -6,7 +6,7 @@
 //   MODE_NODE   EGCL.update (+ residual, + mean scale)      (cegnn_utils.py:264-275)
 // BWD = recompute-forward + backward for the same three.
 #pragma once
-#include "cemlp_device.hpp"
+#include "cemlp_lane.hpp"
 
 namespace csmpn {
 
@@ -321,15 +321,7 @@ template <int MODE> constexpr int kModeSegs = MODE == MODE_PLAIN ? 1 : (MODE == 
 // state of a block live: 256 threads (1 wave/SIMD, up to 512 VGPRs).
 template <class ALG, int MODE, int VAR, int H, bool BWD>
 __global__ void __launch_bounds__(BWD ? 256 : 512) cemlp_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    // Read the descriptors in place from the kernarg segment (constant address space, scalar
-    // loads). Indexing the by-value arguments dynamically (C.b[k]) makes the compiler copy
-    // the whole struct to scratch and turns every field access into a scratch load.
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& C = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(C);
     using GE = Geo<ALG, H>;
     constexpr int D = ALG::D, G = ALG::G, R = GE::R, NW = GE::NW;
     constexpr bool MULTI = kVarBarrier<VAR>;

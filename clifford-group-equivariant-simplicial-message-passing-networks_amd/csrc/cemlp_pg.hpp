@@ -27,7 +27,7 @@
 // rows leave through A with coalesced stores / one atomic per 256 bytes and equal consecutive targets summed first.
 // State for the backward (CSMPN_FLAG_SAVE_STATE): y, R, s of both blocks in ROW-layout lane order, whole 1 KB pieces.
 #pragma once
-#include "cemlp_device.hpp"
+#include "cemlp_lane.hpp"
 
 namespace csmpn {
 
@@ -69,8 +69,6 @@ struct PgStamp {
 #endif
 };
 
-CSMPN_DEV f4 pg_ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
-CSMPN_DEV void pg_st4(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
 // float offset of 16-byte piece j (blades 4j .. 4j+3) of (channel slot c, row r)
 CSMPN_DEV int pg_off(int c, int r, int j) { return c * kPgCS + r * 32 + 4 * (j ^ (r & 7)); }
 // grade of blade d in the grade-sorted order of 5 generators (1, 5, 10, 10, 5, 1)
@@ -197,7 +195,7 @@ CSMPN_DEV void pg_mix_acc(f4 (&acc)[4][NT], const float* buf, const f4* tab, int
     const float* bp = buf + pg_off(k, n, wave);
     f4 b[NSTEP];
 #pragma unroll
-    for (int s = 0; s < NSTEP; ++s) b[s] = pg_ld4(bp + 4 * s * kPgCS);
+    for (int s = 0; s < NSTEP; ++s) b[s] = ld4(bp + 4 * s * kPgCS);
     const int g_lo = pg_grade(4 * wave), g_hi = pg_grade(4 * wave + 3);   // at most two (consecutive) grades per 4 blades
     f4 alo[NT][KS4], ahi[NT][KS4];
 #pragma unroll
@@ -231,7 +229,7 @@ CSMPN_DEV void pg_mix_acc2(f4 (&accR)[4][2], f4 (&accL)[4][2], const float* buf,
     const float* bp = buf + pg_off(k, n, wave);
     f4 b[NSTEP];
 #pragma unroll
-    for (int s = 0; s < NSTEP; ++s) b[s] = pg_ld4(bp + 4 * s * kPgCS);
+    for (int s = 0; s < NSTEP; ++s) b[s] = ld4(bp + 4 * s * kPgCS);
     const int g_lo = pg_grade(4 * wave), g_hi = pg_grade(4 * wave + 3);
     bool hi[4];
 #pragma unroll
@@ -275,7 +273,7 @@ CSMPN_DEV void pg_write_d(float* buf, const f4 (&acc)[4][NT], int lane, int wave
 #pragma unroll
         for (int v = 0; v < 4; ++v)
             if (SLOTS >= 16 * NT || 16 * ot + 4 * q + v < SLOTS)
-                pg_st4(buf + pg_off(16 * ot + 4 * q + v, n, wave), f4{acc[0][ot][v], acc[1][ot][v], acc[2][ot][v], acc[3][ot][v]});
+                st4(buf + pg_off(16 * ot + 4 * q + v, n, wave), f4{acc[0][ot][v], acc[1][ot][v], acc[2][ot][v], acc[3][ot][v]});
 }
 
 // empty asm statements that take a tensor's registers: every value is final at this point (without them the compiler sinks
@@ -290,13 +288,13 @@ CSMPN_DEV void pg_pin32(float (&t)[32]) {
 CSMPN_DEV void pg_ld32(float (&t)[32], const float* buf, int r, int c) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const f4 v = pg_ld4(buf + pg_off(c, r, j));
+        const f4 v = ld4(buf + pg_off(c, r, j));
         t[4 * j] = v.x; t[4 * j + 1] = v.y; t[4 * j + 2] = v.z; t[4 * j + 3] = v.w;
     }
 }
 CSMPN_DEV void pg_st32(float* buf, int r, int c, const float (&t)[32]) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) pg_st4(buf + pg_off(c, r, j), f4{t[4 * j], t[4 * j + 1], t[4 * j + 2], t[4 * j + 3]});
+    for (int j = 0; j < 8; ++j) st4(buf + pg_off(c, r, j), f4{t[4 * j], t[4 * j + 1], t[4 * j + 2], t[4 * j + 3]});
 }
 // state rows (CSMPN_FLAG_SAVE_STATE): piece j of lane l of wave w of tile t at (((t * 8 + w) * 8 + j) * 64 + l) * 4 floats of the
 // tensor's region - one store / load instruction of a wave covers 1 KB
@@ -314,50 +312,11 @@ CSMPN_DEV void pg_load_state(float (&t)[32], const float* p) {
     }
 }
 
-// out[j] += sum_p w[p] sum_{(i,k) -> j in path p} sign(i,k) z[i] r[k]   (cegnn_utils.py:126-152), all 32 blades in the lane;
-// wrow: this channel's P path weights (LDS, 16-byte aligned)
-template <class ALG>
-CSMPN_DEV void pg_weighted_gp(float (&out)[32], const float (&z)[32], const float (&r)[32], const float* wrow) {
-    constexpr int P = ALG::P;
-    static_assert(P % 4 == 0, "whole 16-byte pieces of path weights");
-    static_for<0, P / 4>([&](auto qq) {
-        const f4 wv = pg_ld4(wrow + 4 * decltype(qq)::value);
-        static_for<0, 4>([&](auto pp) {
-            constexpr int p = 4 * decltype(qq)::value + decltype(pp)::value;
-            constexpr int gi = ALG::t.path_g[p][0], gj = ALG::t.path_g[p][1], gk = ALG::t.path_g[p][2];
-            constexpr int i0 = ALG::gstart(gi), ni = ALG::gsize(gi);
-            constexpr int j0 = ALG::gstart(gj), nj = ALG::gsize(gj);
-            constexpr int k0 = ALG::gstart(gk), nk = ALG::gsize(gk);
-            const float w = wv[decltype(pp)::value];
-            float tmp[nj];
-#pragma unroll
-            for (int t = 0; t < nj; ++t) tmp[t] = 0.f;
-            static_for<0, ni>([&](auto ii) {
-                static_for<0, nk>([&](auto kk) {
-                    constexpr int i = i0 + ii, k = k0 + kk;
-                    constexpr int j = ALG::t.out[i][k];
-                    if constexpr (j >= j0 && j < j0 + nj) {
-                        constexpr float sg = float(ALG::t.sign[i][k]);
-                        tmp[j - j0] = __builtin_fmaf(sg * z[i], r[k], tmp[j - j0]);
-                    }
-                });
-            });
-#pragma unroll
-            for (int t = 0; t < nj; ++t) out[j0 + t] = __builtin_fmaf(w, tmp[t], out[j0 + t]);
-        });
-    });
-}
-
 // ---------------------------------------------------------------------------------
 // forward kernel: two blocks of C channels, EGCL edge / node program
 template <class ALG, class CF>
 __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     constexpr int C = CF::C, MODE = CF::MODE, NA = CF::NA, D = 32, G = 6, P = CF::P, ROW = CF::ROW, NST = CF::NST;
     constexpr int ROWP = 32 * D;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -430,11 +389,11 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
             pre_a[i] = pre_b[i] = f4{0.f, 0.f, 0.f, 0.f};
             if (idx[rr] >= 0) {
                 if constexpr (MODE == MODE_EDGE) {
-                    pre_a[i] = pg_ld4(io.seg[0].a + (size_t)idx[rr] * ROW + 4 * e);
-                    pre_b[i] = pg_ld4(io.seg[0].b + (size_t)idx[16 + rr] * ROW + 4 * e);
+                    pre_a[i] = ld4(io.seg[0].a + (size_t)idx[rr] * ROW + 4 * e);
+                    pre_b[i] = ld4(io.seg[0].b + (size_t)idx[16 + rr] * ROW + 4 * e);
                 } else {
-                    pre_a[i] = pg_ld4(io.seg[0].a + (size_t)(tile_ * kPgRows + rr) * ROW + 4 * e);
-                    pre_b[i] = pg_ld4(io.seg[1].a + (size_t)(tile_ * kPgRows + rr) * ROW + 4 * e) * sc_[rr];
+                    pre_a[i] = ld4(io.seg[0].a + (size_t)(tile_ * kPgRows + rr) * ROW + 4 * e);
+                    pre_b[i] = ld4(io.seg[1].a + (size_t)(tile_ * kPgRows + rr) * ROW + 4 * e) * sc_[rr];
                 }
             }
         }
@@ -443,8 +402,8 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
             const int p = t + i * kPgThreads, rr = (p / PPA) & 15, e = p % PPA;
             pre_x[i] = f4{0.f, 0.f, 0.f, 0.f};
             if (p < kPgRows * PPA && idx[rr] >= 0 && e < NA * 8) {
-                if constexpr (MODE == MODE_EDGE) pre_x[i] = pg_ld4(io.seg[1].a + (size_t)idx[32 + rr] * (NA * D) + 4 * e);
-                else pre_x[i] = pg_ld4(io.seg[2].a + (size_t)(tile_ * kPgRows + rr) * (NA * D) + 4 * e);
+                if constexpr (MODE == MODE_EDGE) pre_x[i] = ld4(io.seg[1].a + (size_t)idx[32 + rr] * (NA * D) + 4 * e);
+                else pre_x[i] = ld4(io.seg[2].a + (size_t)(tile_ * kPgRows + rr) * (NA * D) + 4 * e);
             }
         }
     };
@@ -461,17 +420,17 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
             for (int i = 0; i < NPRE; ++i) {
                 const int p = tid + i * kPgThreads, rr = p / PPR, e = p % PPR;
                 if constexpr (MODE == MODE_EDGE) {
-                    pg_st4(bufA + pg_off(e >> 3, rr, e & 7), pre_a[i] - pre_b[i]);
+                    st4(bufA + pg_off(e >> 3, rr, e & 7), pre_a[i] - pre_b[i]);
                 } else {
-                    pg_st4(bufA + pg_off(e >> 3, rr, e & 7), pre_a[i]);
-                    pg_st4(bufB + pg_off(e >> 3, rr, e & 7), pre_b[i]);
+                    st4(bufA + pg_off(e >> 3, rr, e & 7), pre_a[i]);
+                    st4(bufB + pg_off(e >> 3, rr, e & 7), pre_b[i]);
                 }
             }
             float* const bufX = MODE == MODE_EDGE ? bufB : bufE;
 #pragma unroll
             for (int i = 0; i < NPA; ++i) {
                 const int p = tid + i * kPgThreads, rr = (p / PPA) & 15, e = p % PPA;
-                if (p < kPgRows * PPA) pg_st4(bufX + pg_off(e >> 3, rr, e & 7), pre_x[i]);
+                if (p < kPgRows * PPA) st4(bufX + pg_off(e >> 3, rr, e & 7), pre_x[i]);
             }
             if (tid < kPgRows) load_idx(sidx_n, tile + gridDim.x, tid);
         }
@@ -501,7 +460,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
                     if (io.save) {
                         for (int p = tid; p < kPgRows * PPR; p += kPgThreads) {
                             const int rr = p / PPR, e = p % PPR;
-                            if (row0 + rr < io.rows) pg_st4(io.save + (size_t)(row0 + rr) * ROW + 4 * e, pg_ld4(bufB + pg_off(e >> 3, rr, e & 7)));
+                            if (row0 + rr < io.rows) st4(io.save + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pg_off(e >> 3, rr, e & 7)));
                         }
                     }
                 }
@@ -572,7 +531,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
 #pragma unroll
                     for (int t = 0; t < nd; ++t) R[d0 + t] *= inv;
                 });
-                pg_weighted_gp<ALG>(s, z, R, wrow);
+                lane_weighted_gp<ALG>(s, z, R, wrow);
             }
             float qs = 0.f;
             static_for<0, 32>([&](auto dd) {
@@ -589,7 +548,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
             float tot = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const f4 v = pg_ld4(lnx + r * 32 + 4 * j);
+                const f4 v = ld4(lnx + r * 32 + 4 * j);
                 tot += (v.x + v.y) + (v.z + v.w);
             }
             const float kf = par[2] * fast_rcp(__builtin_fmaf(tot, 1.0f / float(C), kEps));
@@ -607,7 +566,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
             if (io.row_store) {   // deterministic mode: message rows to the [E, C, D] table in sorted edge order
                 for (int p = tid; p < kPgRows * PPR; p += kPgThreads) {
                     const int rr = p / PPR, e = p % PPR;
-                    if (row0 + rr < io.rows) pg_st4(io.agg + (size_t)(row0 + rr) * ROW + 4 * e, pg_ld4(bufA + pg_off(e >> 3, rr, e & 7)));
+                    if (row0 + rr < io.rows) st4(io.agg + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufA + pg_off(e >> 3, rr, e & 7)));
                 }
             } else {
                 // one atomic per 256 bytes of a target row; equal consecutive targets (the rows are sorted by target) are summed first
@@ -632,9 +591,9 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
             for (int p = tid; p < kPgRows * PPR; p += kPgThreads) {
                 const int rr = p / PPR, e = p % PPR;
                 if (row0 + rr < io.rows) {
-                    f4 v = pg_ld4(bufA + pg_off(e >> 3, rr, e & 7));
-                    if (io.resid) v += pg_ld4(io.resid + (size_t)(row0 + rr) * ROW + 4 * e);
-                    pg_st4(io.y + (size_t)(row0 + rr) * ROW + 4 * e, v);
+                    f4 v = ld4(bufA + pg_off(e >> 3, rr, e & 7));
+                    if (io.resid) v += ld4(io.resid + (size_t)(row0 + rr) * ROW + 4 * e);
+                    st4(io.y + (size_t)(row0 + rr) * ROW + 4 * e, v);
                 }
             }
         }
@@ -661,104 +620,6 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
 // every element of the slice has one owner and no sums cross waves. Per-channel parameter gradients: summed over the 16
 // rows of a tile by the transposing butterfly of cemlp_cmb.hpp (a DPP row = the 16 rows of one channel), 5 registers per lane.
 
-// 16 values in, lane j of the 16-lane DPP row keeps the sum over the row's lanes of value j (cb_rows_sum of cemlp_cmb.hpp)
-CSMPN_DEV float pg_rows_sum(float (&x)[16], int l16) {
-    const bool b0 = l16 & 1, b1 = l16 & 2, b2 = l16 & 4, b3 = l16 & 8;
-    float y[8], z[4], u[2];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float keep = b0 ? x[2 * j + 1] : x[2 * j], send = b0 ? x[2 * j] : x[2 * j + 1];
-        y[j] = keep + dpp_mov<0xB1>(send);   // quad_perm [1,0,3,2]
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float keep = b1 ? y[2 * j + 1] : y[2 * j], send = b1 ? y[2 * j] : y[2 * j + 1];
-        z[j] = keep + dpp_mov<0x4E>(send);   // quad_perm [2,3,0,1]
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const float keep = b2 ? z[2 * j + 1] : z[2 * j], send = b2 ? z[2 * j] : z[2 * j + 1];
-        u[j] = keep + dpp_mov<0x124>(send);  // row_ror 4
-    }
-    const float keep = b3 ? u[1] : u[0], send = b3 ? u[0] : u[1];
-    return keep + dpp_mov<0x128>(send);      // row_ror 8
-}
-// collects the per-channel gradients of a tile in slot order and runs a butterfly whenever 16 are there
-struct PgCollect {
-    float buf[16];
-    template <int IDX>
-    CSMPN_DEV void add(float v, float (&small)[5], int l16) {
-        buf[IDX % 16] = v;
-        if constexpr (IDX % 16 == 15) small[IDX / 16] += pg_rows_sum(buf, l16);
-    }
-};
-
-// geometric product backward, all 32 blades in the lane, two passes (each keeps four tensors live):
-//   Z: gz[i] += w_p U[i], gw_p = sum_i z[i] U[i],  U[i] = sum sign ggp[j] r[k];   R: gr[k] = sum_p w_p sum sign ggp[j] z[i]
-template <class ALG>
-CSMPN_DEV void pg_gp_bwd_z(const float (&ggp)[32], const float (&z)[32], const float (&rf)[32], float (&gz)[32], const float* wrow,
-                           PgCollect& col, float (&small)[5], int l16) {
-    constexpr int P = ALG::P;
-    static_for<0, P / 4>([&](auto qq) {
-        const f4 wv = pg_ld4(wrow + 4 * decltype(qq)::value);
-        static_for<0, 4>([&](auto pp) {
-            constexpr int p = 4 * decltype(qq)::value + decltype(pp)::value;
-            constexpr int gi = ALG::t.path_g[p][0], gj = ALG::t.path_g[p][1], gk = ALG::t.path_g[p][2];
-            constexpr int i0 = ALG::gstart(gi), ni = ALG::gsize(gi);
-            constexpr int j0 = ALG::gstart(gj), nj = ALG::gsize(gj);
-            constexpr int k0 = ALG::gstart(gk), nk = ALG::gsize(gk);
-            const float w = wv[decltype(pp)::value];
-            float U[ni];
-#pragma unroll
-            for (int t = 0; t < ni; ++t) U[t] = 0.f;
-            static_for<0, ni>([&](auto ii) {
-                static_for<0, nk>([&](auto kk) {
-                    constexpr int i = i0 + ii, k = k0 + kk;
-                    constexpr int j = ALG::t.out[i][k];
-                    if constexpr (j >= j0 && j < j0 + nj) {
-                        constexpr float sg = float(ALG::t.sign[i][k]);
-                        U[ii] = __builtin_fmaf(sg * ggp[j], rf[k], U[ii]);
-                    }
-                });
-            });
-            float gwv = 0.f;
-#pragma unroll
-            for (int t = 0; t < ni; ++t) { gz[i0 + t] = __builtin_fmaf(w, U[t], gz[i0 + t]); gwv = __builtin_fmaf(z[i0 + t], U[t], gwv); }
-            col.template add<p>(gwv, small, l16);
-        });
-    });
-}
-template <class ALG>
-CSMPN_DEV void pg_gp_bwd_r(const float (&ggp)[32], const float (&z)[32], float (&gr)[32], const float* wrow) {
-    constexpr int P = ALG::P;
-    static_for<0, P / 4>([&](auto qq) {
-        const f4 wv = pg_ld4(wrow + 4 * decltype(qq)::value);
-        static_for<0, 4>([&](auto pp) {
-            constexpr int p = 4 * decltype(qq)::value + decltype(pp)::value;
-            constexpr int gi = ALG::t.path_g[p][0], gj = ALG::t.path_g[p][1], gk = ALG::t.path_g[p][2];
-            constexpr int i0 = ALG::gstart(gi), ni = ALG::gsize(gi);
-            constexpr int j0 = ALG::gstart(gj), nj = ALG::gsize(gj);
-            constexpr int k0 = ALG::gstart(gk), nk = ALG::gsize(gk);
-            const float w = wv[decltype(pp)::value];
-            float V[nk];
-#pragma unroll
-            for (int t = 0; t < nk; ++t) V[t] = 0.f;
-            static_for<0, ni>([&](auto ii) {
-                static_for<0, nk>([&](auto kk) {
-                    constexpr int i = i0 + ii, k = k0 + kk;
-                    constexpr int j = ALG::t.out[i][k];
-                    if constexpr (j >= j0 && j < j0 + nj) {
-                        constexpr float sg = float(ALG::t.sign[i][k]);
-                        V[kk] = __builtin_fmaf(sg * ggp[j], z[i], V[kk]);
-                    }
-                });
-            });
-#pragma unroll
-            for (int t = 0; t < nk; ++t) gr[k0 + t] = __builtin_fmaf(w, V[t], gr[k0 + t]);
-        });
-    });
-}
-
 // d/dW tile (ot, ct) += G^T X over the 16 rows, the 16 blades of one half: acc[gs] = the half's three grades.
 // G: gradient tile (its channel slots are the rows of the matrix), X: operand tile, both in LDS.
 template <int HALF>
@@ -769,8 +630,8 @@ CSMPN_DEV void pg_wgrad_half(f4 (&acc)[3], const float* bufG, const float* bufX,
         f4 a[4], b[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            a[s] = pg_ld4(bufG + pg_off(16 * ot + i, 4 * s + k, j));
-            b[s] = pg_ld4(bufX + pg_off(16 * ct + (i & xmask), 4 * s + k, j));
+            a[s] = ld4(bufG + pg_off(16 * ot + i, 4 * s + k, j));
+            b[s] = ld4(bufX + pg_off(16 * ct + (i & xmask), 4 * s + k, j));
         }
         static_for<0, 4>([&](auto bb) {
             constexpr int d = 4 * j + decltype(bb)::value;
@@ -798,15 +659,14 @@ CSMPN_DEV void pg_wgrad1(f4 (&acc)[3], const float* bufG, const float* bufX, int
 template <int NCT>
 CSMPN_DEV void pg_store_unit(float* base, const f4 (&acc)[3], int ot, int ct, int half, int lane) {
 #pragma unroll
-    for (int gs = 0; gs < 3; ++gs) pg_st4(base + ((((3 * half + gs) * 2 + ot) * NCT + ct) * 64 + lane) * 4, acc[gs]);
+    for (int gs = 0; gs < 3; ++gs) st4(base + ((((3 * half + gs) * 2 + ot) * NCT + ct) * 64 + lane) * 4, acc[gs]);
 }
 
 // lane-derived indices of ONE phase. The thread id passes through an empty asm statement: derived from the same value in
 // every phase, the LDS addresses of all phases (hundreds: the XOR swizzle makes every (row, piece) pair its own value) are
 // loop invariants that the compiler computes once and keeps alive across the tile loop - 370 spills per tile.
-CSMPN_DEV int pg_tid() { int t = threadIdx.x; asm volatile("" : "+v"(t)); return t; }
 #define PG_PHASE_IDS()                                                                                              \
-    const int tid = pg_tid();                                                                                       \
+    const int tid = fenced_tid();                                                                                   \
     const int wave = tid >> 6, lane = tid & 63, r = lane & 15, c = 4 * wave + (lane >> 4), l16 = lane & 15;         \
     const bool cvalid = c < C, live = cvalid && row0 + r < io.rows;                                                 \
     const float* par = smem + CF::b_par + c * CF::par_stride;                                                       \
@@ -816,12 +676,7 @@ CSMPN_DEV int pg_tid() { int t = threadIdx.x; asm volatile("" : "+v"(t)); return
 
 template <class ALG, class CF, int K>
 __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     constexpr int C = CF::C, MODE = CF::MODE, NA = CF::NA, D = 32, G = 6, P = CF::P, ROW = CF::ROW, NST = CF::NST;
     constexpr int ROWP = 32 * D, PPR = C * 8;
     constexpr int NM = CF::nmat(K), mR = NM - 2, mL = NM - 1;
@@ -889,9 +744,9 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
             if (idx[rr] >= 0) {
                 if constexpr (K == 1) {
                     const size_t grow = MODE == MODE_EDGE ? (size_t)idx[rr] : (size_t)(tile_ * kPgRows + rr);
-                    pre[i] = pg_ld4(io.gy + grow * ROW + 4 * e);
+                    pre[i] = ld4(io.gy + grow * ROW + 4 * e);
                 } else {
-                    pre[i] = pg_ld4(io.plw_g1 + (size_t)(tile_ * kPgRows + rr) * ROW + 4 * e);
+                    pre[i] = ld4(io.plw_g1 + (size_t)(tile_ * kPgRows + rr) * ROW + 4 * e);
                 }
             }
         }
@@ -917,7 +772,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
 #pragma unroll
         for (int i = 0; i < NPRE; ++i) {
             const int p = tid + i * kPgThreads, rr = p / PPR, e = p % PPR;
-            pg_st4(bufA + pg_off(e >> 3, rr, e & 7), pre[i]);
+            st4(bufA + pg_off(e >> 3, rr, e & 7), pre[i]);
         }
         if (tid < kPgRows) load_idx(sidx_n, tile + gridDim.x, tid);
         }
@@ -962,7 +817,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
             float tot = 0.f, totd = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const f4 v1 = pg_ld4(ln1 + r * 32 + 4 * j), v2 = pg_ld4(ln2 + r * 32 + 4 * j);
+                const f4 v1 = ld4(ln1 + r * 32 + 4 * j), v2 = ld4(ln2 + r * 32 + 4 * j);
                 tot += (v1.x + v1.y) + (v1.z + v1.w);
                 totd += (v2.x + v2.y) + (v2.z + v2.w);
             }
@@ -1007,7 +862,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
         stamp(3);
         // ---- ROW: geometric product + normalisation backward -> gR -> B; gz stays in registers
         float gz[32];
-        PgCollect col;
+        RowsCollect<5> col;
         {
             PG_PHASE_IDS();
             float z[32];
@@ -1030,13 +885,13 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
                 for (int t = 0; t < nd; ++t) R[d0 + t] *= invden[g];    // R holds r = R / den from here on (R = r den where it is needed again)
             });
             float (&rf)[32] = R;
-            pg_gp_bwd_z<ALG>(ggp, z, rf, gz, wrow, col, small, l16);
+            lane_gp_bwd_z<ALG>(ggp, z, rf, gz, wrow, col, small, l16);
             pg_pin32(gz);
             CSMPN_PHASE();
             float gr[32];
 #pragma unroll
             for (int d = 0; d < 32; ++d) gr[d] = 0.f;
-            pg_gp_bwd_r<ALG>(ggp, z, gr, wrow);
+            lane_gp_bwd_r<ALG>(ggp, z, gr, wrow);
             pg_pin32(gr);
             CSMPN_PHASE();
             // NormalizationLayer backward: gR (into gr), d/d(an)
@@ -1097,11 +952,11 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
             xa[i] = f4{0.f, 0.f, 0.f, 0.f};
             if constexpr (K == 0 && MODE == MODE_EDGE) xb[i] = f4{0.f, 0.f, 0.f, 0.f};
             if (sidx[rr] >= 0) {
-                if constexpr (K == 1) xa[i] = pg_ld4(io.saved + (size_t)(row0 + rr) * ROW + 4 * e);
+                if constexpr (K == 1) xa[i] = ld4(io.saved + (size_t)(row0 + rr) * ROW + 4 * e);
                 else if constexpr (MODE == MODE_EDGE) {
-                    xa[i] = pg_ld4(io.seg[0].a + (size_t)sidx[rr] * ROW + 4 * e);
-                    xb[i] = pg_ld4(io.seg[0].b + (size_t)sidx[16 + rr] * ROW + 4 * e);
-                } else xa[i] = pg_ld4(io.seg[0].a + (size_t)(row0 + rr) * ROW + 4 * e);
+                    xa[i] = ld4(io.seg[0].a + (size_t)sidx[rr] * ROW + 4 * e);
+                    xb[i] = ld4(io.seg[0].b + (size_t)sidx[16 + rr] * ROW + 4 * e);
+                } else xa[i] = ld4(io.seg[0].a + (size_t)(row0 + rr) * ROW + 4 * e);
             }
         }
         if constexpr (K == 0) {
@@ -1110,10 +965,10 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
                 const int rr = p / PPA, e = p % PPA;
                 f4 v = f4{0.f, 0.f, 0.f, 0.f};
                 if (sidx[rr] >= 0 && e < NA * 8) {
-                    if constexpr (MODE == MODE_EDGE) v = pg_ld4(io.seg[1].a + (size_t)sidx[32 + rr] * (NA * D) + 4 * e);
-                    else v = pg_ld4(io.seg[2].a + (size_t)(row0 + rr) * (NA * D) + 4 * e);
+                    if constexpr (MODE == MODE_EDGE) v = ld4(io.seg[1].a + (size_t)sidx[32 + rr] * (NA * D) + 4 * e);
+                    else v = ld4(io.seg[2].a + (size_t)(row0 + rr) * (NA * D) + 4 * e);
                 }
-                if (e < 8 * 8) pg_st4(bufE + pg_off(e >> 3, rr, e & 7), v);
+                if (e < 8 * 8) st4(bufE + pg_off(e >> 3, rr, e & 7), v);
             }
         }
         }
@@ -1161,7 +1016,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
             for (int i = 0; i < NPRE; ++i) {
                 const int p = tid + i * kPgThreads, rr = p / PPR, e = p % PPR;
                 if constexpr (K == 0 && MODE == MODE_EDGE) xa[i] -= xb[i];
-                pg_st4(bufA + pg_off(e >> 3, rr, e & 7), xa[i]);
+                st4(bufA + pg_off(e >> 3, rr, e & 7), xa[i]);
             }
         }
         __syncthreads();
@@ -1204,8 +1059,8 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
             for (int p = tid; p < kPgRows * PPR; p += kPgThreads) {
                 const int rr = p / PPR, e = p % PPR;
                 f4 v = f4{0.f, 0.f, 0.f, 0.f};
-                if (sidx[rr] >= 0) v = pg_ld4(io.seg[1].a + (size_t)(row0 + rr) * ROW + 4 * e) * sscale[rr];
-                pg_st4(bufA + pg_off(e >> 3, rr, e & 7), v);
+                if (sidx[rr] >= 0) v = ld4(io.seg[1].a + (size_t)(row0 + rr) * ROW + 4 * e) * sscale[rr];
+                st4(bufA + pg_off(e >> 3, rr, e & 7), v);
             }
             __syncthreads();
             pg_zero(accg);
@@ -1226,14 +1081,14 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
         if constexpr (K == 1) {
             for (int p = tid; p < kPgRows * PPR; p += kPgThreads) {
                 const int rr = p / PPR, e = p % PPR;
-                if (row0 + rr < io.rows) pg_st4(io.plw_g1 + (size_t)(row0 + rr) * ROW + 4 * e, pg_ld4(bufB + pg_off(e >> 3, rr, e & 7)));
+                if (row0 + rr < io.rows) st4(io.plw_g1 + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pg_off(e >> 3, rr, e & 7)));
             }
         } else if constexpr (MODE == MODE_EDGE) {
             if (io.gx[0]) {
                 if (io.row_store) {
                     for (int p = tid; p < kPgRows * PPR; p += kPgThreads) {
                         const int rr = p / PPR, e = p % PPR;
-                        if (row0 + rr < io.rows) pg_st4(io.gx[0] + (size_t)(row0 + rr) * ROW + 4 * e, pg_ld4(bufB + pg_off(e >> 3, rr, e & 7)));
+                        if (row0 + rr < io.rows) st4(io.gx[0] + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pg_off(e >> 3, rr, e & 7)));
                     }
                 } else {
                     for (int col_ = tid; col_ < ROW; col_ += kPgThreads) {
@@ -1259,7 +1114,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
             if (io.gx[1]) {
                 for (int p = tid; p < kPgRows * NA * 8; p += kPgThreads) {
                     const int rr = p / (NA * 8), e = p % (NA * 8);
-                    if (row0 + rr < io.rows) pg_st4(io.gx[1] + (size_t)sidx[32 + rr] * (NA * D) + 4 * e, pg_ld4(bufE + pg_off(e >> 3, rr, e & 7)));
+                    if (row0 + rr < io.rows) st4(io.gx[1] + (size_t)sidx[32 + rr] * (NA * D) + 4 * e, ld4(bufE + pg_off(e >> 3, rr, e & 7)));
                 }
             }
         } else {
@@ -1267,17 +1122,17 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
                 const int rr = p / PPR, e = p % PPR;
                 if (row0 + rr < io.rows) {
                     if (io.gx[0]) {
-                        f4 v = pg_ld4(bufA + pg_off(e >> 3, rr, e & 7));
-                        if (io.resid_bwd) v += pg_ld4(io.gy + (size_t)(row0 + rr) * ROW + 4 * e);
-                        pg_st4(io.gx[0] + (size_t)(row0 + rr) * ROW + 4 * e, v);
+                        f4 v = ld4(bufA + pg_off(e >> 3, rr, e & 7));
+                        if (io.resid_bwd) v += ld4(io.gy + (size_t)(row0 + rr) * ROW + 4 * e);
+                        st4(io.gx[0] + (size_t)(row0 + rr) * ROW + 4 * e, v);
                     }
-                    if (io.gx[1]) pg_st4(io.gx[1] + (size_t)(row0 + rr) * ROW + 4 * e, pg_ld4(bufB + pg_off(e >> 3, rr, e & 7)) * sscale[rr]);
+                    if (io.gx[1]) st4(io.gx[1] + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pg_off(e >> 3, rr, e & 7)) * sscale[rr]);
                 }
             }
             if (io.gx[2]) {
                 for (int p = tid; p < kPgRows * NA * 8; p += kPgThreads) {
                     const int rr = p / (NA * 8), e = p % (NA * 8);
-                    if (row0 + rr < io.rows) pg_st4(io.gx[2] + (size_t)(row0 + rr) * (NA * D) + 4 * e, pg_ld4(bufE + pg_off(e >> 3, rr, e & 7)));
+                    if (row0 + rr < io.rows) st4(io.gx[2] + (size_t)(row0 + rr) * (NA * D) + 4 * e, ld4(bufE + pg_off(e >> 3, rr, e & 7)));
                 }
             }
         }

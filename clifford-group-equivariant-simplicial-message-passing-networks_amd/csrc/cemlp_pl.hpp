@@ -69,7 +69,6 @@ CSMPN_DEV float pl_chan_sum(float v) {
     v += dpp_mov<0x128>(v);   // row_ror 8
     return v;
 }
-CSMPN_DEV f4 pl_ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
 // Ordering point for the instruction scheduler. A bare sched_barrier does not order pure arithmetic (the
 // selection DAG sinks it below a run of barriers and the whole phase becomes one region with hundreds of
 // values in flight); passing the values just produced through an empty volatile asm ties them to the barrier.
@@ -263,14 +262,14 @@ template <class ALG>
 CSMPN_DEV void pl_load(float (&x)[PS<ALG>::DL], const float* p, int s, float scale) {
     f4 v[ALG::D / 4];
 #pragma unroll
-    for (int e = 0; e < ALG::D / 4; ++e) v[e] = pl_ld4(p + 4 * e);
+    for (int e = 0; e < ALG::D / 4; ++e) v[e] = ld4(p + 4 * e);
     pl_pick<ALG>(x, v, s, scale);
 }
 template <class ALG>
 CSMPN_DEV void pl_load_diff(float (&x)[PS<ALG>::DL], const float* pa, const float* pb, int s, float scale) {
     f4 v[ALG::D / 4];
 #pragma unroll
-    for (int e = 0; e < ALG::D / 4; ++e) v[e] = pl_ld4(pa + 4 * e) - pl_ld4(pb + 4 * e);
+    for (int e = 0; e < ALG::D / 4; ++e) v[e] = ld4(pa + 4 * e) - ld4(pb + 4 * e);
     pl_pick<ALG>(x, v, s, scale);
 }
 // this lane's half tensor -> the wave's staging tile [4 rows][nch * D (+4)], reference blade order
@@ -880,7 +879,7 @@ CSMPN_DEV void pl_copy_rows(const float* sc, int rs, int ncol, int lane, F&& out
     for (int r = 0; r < kPlRows; ++r) {
         float* dst = out_row(r);
         if (dst)
-            for (int e = 4 * lane; e < ncol; e += 256) *reinterpret_cast<f4*>(dst + e) = pl_ld4(sc + r * rs + e);
+            for (int e = 4 * lane; e < ncol; e += 256) *reinterpret_cast<f4*>(dst + e) = ld4(sc + r * rs + e);
     }
 }
 // scatter-add of the staged rows to table[t_add[row]] (sorted targets: equal consecutive targets are summed first)
@@ -922,12 +921,7 @@ CSMPN_DEV void pl_scatter(const float* sc, int rs, int t_add, int t_sub, float* 
 // saved buffer hold s, y, R of block 0 / 1 (pl_store_state; a compile-time choice, as in cemlp_cl.hpp).
 template <class ALG, int MODE, int NBLK, int I0, bool BWD, bool SAVES = false>
 __global__ void __launch_bounds__(64 * kPlWaves, BWD ? CSMPN_PL_BWD_WAVES : CSMPN_PL_FWD_WAVES) cemlp_pl_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     using LY = PlLay<ALG, NBLK, I0>;
     using P = PS<ALG>;
     constexpr int D = ALG::D, DL = P::DL, GC = P::GC, C = 8, ROW = C * D, RS = LY::RS, NCH0 = LY::nch(0);

@@ -131,7 +131,7 @@ __global__ void plw_pack_kernel(const DevCemlp Cd, float* tabs) {
 // the 24 weights of this lane for one (output group, input group) block: 6 x 16 bytes from the packed tables (L2)
 CSMPN_DEV void plw_ldw(f4 (&wv)[6], const float* tp) {
 #pragma unroll
-    for (int e = 0; e < 6; ++e) wv[e] = pl_ld4(tp + 4 * e);
+    for (int e = 0; e < 6; ++e) wv[e] = ld4(tp + 4 * e);
 }
 // acc[j] += sum_r T[r][class(j)] * rot_r(x[j])
 template <class ALG>
@@ -320,12 +320,7 @@ template <class ALG, class CF>
 __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? (CF::fwd_total * 4 <= 80 * 1024 ? 2 * CF::WG_PER_CU_BWD : CF::WG_PER_CU_BWD)
                                                              : CF::waves_per_simd(CF::fwd_total * 4 <= 80 * 1024 ? 2 * CF::WG_PER_CU_BWD : CF::WG_PER_CU_BWD))
     cemlp_plw_fwd_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     using P = PS<ALG>;
     constexpr int D = ALG::D, DL = P::DL, G = ALG::G, NG = CF::NG, C = CF::C, CP = CF::CP, ROW = CF::ROW, RS = CF::RS;
     constexpr int MODE = CF::MODE, NA = CF::NA, NT = 64 * NG, NCH0 = CF::NCH0;
@@ -455,7 +450,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? (CF::fwd_total * 4 
                     const long rr = tile * kPlRows + r;
                     if (rr < io.rows)
                         for (int e = 4 * threadIdx.x; e < ROW; e += 4 * NT)
-                            *reinterpret_cast<f4*>(io.save + (size_t)rr * ROW + e) = pl_ld4(stg + r * RS + e);
+                            *reinterpret_cast<f4*>(io.save + (size_t)rr * ROW + e) = ld4(stg + r * RS + e);
                 }
             }
 #pragma unroll
@@ -486,7 +481,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? (CF::fwd_total * 4 
                     const long rr = tile * kPlRows + r;
                     if (rr < io.rows)
                         for (int e = 4 * threadIdx.x; e < ROW; e += 4 * NT)
-                            *reinterpret_cast<f4*>(io.agg + (size_t)rr * ROW + e) = pl_ld4(stg + r * RS + e);
+                            *reinterpret_cast<f4*>(io.agg + (size_t)rr * ROW + e) = ld4(stg + r * RS + e);
                 }
             } else
             for (int col = threadIdx.x; col < ROW; col += NT) {
@@ -513,7 +508,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? (CF::fwd_total * 4 
                     const long rr = tile * kPlRows + r;
                     if (rr < io.rows) {
                         const int slot = (int)(rr / emb_np - s0);
-                        const f4 v = pl_ld4(stg + r * RS + e);
+                        const f4 v = ld4(stg + r * RS + e);
 #pragma unroll
                         for (int i = 0; i < kPlRows; ++i) if (i == slot) eacc[i] += v;
                     }
@@ -524,7 +519,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? (CF::fwd_total * 4 
                 const long rr = tile * kPlRows + r;
                 if (rr < io.rows)
                     for (int e = 4 * threadIdx.x; e < ROW; e += 4 * NT)
-                        *reinterpret_cast<f4*>(io.y + (size_t)rr * ROW + e) = pl_ld4(stg + r * RS + e);
+                        *reinterpret_cast<f4*>(io.y + (size_t)rr * ROW + e) = ld4(stg + r * RS + e);
             }
         }
         __syncthreads();                  // staging tile and exchange buffers free for the next tile
@@ -766,12 +761,7 @@ __global__ void __launch_bounds__(64 * kPlReduceSubs) plw_reduce_kernel(const De
 // compile-time choice, as in cemlp_pl.hpp / cemlp_cl.hpp.
 template <class ALG, class CF, int BLK, bool SAVES = false>
 __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? CF::WG_PER_CU_BWD : CF::waves_per_simd(CF::WG_PER_CU_BWD)) cemlp_plw_bwd_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     using P = PS<ALG>;
     using SI = PlSumIdx<ALG>;
     constexpr int D = ALG::D, DL = P::DL, G = ALG::G, GC = P::GC, NG = CF::NG, C = CF::C, CP = CF::CP, ROW = CF::ROW, RS = CF::RS;
@@ -881,7 +871,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? CF::WG_PER_CU_BWD :
                 const long rr = tile * kPlRows + r;
                 if (rr < io.rows)
                     for (int e = 4 * threadIdx.x; e < ROW; e += 4 * NT)
-                        *reinterpret_cast<f4*>(io.plw_g1 + (size_t)rr * ROW + e) = pl_ld4(stg + r * RS + e);
+                        *reinterpret_cast<f4*>(io.plw_g1 + (size_t)rr * ROW + e) = ld4(stg + r * RS + e);
             }
             __syncthreads();
         } else {
@@ -971,7 +961,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? CF::WG_PER_CU_BWD :
                     const long rr = tile * kPlRows + r;
                     if (rr < io.rows) {
                         float* d = dst + (size_t)row_of(r, rr) * ncol;
-                        for (int e = 4 * threadIdx.x; e < ncol; e += 4 * NT) *reinterpret_cast<f4*>(d + e) = pl_ld4(stg + r * RS + e);
+                        for (int e = 4 * threadIdx.x; e < ncol; e += 4 * NT) *reinterpret_cast<f4*>(d + e) = ld4(stg + r * RS + e);
                     }
                 }
             };

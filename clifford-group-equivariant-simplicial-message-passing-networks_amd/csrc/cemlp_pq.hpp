@@ -24,8 +24,7 @@
 // Backward: one launch per block on the state the forward saved (y, R, s in ROW-layout lane order), phases as cemlp_pg.hpp;
 // a wave owns ONE (o-tile, c-tile) tile of every weight gradient (all four grades: 16 registers per matrix).
 #pragma once
-#include "cemlp_device.hpp"
-#include "cemlp_pg.hpp"   // pg_pack_kernel, pg_ld4 / pg_st4, pg_rows_sum, pg_tid, PgStamp
+#include "cemlp_pg.hpp"   // pg_pack_kernel, PgStamp; through it cemlp_lane.hpp: ld4 / st4, the in-lane geometric product, RowsCollect, fenced_tid
 
 namespace csmpn {
 
@@ -129,7 +128,7 @@ CSMPN_DEV void pq_mix_run(f4 (&acc)[4], const float* buf, const PqA<NSTEP>& a, i
     const float* bp = buf + pq_off(k, n, p);
     f4 b[NSTEP];
 #pragma unroll
-    for (int s = 0; s < NSTEP; ++s) b[s] = pg_ld4(bp + 4 * s * kPqCS);
+    for (int s = 0; s < NSTEP; ++s) b[s] = ld4(bp + 4 * s * kPqCS);
 #pragma unroll
     for (int s = 0; s < NSTEP; ++s) {
         const float a0 = a.lo[s / 4][s % 4], a3 = a.hi[s / 4][s % 4];
@@ -153,7 +152,7 @@ CSMPN_DEV void pq_mix_run2(f4 (&accR)[4], f4 (&accL)[4], const float* buf, const
     const float* bp = buf + pq_off(k, n, p);
     f4 b[NSTEP];
 #pragma unroll
-    for (int s = 0; s < NSTEP; ++s) b[s] = pg_ld4(bp + 4 * s * kPqCS);
+    for (int s = 0; s < NSTEP; ++s) b[s] = ld4(bp + 4 * s * kPqCS);
     static_for<0, 2>([&](auto mm) {
         const PqA<NSTEP>& a = decltype(mm)::value == 0 ? aR : aL;
 #pragma unroll
@@ -186,17 +185,17 @@ CSMPN_DEV void pq_write_d(float* buf, const f4 (&acc)[4], int lane, int p, int o
 #pragma unroll
     for (int v = 0; v < 4; ++v)
         if (SLOTS >= 32 || 16 * ot + 4 * q + v < SLOTS)
-            pg_st4(buf + pq_off(16 * ot + 4 * q + v, n, p), f4{acc[0][v], acc[1][v], acc[2][v], acc[3][v]});
+            st4(buf + pq_off(16 * ot + 4 * q + v, n, p), f4{acc[0][v], acc[1][v], acc[2][v], acc[3][v]});
 }
 
 // ROW layout: the 8 blades of (row r, channel slot c)
 CSMPN_DEV void pq_ld8(float (&t)[8], const float* buf, int r, int c) {
-    const f4 a = pg_ld4(buf + pq_off(c, r, 0)), b = pg_ld4(buf + pq_off(c, r, 1));
+    const f4 a = ld4(buf + pq_off(c, r, 0)), b = ld4(buf + pq_off(c, r, 1));
     t[0] = a.x; t[1] = a.y; t[2] = a.z; t[3] = a.w; t[4] = b.x; t[5] = b.y; t[6] = b.z; t[7] = b.w;
 }
 CSMPN_DEV void pq_st8(float* buf, int r, int c, const float (&t)[8]) {
-    pg_st4(buf + pq_off(c, r, 0), f4{t[0], t[1], t[2], t[3]});
-    pg_st4(buf + pq_off(c, r, 1), f4{t[4], t[5], t[6], t[7]});
+    st4(buf + pq_off(c, r, 0), f4{t[0], t[1], t[2], t[3]});
+    st4(buf + pq_off(c, r, 1), f4{t[4], t[5], t[6], t[7]});
 }
 CSMPN_DEV void pq_pin8(float (&t)[8]) {
     asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]));
@@ -229,48 +228,11 @@ CSMPN_DEV float pq_sum_q(float v) {
     return v;
 }
 
-// out[j] += sum_p w[p] sum_{(i,k) -> j in path p} sign(i,k) z[i] r[k]   (cegnn_utils.py:126-152); wrow: this channel's P path weights (LDS)
-template <class ALG>
-CSMPN_DEV void pq_weighted_gp(float (&out)[8], const float (&z)[8], const float (&r)[8], const float* wrow) {
-    constexpr int P = ALG::P;
-    static_for<0, P / 4>([&](auto qq) {
-        const f4 wv = pg_ld4(wrow + 4 * decltype(qq)::value);
-        static_for<0, 4>([&](auto pp) {
-            constexpr int p = 4 * decltype(qq)::value + decltype(pp)::value;
-            constexpr int gi = ALG::t.path_g[p][0], gj = ALG::t.path_g[p][1], gk = ALG::t.path_g[p][2];
-            constexpr int i0 = ALG::gstart(gi), ni = ALG::gsize(gi);
-            constexpr int j0 = ALG::gstart(gj), nj = ALG::gsize(gj);
-            constexpr int k0 = ALG::gstart(gk), nk = ALG::gsize(gk);
-            const float w = wv[decltype(pp)::value];
-            float tmp[nj];
-#pragma unroll
-            for (int t = 0; t < nj; ++t) tmp[t] = 0.f;
-            static_for<0, ni>([&](auto ii) {
-                static_for<0, nk>([&](auto kk) {
-                    constexpr int i = i0 + ii, k = k0 + kk;
-                    constexpr int j = ALG::t.out[i][k];
-                    if constexpr (j >= j0 && j < j0 + nj) {
-                        constexpr float sg = float(ALG::t.sign[i][k]);
-                        tmp[j - j0] = __builtin_fmaf(sg * z[i], r[k], tmp[j - j0]);
-                    }
-                });
-            });
-#pragma unroll
-            for (int t = 0; t < nj; ++t) out[j0 + t] = __builtin_fmaf(w, tmp[t], out[j0 + t]);
-        });
-    });
-}
-
 // ---------------------------------------------------------------------------------
 // forward kernel: two blocks of C channels, EGCL edge / node program
 template <class ALG, class CF>
 __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCemlp C_arg, const RowIO io_arg) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     constexpr int C = CF::C, MODE = CF::MODE, NA = CF::NA, D = 8, G = 4, P = CF::P, ROW = CF::ROW, NST = CF::NST;
     constexpr bool PLAIN = CF::PLAIN;
     constexpr int NBLK = CF::NBLK, I0 = CF::I0, NCH0 = CF::NCH0;
@@ -331,7 +293,7 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
     };
     // plain program: input chunk m of row `row` (pieces 64 m .. 64 m + 63 of the I0-channel row; zero beyond it)
     auto plain_piece = [&](long row, int m, int e) {
-        return 64 * m + e < 2 * I0 ? pg_ld4(io.seg[0].a + (size_t)row * (I0 * D) + 256 * m + 4 * e) : f4{0.f, 0.f, 0.f, 0.f};
+        return 64 * m + e < 2 * I0 ? ld4(io.seg[0].a + (size_t)row * (I0 * D) + 256 * m + 4 * e) : f4{0.f, 0.f, 0.f, 0.f};
     };
     f4 pre_a[NPRE], pre_b[NPRE], pre_x[PLAIN && NCH0 == 3 ? NPRE : NPA];
     auto issue_rows = [&](const int* idx, long tile_, int t) {
@@ -356,15 +318,15 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
             if constexpr (PLAIN && NCH0 == 3) pre_x[i] = f4{0.f, 0.f, 0.f, 0.f};
             if (ia[i] >= 0) {
                 if constexpr (MODE == MODE_EDGE) {
-                    pre_a[i] = pg_ld4(io.seg[0].a + (size_t)ia[i] * ROW + 4 * e);
-                    pre_b[i] = pg_ld4(io.seg[0].b + (size_t)ib[i] * ROW + 4 * e);
+                    pre_a[i] = ld4(io.seg[0].a + (size_t)ia[i] * ROW + 4 * e);
+                    pre_b[i] = ld4(io.seg[0].b + (size_t)ib[i] * ROW + 4 * e);
                 } else if constexpr (PLAIN) {
                     pre_a[i] = plain_piece(tile_ * kPqRows + rr, 0, e);
                     if constexpr (NCH0 >= 2) pre_b[i] = plain_piece(tile_ * kPqRows + rr, 1, e);
                     if constexpr (NCH0 == 3) pre_x[i] = plain_piece(tile_ * kPqRows + rr, 2, e);
                 } else {
-                    pre_a[i] = pg_ld4(io.seg[0].a + (size_t)(tile_ * kPqRows + rr) * ROW + 4 * e);
-                    pre_b[i] = pg_ld4(io.seg[1].a + (size_t)(tile_ * kPqRows + rr) * ROW + 4 * e) * sc_[rr];
+                    pre_a[i] = ld4(io.seg[0].a + (size_t)(tile_ * kPqRows + rr) * ROW + 4 * e);
+                    pre_b[i] = ld4(io.seg[1].a + (size_t)(tile_ * kPqRows + rr) * ROW + 4 * e) * sc_[rr];
                 }
             }
         }
@@ -374,8 +336,8 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
                 const int p = t + i * kPqThreads, rr = (p / PPA) & 15, e = p % PPA;
                 pre_x[i] = f4{0.f, 0.f, 0.f, 0.f};
                 if (p < kPqRows * PPA && idx[rr] >= 0 && e < NA * 2) {
-                    if constexpr (MODE == MODE_EDGE) pre_x[i] = pg_ld4(io.seg[1].a + (size_t)idx[32 + rr] * (NA * D) + 4 * e);
-                    else pre_x[i] = pg_ld4(io.seg[2].a + (size_t)(tile_ * kPqRows + rr) * (NA * D) + 4 * e);
+                    if constexpr (MODE == MODE_EDGE) pre_x[i] = ld4(io.seg[1].a + (size_t)idx[32 + rr] * (NA * D) + 4 * e);
+                    else pre_x[i] = ld4(io.seg[2].a + (size_t)(tile_ * kPqRows + rr) * (NA * D) + 4 * e);
                 }
             }
         }
@@ -406,10 +368,10 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
             for (int i = 0; i < NPRE; ++i) {
                 const int rr = pq_row_of(tid, i), e = tid & 63;
                 if constexpr (MODE == MODE_EDGE) {
-                    pg_st4(bufA + pq_off(e >> 1, rr, e & 1), pre_a[i] - pre_b[i]);
+                    st4(bufA + pq_off(e >> 1, rr, e & 1), pre_a[i] - pre_b[i]);
                 } else {
-                    pg_st4(bufA + pq_off(e >> 1, rr, e & 1), pre_a[i]);
-                    if constexpr (!PLAIN || NCH0 >= 2) pg_st4(bufB + pq_off(e >> 1, rr, e & 1), pre_b[i]);
+                    st4(bufA + pq_off(e >> 1, rr, e & 1), pre_a[i]);
+                    if constexpr (!PLAIN || NCH0 >= 2) st4(bufB + pq_off(e >> 1, rr, e & 1), pre_b[i]);
                 }
             }
             if constexpr (!PLAIN) {
@@ -417,7 +379,7 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
 #pragma unroll
                 for (int i = 0; i < NPA; ++i) {
                     const int p = tid + i * kPqThreads, rr = (p / PPA) & 15, e = p % PPA;
-                    if (p < kPqRows * PPA) pg_st4(bufX + pq_off(e >> 1, rr, e & 1), pre_x[i]);
+                    if (p < kPqRows * PPA) st4(bufX + pq_off(e >> 1, rr, e & 1), pre_x[i]);
                 }
             }
             if (tid < kPqRows) load_idx(sidx_n, tile + gridDim.x, tid);
@@ -445,7 +407,7 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
 #pragma unroll
                             for (int i = 0; i < NPRE; ++i) {
                                 const int rr = pq_row_of(tid, i), e = tid & 63;
-                                pg_st4(bufB + pq_off(e >> 1, rr, e & 1), pre_x[i]);
+                                st4(bufB + pq_off(e >> 1, rr, e & 1), pre_x[i]);
                             }
                             __syncthreads();
                             pq_mix_run(acc, bufB, aW0x, lane, mp);
@@ -462,7 +424,7 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
 #pragma unroll
                         for (int i = 0; i < NPRE; ++i) {
                             const int rr = pq_row_of(tid, i), e = tid & 63;
-                            if (row0 + rr < io.rows) pg_st4(io.save + (size_t)(row0 + rr) * ROW + 4 * e, pg_ld4(bufB + pq_off(e >> 1, rr, e & 1)));
+                            if (row0 + rr < io.rows) st4(io.save + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pq_off(e >> 1, rr, e & 1)));
                         }
                     }
                 }
@@ -545,7 +507,7 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
 #pragma unroll
                     for (int t = 0; t < nd; ++t) R[d0 + t] *= inv;
                 });
-                pq_weighted_gp<ALG>(s[mv], z[mv], R, wb + c * P);
+                lane_weighted_gp<ALG>(s[mv], z[mv], R, wb + c * P);
                 float qs = 0.f;
                 static_for<0, 8>([&](auto dd) {
                     constexpr int d = decltype(dd)::value;
@@ -586,7 +548,7 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
 #pragma unroll
                 for (int i = 0; i < NPRE; ++i) {
                     const int rr = pq_row_of(tid, i), e = tid & 63;
-                    if (row0 + rr < io.rows) pg_st4(io.agg + (size_t)(row0 + rr) * ROW + 4 * e, pg_ld4(bufA + pq_off(e >> 1, rr, e & 1)));
+                    if (row0 + rr < io.rows) st4(io.agg + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufA + pq_off(e >> 1, rr, e & 1)));
                 }
             } else {
                 // one atomic per 256 bytes of a target row; equal consecutive targets (the rows are sorted by target) are summed first
@@ -616,9 +578,9 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
             for (int i = 0; i < NPRE; ++i) {
                 const int rr = pq_row_of(tid, i), e = tid & 63;
                 if (row0 + rr < io.rows) {
-                    f4 v = pg_ld4(bufA + pq_off(e >> 1, rr, e & 1));
-                    if (io.resid) v += pg_ld4(io.resid + (size_t)(row0 + rr) * ROW + 4 * e);
-                    pg_st4(io.y + (size_t)(row0 + rr) * ROW + 4 * e, v);
+                    f4 v = ld4(bufA + pq_off(e >> 1, rr, e & 1));
+                    if (io.resid) v += ld4(io.resid + (size_t)(row0 + rr) * ROW + 4 * e);
+                    st4(io.y + (size_t)(row0 + rr) * ROW + 4 * e, v);
                 }
             }
         }
@@ -639,81 +601,7 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
 // Weight gradients: contraction over the 16 rows, wave w owns tile (ot = w >> 1, ct = w & 1) of every 32 x 32 matrix, all
 // grades (16 accumulator registers per matrix, persistent over the launch); the attribute chunk (one c-tile): wave w owns
 // (ot = w >> 1, piece w & 1). Per-channel parameter gradients: summed over the 16 rows by the transposing butterfly
-// (pg_rows_sum: a DPP row = the 16 rows of one channel), 3 registers per lane and channel.
-
-struct PqCollect {
-    float buf[16];
-    template <int IDX>
-    CSMPN_DEV void add(float v, float (&small)[3], int l16) {
-        buf[IDX % 16] = v;
-        if constexpr (IDX % 16 == 15) small[IDX / 16] += pg_rows_sum(buf, l16);
-    }
-};
-
-// geometric product backward, 8 blades in the lane, two passes (as pg_gp_bwd_z / _r)
-template <class ALG>
-CSMPN_DEV void pq_gp_bwd_z(const float (&ggp)[8], const float (&z)[8], const float (&rf)[8], float (&gz)[8], const float* wrow,
-                           PqCollect& col, float (&small)[3], int l16) {
-    constexpr int P = ALG::P;
-    static_for<0, P / 4>([&](auto qq) {
-        const f4 wv = pg_ld4(wrow + 4 * decltype(qq)::value);
-        static_for<0, 4>([&](auto pp) {
-            constexpr int p = 4 * decltype(qq)::value + decltype(pp)::value;
-            constexpr int gi = ALG::t.path_g[p][0], gj = ALG::t.path_g[p][1], gk = ALG::t.path_g[p][2];
-            constexpr int i0 = ALG::gstart(gi), ni = ALG::gsize(gi);
-            constexpr int j0 = ALG::gstart(gj), nj = ALG::gsize(gj);
-            constexpr int k0 = ALG::gstart(gk), nk = ALG::gsize(gk);
-            const float w = wv[decltype(pp)::value];
-            float U[ni];
-#pragma unroll
-            for (int t = 0; t < ni; ++t) U[t] = 0.f;
-            static_for<0, ni>([&](auto ii) {
-                static_for<0, nk>([&](auto kk) {
-                    constexpr int i = i0 + ii, k = k0 + kk;
-                    constexpr int j = ALG::t.out[i][k];
-                    if constexpr (j >= j0 && j < j0 + nj) {
-                        constexpr float sg = float(ALG::t.sign[i][k]);
-                        U[ii] = __builtin_fmaf(sg * ggp[j], rf[k], U[ii]);
-                    }
-                });
-            });
-            float gwv = 0.f;
-#pragma unroll
-            for (int t = 0; t < ni; ++t) { gz[i0 + t] = __builtin_fmaf(w, U[t], gz[i0 + t]); gwv = __builtin_fmaf(z[i0 + t], U[t], gwv); }
-            col.template add<p>(gwv, small, l16);
-        });
-    });
-}
-template <class ALG>
-CSMPN_DEV void pq_gp_bwd_r(const float (&ggp)[8], const float (&z)[8], float (&gr)[8], const float* wrow) {
-    constexpr int P = ALG::P;
-    static_for<0, P / 4>([&](auto qq) {
-        const f4 wv = pg_ld4(wrow + 4 * decltype(qq)::value);
-        static_for<0, 4>([&](auto pp) {
-            constexpr int p = 4 * decltype(qq)::value + decltype(pp)::value;
-            constexpr int gi = ALG::t.path_g[p][0], gj = ALG::t.path_g[p][1], gk = ALG::t.path_g[p][2];
-            constexpr int i0 = ALG::gstart(gi), ni = ALG::gsize(gi);
-            constexpr int j0 = ALG::gstart(gj), nj = ALG::gsize(gj);
-            constexpr int k0 = ALG::gstart(gk), nk = ALG::gsize(gk);
-            const float w = wv[decltype(pp)::value];
-            float V[nk];
-#pragma unroll
-            for (int t = 0; t < nk; ++t) V[t] = 0.f;
-            static_for<0, ni>([&](auto ii) {
-                static_for<0, nk>([&](auto kk) {
-                    constexpr int i = i0 + ii, k = k0 + kk;
-                    constexpr int j = ALG::t.out[i][k];
-                    if constexpr (j >= j0 && j < j0 + nj) {
-                        constexpr float sg = float(ALG::t.sign[i][k]);
-                        V[kk] = __builtin_fmaf(sg * ggp[j], z[i], V[kk]);
-                    }
-                });
-            });
-#pragma unroll
-            for (int t = 0; t < nk; ++t) gr[k0 + t] = __builtin_fmaf(w, V[t], gr[k0 + t]);
-        });
-    });
-}
+// (rows16_sum: a DPP row = the 16 rows of one channel), 3 registers per lane and channel.
 
 // d/dW tile (ot, ct) += G^T X over the 16 rows, piece PIECE: acc[grade]. G: gradient tile (its channel slots are the rows of the
 // matrix), X: operand tile, both in LDS, lane = (channel i, rows 4 s + k).
@@ -723,8 +611,8 @@ CSMPN_DEV void pq_wgrad_piece(f4 (&acc)[4], const float* bufG, const float* bufX
     f4 a[4], b[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        a[s] = pg_ld4(bufG + pq_off(16 * ot + i, 4 * s + k, PIECE));
-        b[s] = pg_ld4(bufX + pq_off(16 * ct + (i & xmask), 4 * s + k, PIECE));
+        a[s] = ld4(bufG + pq_off(16 * ot + i, 4 * s + k, PIECE));
+        b[s] = ld4(bufX + pq_off(16 * ct + (i & xmask), 4 * s + k, PIECE));
     }
     static_for<0, 4>([&](auto bb) {
         constexpr int d = 4 * PIECE + decltype(bb)::value;
@@ -748,11 +636,11 @@ template <int NCT>
 CSMPN_DEV void pq_store_unit(float* base, const f4 (&acc)[4], int ot, int ct, int lane, int g0, int ng) {
 #pragma unroll
     for (int g = 0; g < 4; ++g)
-        if (g >= g0 && g < g0 + ng) pg_st4(base + (((g * 2 + ot) * NCT + ct) * 64 + lane) * 4, acc[g]);
+        if (g >= g0 && g < g0 + ng) st4(base + (((g * 2 + ot) * NCT + ct) * 64 + lane) * 4, acc[g]);
 }
 
 #define PQ_PHASE_IDS()                                                                                              \
-    const int tid = pg_tid();                                                                                       \
+    const int tid = fenced_tid();                                                                                   \
     const int wave = tid >> 6, lane = tid & 63, r = tid & 15, cq = tid >> 4, l16 = tid & 15;                        \
     const int mp = wave & 1, mot = wave >> 1;                                                                       \
     const bool live = row0 + r < io.rows;                                                                           \
@@ -833,12 +721,7 @@ struct PqAux {
 #endif
 template <class ALG, class CF, int K>
 __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(const DevCemlp C_arg, const RowIO io_arg, const PqAux aux) {
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& Cd = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(Cd);
     // (the summing workgroups come FIRST in the grid: dispatched in index order, they start with the launch)
     const int nred = (int)gridDim.x - aux.groups;
     if constexpr (K == 0) {
@@ -907,7 +790,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
     };
     // plain program: input chunk m of row `row` (pieces 64 m .. 64 m + 63 of the I0-channel row; zero beyond it)
     auto plain_piece = [&](long row, int m, int e) {
-        return 64 * m + e < 2 * I0 ? pg_ld4(io.seg[0].a + (size_t)row * (I0 * D) + 256 * m + 4 * e) : f4{0.f, 0.f, 0.f, 0.f};
+        return 64 * m + e < 2 * I0 ? ld4(io.seg[0].a + (size_t)row * (I0 * D) + 256 * m + 4 * e) : f4{0.f, 0.f, 0.f, 0.f};
     };
     f4 pre[NPRE];
     auto issue_gout = [&](const int* idx, long tile_, int t) {
@@ -923,9 +806,9 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
             if (ia[i] >= 0) {
                 if constexpr (LAST) {
                     const size_t grow = MODE == MODE_EDGE ? (size_t)ia[i] : (size_t)(tile_ * kPqRows + rr);
-                    pre[i] = pg_ld4(io.gy + grow * ROW + 4 * e);
+                    pre[i] = ld4(io.gy + grow * ROW + 4 * e);
                 } else {
-                    pre[i] = pg_ld4(io.plw_g1 + (size_t)(tile_ * kPqRows + rr) * ROW + 4 * e);
+                    pre[i] = ld4(io.plw_g1 + (size_t)(tile_ * kPqRows + rr) * ROW + 4 * e);
                 }
             }
         }
@@ -954,7 +837,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
 #pragma unroll
             for (int i = 0; i < NPRE; ++i) {
                 const int rr = pq_row_of(tid, i), e = tid & 63;
-                pg_st4(bufA + pq_off(e >> 1, rr, e & 1), pre[i]);
+                st4(bufA + pq_off(e >> 1, rr, e & 1), pre[i]);
             }
             if (tid < kPqRows) load_idx(sidx_n, tile + ngroups, tid);
         }
@@ -1054,7 +937,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
         stamp(3);
         // ---- ROW: geometric product + normalisation backward -> gR -> B; gz stays in registers
         float gz[2][8];
-        PqCollect col;      // one buffer: a multivector's slots are flushed (16 at a time) before the next one starts
+        RowsCollect<3> col;      // one buffer: a multivector's slots are flushed (16 at a time) before the next one starts
         {
             PQ_PHASE_IDS();
             // (fragments loaded at their MIX phase: the prefetch cost registers at three waves per SIMD and bought nothing)
@@ -1083,11 +966,11 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
                     for (int t = 0; t < nd; ++t) R[d0 + t] *= invden[g];    // R holds r = R / den from here on
                 });
                 float (&rf)[8] = R;
-                pq_gp_bwd_z<ALG>(ggp[mv], z, rf, gz[mv], wrow, col, small[mv], l16);
+                lane_gp_bwd_z<ALG>(ggp[mv], z, rf, gz[mv], wrow, col, small[mv], l16);
                 float gr[8];
 #pragma unroll
                 for (int d = 0; d < 8; ++d) gr[d] = 0.f;
-                pq_gp_bwd_r<ALG>(ggp[mv], z, gr, wrow);
+                lane_gp_bwd_r<ALG>(ggp[mv], z, gr, wrow);
                 // NormalizationLayer backward: gR (into gr), d/d(an)
                 static_for<0, G>([&](auto g) {
                     constexpr int d0 = ALG::gstart(g), nd = ALG::gsize(g);
@@ -1157,12 +1040,12 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
                 xa[i] = f4{0.f, 0.f, 0.f, 0.f};
                 if constexpr (K == 0 && MODE == MODE_EDGE) xb[i] = f4{0.f, 0.f, 0.f, 0.f};
                 if (ia[i] >= 0) {
-                    if constexpr (K == 1) xa[i] = pg_ld4(io.saved + (size_t)(row0 + rr) * ROW + 4 * e);
+                    if constexpr (K == 1) xa[i] = ld4(io.saved + (size_t)(row0 + rr) * ROW + 4 * e);
                     else if constexpr (MODE == MODE_EDGE) {
-                        xa[i] = pg_ld4(io.seg[0].a + (size_t)ia[i] * ROW + 4 * e);
-                        xb[i] = pg_ld4(io.seg[0].b + (size_t)ib[i] * ROW + 4 * e);
+                        xa[i] = ld4(io.seg[0].a + (size_t)ia[i] * ROW + 4 * e);
+                        xb[i] = ld4(io.seg[0].b + (size_t)ib[i] * ROW + 4 * e);
                     } else if constexpr (PLAIN) xa[i] = plain_piece(row0 + rr, 0, e);
-                    else xa[i] = pg_ld4(io.seg[0].a + (size_t)(row0 + rr) * ROW + 4 * e);
+                    else xa[i] = ld4(io.seg[0].a + (size_t)(row0 + rr) * ROW + 4 * e);
                 }
             }
             if constexpr (K == 0 && !PLAIN) {
@@ -1171,10 +1054,10 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
                 const int rr = tid / PPA, e = tid % PPA;
                 f4 v = f4{0.f, 0.f, 0.f, 0.f};
                 if (sidx[rr] >= 0 && e < NA * 2) {
-                    if constexpr (MODE == MODE_EDGE) v = pg_ld4(io.seg[1].a + (size_t)sidx[32 + rr] * (NA * D) + 4 * e);
-                    else v = pg_ld4(io.seg[2].a + (size_t)(row0 + rr) * (NA * D) + 4 * e);
+                    if constexpr (MODE == MODE_EDGE) v = ld4(io.seg[1].a + (size_t)sidx[32 + rr] * (NA * D) + 4 * e);
+                    else v = ld4(io.seg[2].a + (size_t)(row0 + rr) * (NA * D) + 4 * e);
                 }
-                pg_st4(bufE + pq_off(e >> 1, rr, e & 1), v);
+                st4(bufE + pq_off(e >> 1, rr, e & 1), v);
             }
         }
         // ---- ROW: MVSiLU backward -> gy -> B
@@ -1227,7 +1110,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
             for (int i = 0; i < NPRE; ++i) {
                 const int rr = pq_row_of(tid, i), e = tid & 63;
                 if constexpr (K == 0 && MODE == MODE_EDGE) xa[i] -= xb[i];
-                pg_st4(bufA + pq_off(e >> 1, rr, e & 1), xa[i]);
+                st4(bufA + pq_off(e >> 1, rr, e & 1), xa[i]);
             }
         }
         __syncthreads();
@@ -1284,7 +1167,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
                     for (int i = 0; i < NPRE; ++i) {
                         const int rr = pq_row_of(tid, i), e = tid & 63;
                         if (row0 + rr < io.rows && 64 * m + e < 2 * I0)
-                            pg_st4(io.gx[0] + (size_t)(row0 + rr) * (I0 * D) + 256 * m + 4 * e, pg_ld4(bufA + pq_off(e >> 1, rr, e & 1)));
+                            st4(io.gx[0] + (size_t)(row0 + rr) * (I0 * D) + 256 * m + 4 * e, ld4(bufA + pq_off(e >> 1, rr, e & 1)));
                     }
                     if constexpr (m + 1 < NCH0) __syncthreads();
                 }
@@ -1292,7 +1175,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
 #pragma unroll
                     for (int i = 0; i < NPRE; ++i) {
                         const int rr = pq_row_of(tid, i), e = tid & 63;
-                        pg_st4(bufA + pq_off(e >> 1, rr, e & 1), nxt[i]);
+                        st4(bufA + pq_off(e >> 1, rr, e & 1), nxt[i]);
                     }
                     __syncthreads();
                 }
@@ -1317,8 +1200,8 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
             for (int i = 0; i < NPRE; ++i) {
                 const int rr = pq_row_of(tid, i), e = tid & 63;
                 f4 v = f4{0.f, 0.f, 0.f, 0.f};
-                if (pq_sidx(sidx, rr) >= 0) v = pg_ld4(io.seg[1].a + (size_t)(row0 + rr) * ROW + 4 * e) * sscale[rr];
-                pg_st4(bufA + pq_off(e >> 1, rr, e & 1), v);
+                if (pq_sidx(sidx, rr) >= 0) v = ld4(io.seg[1].a + (size_t)(row0 + rr) * ROW + 4 * e) * sscale[rr];
+                st4(bufA + pq_off(e >> 1, rr, e & 1), v);
             }
             __syncthreads();
             pq_zero(accg);
@@ -1339,7 +1222,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
 #pragma unroll
                 for (int i = 0; i < NPRE; ++i) {
                     const int rr = pq_row_of(tid, i), e = tid & 63;
-                    if (row0 + rr < io.rows) pg_st4(io.plw_g1 + (size_t)(row0 + rr) * ROW + 4 * e, pg_ld4(bufB + pq_off(e >> 1, rr, e & 1)));
+                    if (row0 + rr < io.rows) st4(io.plw_g1 + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pq_off(e >> 1, rr, e & 1)));
                 }
             } else if constexpr (PLAIN) {
                 // (every chunk's d/dx rows left in the MIX phase above)
@@ -1349,7 +1232,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
 #pragma unroll
                         for (int i = 0; i < NPRE; ++i) {
                             const int rr = pq_row_of(tid, i), e = tid & 63;
-                            if (row0 + rr < io.rows) pg_st4(io.gx[0] + (size_t)(row0 + rr) * ROW + 4 * e, pg_ld4(bufB + pq_off(e >> 1, rr, e & 1)));
+                            if (row0 + rr < io.rows) st4(io.gx[0] + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pq_off(e >> 1, rr, e & 1)));
                         }
                     } else {
                         static_assert(ROW == kPqThreads, "one column per thread");
@@ -1379,7 +1262,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
                 if (io.gx[1]) {
                     const int rr = tid / (NA * 2), e = tid % (NA * 2);
                     if (tid < kPqRows * NA * 2 && row0 + rr < io.rows)
-                        pg_st4(io.gx[1] + (size_t)sidx[32 + rr] * (NA * D) + 4 * e, pg_ld4(bufE + pq_off(e >> 1, rr, e & 1)));
+                        st4(io.gx[1] + (size_t)sidx[32 + rr] * (NA * D) + 4 * e, ld4(bufE + pq_off(e >> 1, rr, e & 1)));
                 }
             } else {
 #pragma unroll
@@ -1387,17 +1270,17 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
                     const int rr = pq_row_of(tid, i), e = tid & 63;
                     if (row0 + rr < io.rows) {
                         if (io.gx[0]) {
-                            f4 v = pg_ld4(bufA + pq_off(e >> 1, rr, e & 1));
-                            if (io.resid_bwd) v += pg_ld4(io.gy + (size_t)(row0 + rr) * ROW + 4 * e);
-                            pg_st4(io.gx[0] + (size_t)(row0 + rr) * ROW + 4 * e, v);
+                            f4 v = ld4(bufA + pq_off(e >> 1, rr, e & 1));
+                            if (io.resid_bwd) v += ld4(io.gy + (size_t)(row0 + rr) * ROW + 4 * e);
+                            st4(io.gx[0] + (size_t)(row0 + rr) * ROW + 4 * e, v);
                         }
-                        if (io.gx[1]) pg_st4(io.gx[1] + (size_t)(row0 + rr) * ROW + 4 * e, pg_ld4(bufB + pq_off(e >> 1, rr, e & 1)) * sscale[rr]);
+                        if (io.gx[1]) st4(io.gx[1] + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pq_off(e >> 1, rr, e & 1)) * sscale[rr]);
                     }
                 }
                 if (io.gx[2]) {
                     const int rr = tid / (NA * 2), e = tid % (NA * 2);
                     if (tid < kPqRows * NA * 2 && row0 + rr < io.rows)
-                        pg_st4(io.gx[2] + (size_t)(row0 + rr) * (NA * D) + 4 * e, pg_ld4(bufE + pq_off(e >> 1, rr, e & 1)));
+                        st4(io.gx[2] + (size_t)(row0 + rr) * (NA * D) + 4 * e, ld4(bufE + pq_off(e >> 1, rr, e & 1)));
                 }
             }
         }

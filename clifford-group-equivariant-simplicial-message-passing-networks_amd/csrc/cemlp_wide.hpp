@@ -358,12 +358,7 @@ CSMPN_DEV void wide_block_backward(const DevBlock& B, const float* xin, const fl
 template <class ALG, int MODE, bool BWD>
 __global__ void __launch_bounds__(BWD ? 256 : 512) cemlp_wide_kernel(const DevCemlp C_arg, const RowIO io_arg) {
     // descriptors read in place from the kernarg segment (see cemlp_kernel)
-    typedef const char __attribute__((address_space(4))) * KArgPtr;
-    const KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr size_t kIoOffset = (sizeof(DevCemlp) + alignof(RowIO) - 1) / alignof(RowIO) * alignof(RowIO);
-    const DevCemlp& C = *(const DevCemlp*)(const char*)ka;
-    const RowIO& io = *(const RowIO*)(const char*)(ka + kIoOffset);
-    (void)C_arg; (void)io_arg;
+    CSMPN_KERNEL_ARGS(C);
     using GE = Geo<ALG, 1>;
     constexpr int D = ALG::D, R = GE::R, NW = GE::NW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
