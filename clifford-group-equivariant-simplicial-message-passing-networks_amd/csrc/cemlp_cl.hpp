@@ -27,7 +27,10 @@
 //  * the backward is ONE launch for all blocks, run block by block (last block first): 48-80 accumulator registers +
 //    35 running sums are alive per block instead of both blocks' at once; d/d(block input) rows travel through a
 //    [rows, C, D] region behind the saved block inputs (through L2: a wave reads in block k - 1 what it wrote itself
-//    in block k) or, with one tile per wave, stay in registers. Every workgroup writes one slice of partial sums per
+//    in block k) or, with one tile per wave, stay in registers. One tile per wave (S1's node launch) is an instantiation
+//    of its own inside the kernel (cl_bwd_blocks<..., SINGLE>): what it pays is latency, so every global read of the
+//    launch - tables of both blocks, tile indices, the last block's rows - is requested before the first wait, block 0's
+//    rows travel during block 1's end phase and no store is waited for. Every workgroup writes one slice of partial sums per
 //    block; cl_reduce_kernel adds the slices of all blocks in a fixed order (no atomics on parameters: bit-reproducible).
 //  * gathers: a lane loads its own 32 bytes of a row (2 x 16 bytes); scatters go through a per-wave LDS tile so that
 //    one atomic instruction covers whole 256-byte rows, equal consecutive targets summed first.
@@ -217,84 +220,98 @@ CSMPN_DEV float cl_smooth_abs_sqrt(float q) { return sqrt_pos(sqrt_pos(__builtin
 // ---------------------------------------------------------------------------------
 // parameters -> LDS tables of one block (once per workgroup). dir = +1 / -1: the lane `row_ror:ROTL` reads from holds
 // channel c + dir (probed on the device).
+// Two steps - load: every global read of the block requested; store: into LDS - so that a kernel requests the tables of all
+// its blocks before it waits for the first (one global round trip per launch instead of one per block).
 template <class ALG, int C, class TB, bool BWD>
-__device__ void cl_stage_block(const DevBlock& B, float* base, int tid, int dir) {
-    constexpr int G = ALG::G, P = ALG::P, NE = TB::n_entries, NIT = (NE + 64 * kClWaves - 1) / (64 * kClWaves);
+struct ClStage {
+    static constexpr int G = ALG::G, P = ALG::P, NE = TB::n_entries, NIT = (NE + 64 * kClWaves - 1) / (64 * kClWaves);
+    static constexpr int NPAR = C * kClParStride, NITP = (NPAR + 64 * kClWaves - 1) / (64 * kClWaves);
     static_assert(G == 4, "the weight of one (o, c) pair is one 16-byte vector of 4 grades");
-    const float *pW1 = B.W1, *pWR = B.WR, *pWL = B.WL;
-    const float* src[NIT];
+    static_assert(16 + P <= kClParStride, "parameter stride");
+    f4 v[NIT];
+    float pv[NITP];
+    bool live[NIT], plive[NITP], sig[NITP];
+    __device__ void load(const DevBlock& B, int tid, int dir) {
+        const float *pW1 = B.W1, *pWR = B.WR, *pWL = B.WL;
+        const float* src[NIT];
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int e = tid + it * 64 * kClWaves;   // f4 entry
-        src[it] = nullptr;
-        // forward tables: entry (k, o) = W[o][first channel + ((o + dir k) mod period)]
-        static_for<0, TB::NP>([&](auto p) {
-            constexpr int e0 = TB::W1(p) / 4, PER = TB::period(p), n = PER * C;
-            if (e >= e0 && e < e0 + n) {
-                const int k = (e - e0) / C, o = (e - e0) % C, cs = (o + dir * k) & (PER - 1);
-                if (cs < TB::width(p)) src[it] = pW1 + ((o * TB::I + TB::coff(p) + cs) * G);
-            }
-        });
-        if (e >= TB::WR / 4 && e < TB::fwd_end / 4) {
-            const int f = e - TB::WR / 4, which = f / (C * C), k = (f % (C * C)) / C, o = f % C, cs = (o + dir * k) & (C - 1);
-            src[it] = (which == 0 ? pWR : pWL) + ((o * C + cs) * G);
-        }
-        if constexpr (BWD) {
-            // transposed tables: entry (k, c) = W[(c + dir k) mod C][first channel + (c mod period)]
+        for (int it = 0; it < NIT; ++it) {
+            const int e = tid + it * 64 * kClWaves;   // f4 entry
+            src[it] = nullptr;
+            // forward tables: entry (k, o) = W[o][first channel + ((o + dir k) mod period)]
             static_for<0, TB::NP>([&](auto p) {
-                constexpr int e0 = TB::W1T(p) / 4, PER = TB::period(p);
-                if (e >= e0 && e < e0 + C * C) {
-                    const int k = (e - e0) / C, c = (e - e0) % C, o = (c + dir * k) & (C - 1), cs = c & (PER - 1);
+                constexpr int e0 = TB::W1(p) / 4, PER = TB::period(p), n = PER * C;
+                if (e >= e0 && e < e0 + n) {
+                    const int k = (e - e0) / C, o = (e - e0) % C, cs = (o + dir * k) & (PER - 1);
                     if (cs < TB::width(p)) src[it] = pW1 + ((o * TB::I + TB::coff(p) + cs) * G);
                 }
             });
-            if (e >= TB::WRT / 4 && e < TB::par / 4) {
-                const int f = e - TB::WRT / 4, which = f / (C * C), k = (f % (C * C)) / C, c = f % C, o = (c + dir * k) & (C - 1);
-                src[it] = (which == 0 ? pWR : pWL) + ((o * C + c) * G);
+            if (e >= TB::WR / 4 && e < TB::fwd_end / 4) {
+                const int f = e - TB::WR / 4, which = f / (C * C), k = (f % (C * C)) / C, o = f % C, cs = (o + dir * k) & (C - 1);
+                src[it] = (which == 0 ? pWR : pWL) + ((o * C + cs) * G);
+            }
+            if constexpr (BWD) {
+                // transposed tables: entry (k, c) = W[(c + dir k) mod C][first channel + (c mod period)]
+                static_for<0, TB::NP>([&](auto p) {
+                    constexpr int e0 = TB::W1T(p) / 4, PER = TB::period(p);
+                    if (e >= e0 && e < e0 + C * C) {
+                        const int k = (e - e0) / C, c = (e - e0) % C, o = (c + dir * k) & (C - 1), cs = c & (PER - 1);
+                        if (cs < TB::width(p)) src[it] = pW1 + ((o * TB::I + TB::coff(p) + cs) * G);
+                    }
+                });
+                if (e >= TB::WRT / 4 && e < TB::par / 4) {
+                    const int f = e - TB::WRT / 4, which = f / (C * C), k = (f % (C * C)) / C, c = f % C, o = (c + dir * k) & (C - 1);
+                    src[it] = (which == 0 ? pWR : pWL) + ((o * C + c) * G);
+                }
             }
         }
-    }
-    f4 v[NIT];
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) v[it] = src[it] ? ld4(src[it]) : f4{0.f, 0.f, 0.f, 0.f};
-    // per-channel parameters: [b1, bL, la, 0 | sa[4] | sb[4] | sigmoid(an)[4] | w[P]] per channel
-    constexpr int NPAR = C * kClParStride, NITP = (NPAR + 64 * kClWaves - 1) / (64 * kClWaves);
-    static_assert(16 + P <= kClParStride, "parameter stride");
-    const float *pb1 = B.b1, *pbL = B.bL, *pla = B.la, *psa = B.sa, *psb = B.sb, *pan = B.an, *pw = B.w;
-    const bool has_b1 = B.has_b1 != 0;
-    const float* ps[NITP];
-    bool sig[NITP];
+        for (int it = 0; it < NIT; ++it) {
+            // every thread loads (an entry without a source: the first weight, replaced by zero in `store`): a load under a
+            // branch is waited for inside the branch, one round trip per entry
+            live[it] = src[it] != nullptr;
+            v[it] = ld4(live[it] ? src[it] : pW1);
+        }
+        // per-channel parameters: [b1, bL, la, 0 | sa[4] | sb[4] | sigmoid(an)[4] | w[P]] per channel
+        const float *pb1 = B.b1, *pbL = B.bL, *pla = B.la, *psa = B.sa, *psb = B.sb, *pan = B.an, *pw = B.w;
+        const bool has_b1 = B.has_b1 != 0;
+        const float* ps[NITP];
 #pragma unroll
-    for (int it = 0; it < NITP; ++it) {
-        const int e = tid + it * 64 * kClWaves;
-        ps[it] = nullptr;
-        sig[it] = false;
-        if (e < NPAR) {
-            const int ch = e / kClParStride, s = e % kClParStride;
-            if (s == 0) { if (has_b1) ps[it] = pb1 + ch; }
-            else if (s == 1) ps[it] = pbL + ch;
-            else if (s == 2) ps[it] = pla + ch;
-            else if (s >= 4 && s < 8) ps[it] = psa + ch * G + (s - 4);
-            else if (s >= 8 && s < 12) ps[it] = psb + ch * G + (s - 8);
-            else if (s >= 12 && s < 16) { ps[it] = pan + ch * G + (s - 12); sig[it] = true; }
-            else if (s >= 16 && s < 16 + P) ps[it] = pw + ch * P + (s - 16);
+        for (int it = 0; it < NITP; ++it) {
+            const int e = tid + it * 64 * kClWaves;
+            ps[it] = nullptr;
+            sig[it] = false;
+            if (e < NPAR) {
+                const int ch = e / kClParStride, s = e % kClParStride;
+                if (s == 0) { if (has_b1) ps[it] = pb1 + ch; }
+                else if (s == 1) ps[it] = pbL + ch;
+                else if (s == 2) ps[it] = pla + ch;
+                else if (s >= 4 && s < 8) ps[it] = psa + ch * G + (s - 4);
+                else if (s >= 8 && s < 12) ps[it] = psb + ch * G + (s - 8);
+                else if (s >= 12 && s < 16) { ps[it] = pan + ch * G + (s - 12); sig[it] = true; }
+                else if (s >= 16 && s < 16 + P) ps[it] = pw + ch * P + (s - 16);
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < NITP; ++it) {
+            plive[it] = ps[it] != nullptr;
+            pv[it] = *(plive[it] ? ps[it] : pW1);
         }
     }
-    float pv[NITP];
+    __device__ void store(float* base, int tid) {
 #pragma unroll
-    for (int it = 0; it < NITP; ++it) pv[it] = ps[it] ? *ps[it] : 0.f;
+        for (int it = 0; it < NIT; ++it) {
+            const int e = tid + it * 64 * kClWaves;
+            if (e < NE) st4(base + 4 * e, live[it] ? v[it] : f4{0.f, 0.f, 0.f, 0.f});
+        }
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int e = tid + it * 64 * kClWaves;
-        if (e < NE) st4(base + 4 * e, v[it]);
+        for (int it = 0; it < NITP; ++it) {
+            const int e = tid + it * 64 * kClWaves;
+            if (sig[it]) pv[it] = sigmoidf(pv[it]);
+            if (e < NPAR) base[TB::par + e] = plive[it] ? pv[it] : 0.f;
+        }
     }
-#pragma unroll
-    for (int it = 0; it < NITP; ++it) {
-        const int e = tid + it * 64 * kClWaves;
-        if (sig[it]) pv[it] = sigmoidf(pv[it]);
-        if (e < NPAR) base[TB::par + e] = pv[it];
-    }
-}
+};
 
 // ---------------------------------------------------------------------------------
 // sign-table geometric product with per-path weights, one channel:
@@ -697,26 +714,31 @@ CSMPN_DEV void cl_scatter(const float* sc, int t_add, int t_sub, float* table, i
 
 // ---------------------------------------------------------------------------------
 // tile bookkeeping shared by the kernels
+__device__ const int kClNoDegree = 1;   // what a tile reads as its degree when the launch has none (sum aggregation)
 template <int C, int MODE>
 struct ClTile {
     long row, lrow;
     bool valid;
-    int i_dst, i_src, i_perm;
-    float scale;
+    int i_dst, i_src, i_perm, deg;
+    // mean aggregation. Worked out where it is used: taken at load time, the division waits out the degree's round trip in
+    // front of the row requests that follow the load
+    CSMPN_DEV float scale() const { return 1.0f / float(deg > 1 ? deg : 1); }
     template <int NA>
     CSMPN_DEV void load(const RowIO& io, long tile, int r) {
         row = tile * ClMap<C>::RPW + r;
         valid = row < io.rows;
         lrow = valid ? row : 0;   // lanes past the end compute on row 0 and contribute nothing
         i_dst = i_src = i_perm = 0;
-        scale = 1.0f;
+        deg = 1;
         if constexpr (MODE == MODE_EDGE) {
             i_dst = io.seg[0].ia[lrow];
             i_src = io.seg[0].ib[lrow];
             if constexpr (NA > 0) i_perm = io.seg[1].ia[lrow];
         }
         if constexpr (MODE == MODE_NODE) {   // mean aggregation
-            if (io.seg[1].deg) { const int dg = io.seg[1].deg[lrow]; scale = 1.0f / float(dg > 1 ? dg : 1); }
+            // loaded without a branch (no degrees: the constant 1): a load under a branch is waited for at the end of
+            // the branch, in front of the row requests
+            deg = *(io.seg[1].deg ? io.seg[1].deg + lrow : &kClNoDegree);
         }
     }
 };
@@ -768,7 +790,8 @@ struct ClRaw {
             if constexpr (NA > 0) unpack(x[1], v[4], v[5]);
         } else {
             unpack(x[0], v[0], v[1]);
-            unpack(x[1], v[2] * T.scale, v[3] * T.scale);
+            const float sc_ = T.scale();
+            unpack(x[1], v[2] * sc_, v[3] * sc_);
             if constexpr (NA > 0) unpack(x[2], v[4], v[5]);
         }
     }
@@ -818,14 +841,27 @@ __global__ void __launch_bounds__(64 * kClWaves, 4) cemlp_cl_fwd_kernel(const De
     // the first tile's rows travel while the tables are staged
     {
         const int dir = cl_probe_dir<C>(c);
-        cl_stage_block<ALG, C, T0, false>(Cd.b[0], lds, threadIdx.x, dir);
-        if constexpr (NBLK > 1) cl_stage_block<ALG, C, T1, false>(Cd.b[1], lds + T0::total, threadIdx.x, dir);
+        ClStage<ALG, C, T0, false> st0;
+        ClStage<ALG, C, T1, false> st1;
+        st0.load(Cd.b[0], threadIdx.x, dir);
+        if constexpr (NBLK > 1) st1.load(Cd.b[1], threadIdx.x, dir);
+        st0.store(lds, threadIdx.x);
+        if constexpr (NBLK > 1) st1.store(lds + T0::total, threadIdx.x);
     }
     __syncthreads();
     stamp(0);
     for (long tile = tile0; tile < ntiles; tile += tstride) {
         raw.pin();
         stamp(1);
+        // the residual row is requested here (most likely a cache hit: the node program has just read it as its first
+        // segment) and not where it is added, at the end of the tile with nothing left to hide its round trip
+        f4 res0, res1;
+        if constexpr (MODE == MODE_NODE) {
+            if (io.resid) {
+                const float* pr_ = io.resid + (size_t)T.lrow * ROW + c * D;
+                res0 = ld4(pr_); res1 = ld4(pr_ + 4);
+            }
+        }
         float out[D], in1[D];
         {
             float x[T0::NP][D];
@@ -876,8 +912,7 @@ __global__ void __launch_bounds__(64 * kClWaves, 4) cemlp_cl_fwd_kernel(const De
             }
         } else if (Tc.valid) {
             if (io.resid) {
-                float res[D];
-                cl_ld8(res, io.resid + (size_t)Tc.row * ROW + c * D);
+                const float res[D] = {res0.x, res0.y, res0.z, res0.w, res1.x, res1.y, res1.z, res1.w};
 #pragma unroll
                 for (int d = 0; d < D; ++d) out[d] += res[d];
             }
@@ -898,8 +933,49 @@ constexpr size_t cl_fwd_lds_bytes() {
 // gathers it by target) or from the hand-over rows io.plw_g1; d/d(input of block K) goes to the hand-over rows (K > 0)
 // or to the program's gradient targets (K = 0). Block K > 0 reads its input from the saved rows.
 struct ClCarry { f4 a, b; };
-template <class ALG, int C, int MODE, int NBLK, int NA, int K, bool SAVES>
-CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const ClCarry carry_in, bool single, ClStamp& stamp) {
+// What the first tile of a block reads from global memory, requested BEFORE the block starts: the last block's ahead of the
+// table staging (as the forward does), block 0's - with one tile per wave - ahead of the end phase of the block in front
+// of it. With one tile per wave every global round trip is exposed once per launch; here they travel behind work that
+// is there anyway. d/d(out) of a block that is not the last is the caller's (hand-over rows or registers).
+template <class ALG, int C, int MODE, int NBLK, int NA, bool SAVES>
+struct ClBwdReq {
+    f4 g0, g1, s0, s1, t0, t1;
+    ClRaw<ALG, C, MODE, NA> raw;
+    template <int K>
+    CSMPN_DEV void request(const RowIO& io, const ClTile<C, MODE>& Tl, int c) {
+        constexpr int D = ALG::D, ROW = C * D;
+        if constexpr (K == NBLK - 1) {
+            const float* gsrc = io.gy + (size_t)(MODE == MODE_EDGE ? (long)Tl.i_dst : Tl.lrow) * ROW + c * D;
+            g0 = ld4(gsrc); g1 = ld4(gsrc + 4);
+        }
+        if constexpr (K == 0) {
+            raw.template issue<ClTab<C, MODE, NA, 0, true>>(io, Tl, c);
+        } else {
+            const float* sp = io.saved + (size_t)Tl.lrow * ROW + c * D;
+            s0 = ld4(sp); s1 = ld4(sp + 4);
+        }
+        if constexpr (SAVES) {   // the block's saved state (row 0's for a wave without a tile: never used)
+            const float* ps_ = io.saved + state_region<ROW, ROW>(io.rows, 0, K) + cl_state_off<C>(Tl.lrow, c);
+            t0 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ps_));
+            t1 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ps_ + 256));
+        }
+    }
+    // block 0's requests have arrived (placed in front of stores whose acknowledgement nobody has to wait for: vmcnt counts
+    // in issue order, a later wait for these rows would wait for those stores too)
+    CSMPN_DEV void arrived0() {
+        raw.pin();
+        if constexpr (SAVES) asm volatile("" : "+v"(t0), "+v"(t1));
+    }
+};
+// SINGLE: one tile per wave (uniform over the grid; an instantiation of its own inside the kernel: no tile loop, no next
+// tile, and the waits the compiler places are exact instead of the loop's vmcnt(0)). T0: the wave's first tile (loaded once
+// per launch). cur: the block's row registers; they hold the requests of T0 already for the last block and, when SINGLE,
+// for every block. next: when SINGLE, receives the requests of T0 for block K - 1.
+template <class ALG, int C, int MODE, int NBLK, int NA, int K, bool SAVES, bool SINGLE>
+CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const ClTile<C, MODE>& T0,
+                               ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES>& cur,
+                               ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES>& next, const ClCarry carry_in, ClStamp& stamp) {
+    constexpr bool single = SINGLE, have_pre = SINGLE || K == NBLK - 1;
     f4 carry_a = carry_in.a, carry_b = carry_in.b;
     using MP = ClMap<C>;
     using TB = ClTab<C, MODE, NA, K, true>;
@@ -932,12 +1008,12 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
     const long ntiles = (io.rows + RPW - 1) / RPW;
     const long tstride = (long)gridDim.x * kClWaves;
     // Software pipeline as in the forward: the rows of tile t + 1 are requested in front of the stores / atomics of tile t.
-    f4 g0, g1, s0, s1;
-    ClRaw<ALG, C, MODE, NA> raw;
+    f4 &g0 = cur.g0, &g1 = cur.g1, &s0 = cur.s0, &s1 = cur.s1, &t0 = cur.t0, &t1 = cur.t1;
+    ClRaw<ALG, C, MODE, NA>& raw = cur.raw;
     auto issue = [&](const ClTile<C, MODE>& Tl) {
         const float* gsrc = (kLast ? io.gy + (size_t)(MODE == MODE_EDGE ? (long)Tl.i_dst : Tl.lrow) * ROW
                                    : io.plw_g1 + (size_t)Tl.lrow * ROW) + c * D;
-        if (kLast || !single) {
+        if constexpr (kLast || !single) {
             g0 = ld4(gsrc); g1 = ld4(gsrc + 4);
         } else {   // one tile per wave: d/d(out) of this block stayed in registers
             g0 = carry_a; g1 = carry_b;
@@ -950,10 +1026,14 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
         }
     };
     const long tile0 = (long)blockIdx.x * kClWaves + wave;
-    ClTile<C, MODE> T, Tn;
-    T.template load<NA>(io, tile0, r);
-    issue(T);
-    Tn.template load<NA>(io, tile0 + tstride, r);
+    ClTile<C, MODE> T = T0, Tn = T0;
+    if constexpr (have_pre) {
+        if constexpr (!kLast) { g0 = carry_a; g1 = carry_b; }
+    } else {
+        issue(T);
+    }
+    if constexpr (!single) Tn.template load<NA>(io, tile0 + tstride, r);
+    stamp(20);
     for (long tile = tile0; tile < ntiles; tile += tstride) {
         if constexpr (K == 0) {
             asm volatile("" : "+v"(g0), "+v"(g1));
@@ -981,16 +1061,28 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
             for (int d = 0; d < D; ++d) S.y[d] = 0.f;
             constexpr bool have_s = SAVES;   // compile time: a run-time switch between the two recomputes spills the node program
             if constexpr (have_s) {   // CSMPN_FLAG_SAVE_STATE: the block's output in front of the layer norm, saved by the forward
-                const float* ps_ = io.saved + state_region<ROW, ROW>(io.rows, 0, K) + cl_state_off<C>(Tc.lrow, c);
-                const f4 a_ = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ps_)), b_ = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ps_ + 256));
+                if (!have_pre || (!single && tile != tile0)) {
+                    const float* ps_ = io.saved + state_region<ROW, ROW>(io.rows, 0, K) + cl_state_off<C>(Tc.lrow, c);
+                    t0 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ps_));
+                    t1 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ps_ + 256));
+                }
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { S.s[i] = a_[i]; S.s[4 + i] = b_[i]; }
+                for (int i = 0; i < 4; ++i) { S.s[i] = t0[i]; S.s[4 + i] = t1[i]; }
             }
             static_for<0, NP>([&](auto p) { cl_mix<C, TB::period(p), TB::W1(p)>(S.y, x[p], ldsw); });
             stamp(2);
             float unused[D];
             cl_block_tail<ALG, C, TB, 4>(ldsw, ldsp, S, unused, stamp, 3, have_s);
             cl_block_backward<ALG, C, TB>(ldsw, ldsp, S, gout, gy, sm, accR, accL, stamp, 8);
+        }
+        // one tile per wave (registers to spare): the residual's gradient row travels behind the weight-gradient MFMAs and
+        // the transposed mix
+        f4 res0, res1;
+        if constexpr (K == 0 && MODE == MODE_NODE && single) {
+            if (io.gx[0] && io.resid_bwd) {
+                const float* pr_ = io.gy + (size_t)Tc.lrow * ROW + c * D;
+                res0 = ld4(pr_); res1 = ld4(pr_ + 4);
+            }
         }
         // MVLinear weight gradient: A = gy, B = the pass's input blade
 #ifndef CL_X_NOMFMA
@@ -1002,16 +1094,18 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
 #endif
         stamp(15);
         // next tile's rows, then this tile's stores / atomics
-        T = Tn;
-        issue(T);
-        Tn.template load<NA>(io, tile + 2 * tstride, r);
+        if constexpr (!single) {
+            T = Tn;
+            issue(T);
+            Tn.template load<NA>(io, tile + 2 * tstride, r);
+        }
         // d/d(input)
         if constexpr (K > 0) {
             float gx[D];
 #pragma unroll
             for (int d = 0; d < D; ++d) gx[d] = 0.f;
             cl_mix<C, C, TB::W1T(0)>(gx, gy, ldsw);
-            if (single) {
+            if constexpr (single) {
                 carry_a = f4{gx[0], gx[1], gx[2], gx[3]}; carry_b = f4{gx[4], gx[5], gx[6], gx[7]};
             } else if (Tc.valid) {
                 CL_GST8(io.plw_g1 + (size_t)Tc.row * ROW + c * D, sc + r * SS + c * D, gx);
@@ -1048,8 +1142,11 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
                 cl_mix<C, C, TB::W1T(0)>(gx, gy, ldsw);
                 if (Tc.valid) {
                     if (io.resid_bwd) {
-                        float res[D];
-                        cl_ld8(res, io.gy + (size_t)Tc.row * ROW + c * D);
+                        if constexpr (!single) {
+                            const float* pr_ = io.gy + (size_t)Tc.row * ROW + c * D;
+                            res0 = ld4(pr_); res1 = ld4(pr_ + 4);
+                        }
+                        const float res[D] = {res0.x, res0.y, res0.z, res0.w, res1.x, res1.y, res1.z, res1.w};
 #pragma unroll
                         for (int d = 0; d < D; ++d) gx[d] += res[d];
                     }
@@ -1062,7 +1159,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
                 for (int d = 0; d < D; ++d) gx[d] = 0.f;
                 cl_mix<C, C, TB::W1T(1)>(gx, gy, ldsw);
 #pragma unroll
-                for (int d = 0; d < D; ++d) gx[d] *= Tc.scale;
+                for (int d = 0; d < D; ++d) gx[d] *= Tc.scale();
                 if (Tc.valid) CL_GST8(io.gx[1] + (size_t)Tc.row * ROW + c * D, sc + r * SS + c * D, gx);
             }
             if constexpr (NA > 0) {
@@ -1076,7 +1173,10 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
             }
         }
         stamp(16);
+        if constexpr (single) break;
     }
+    // one tile per wave: block K - 1 works on the same tile; its rows travel during this block's end phase
+    if constexpr (K > 0 && single) next.template request<K - 1>(io, T0, c);
 
 #ifdef CL_X_NOEND   // timing experiment only (results wrong): the sums are kept alive, nothing else
     {
@@ -1134,7 +1234,10 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
             if constexpr (C == 8) s += dpp_mov<0xB1>(s);
             if (q == 0 && (C == 16 || (lane & 1) == 0)) img[PT::pS + PT::off(idx) + c * PT::stride(idx)] = s;
         });
+        stamp(21);
         __syncthreads();
+        stamp(22);
+        if constexpr (K == 1 && single) next.arrived0();
         // block k's slices start behind those of the blocks 0 .. k - 1 (kClSliceCap slices each)
         float* part = io.rl_partials + (K == 0 ? 0 : (size_t)kClSliceCap * ClPart<ALG, C, ClTab<C, MODE, NA, 0, true>::I>::total) +
                       (size_t)blockIdx.x * PT::total;
@@ -1160,6 +1263,32 @@ constexpr size_t cl_bwd_lds_bytes() {
     return sizeof(float) * (TB0::total + (NBLK > 1 ? TB1::total : 0) + kClWaves * (tile > img ? tile : img) +
                             ClSums<ClRed<ALG>::n>::floats_per_wg);
 }
+// the blocks of a backward launch, last block first
+template <class ALG, int C, int MODE, int NBLK, int NA, bool SAVES, bool SINGLE>
+CSMPN_DEV void cl_bwd_blocks(const RowIO& io, float* smem, const ClTile<C, MODE>& T0, ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES>& req,
+                             ClStamp& stamp) {
+    using TB0 = ClTab<C, MODE, NA, 0, true>;
+    using TB1 = ClTab<C, MODE, NA, 1, true>;
+    constexpr int tabs = TB0::total + (NBLK > 1 ? TB1::total : 0);
+    ClCarry carry{f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};
+    if constexpr (NBLK > 1) {
+        // req: block 1's row registers, filled by the kernel in front of the staging. req0: block 0's; block 1 fills them
+        // ahead of its end phase when SINGLE, else block 0 requests into them itself. Block 0 has no block behind it: the
+        // struct passed as its `next` is never written.
+        ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES> req0;
+        carry = cl_bwd_block<ALG, C, MODE, NBLK, NA, 1, SAVES, SINGLE>(io, smem + TB0::total, smem + tabs, T0, req, req0, carry, stamp);
+        // this wave's hand-over rows have left for L2. With one tile per wave there are none: the only stores in flight
+        // are the workgroup's block-1 slice, which nobody reads in this launch
+        if constexpr (!SINGLE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        stamp(18);
+        __syncthreads();                                   // ... and every wave is done with the images
+        stamp(19);
+        cl_bwd_block<ALG, C, MODE, NBLK, NA, 0, SAVES, SINGLE>(io, smem, smem + tabs, T0, req0, req, carry, stamp);
+    } else {
+        // one block: it is the last one, `req` holds its requests; `next` (the same struct) is never written
+        cl_bwd_block<ALG, C, MODE, NBLK, NA, 0, SAVES, SINGLE>(io, smem, smem + tabs, T0, req, req, carry, stamp);
+    }
+}
 // The backward kernel: the blocks one after the other (last block first) in ONE launch. A wave keeps its tiles from
 // block to block, so the hand-over rows d/d(block input) it reads in block k - 1 are the ones it wrote itself in block k
 // (through L2: the region is not read earlier in the launch, its lines cannot sit stale in this CU's L1; the stores are
@@ -1173,23 +1302,30 @@ __global__ void __launch_bounds__(64 * kClWaves, 2) cemlp_cl_bwd_kernel(const De
     using TB0 = ClTab<C, MODE, NA, 0, true>;
     using TB1 = ClTab<C, MODE, NA, 1, true>;
     constexpr int tabs = TB0::total + (NBLK > 1 ? TB1::total : 0);
+    // the wave's first tile: its indices once for all blocks, the last block's rows on their way while the tables are staged
+    ClTile<C, MODE> T0;
+    ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES> req;
+    {
+        const int lane = threadIdx.x & 63;
+        T0.template load<NA>(io, (long)blockIdx.x * kClWaves + (threadIdx.x >> 6), ClMap<C>::row(lane));
+        req.template request<NBLK - 1>(io, T0, ClMap<C>::chan(lane));
+    }
     // the tables of every block are staged up front (one prologue per launch)
     {
         const int dir = cl_probe_dir<C>(ClMap<C>::chan(threadIdx.x & 63));
-        cl_stage_block<ALG, C, TB0, true>(Cd.b[0], smem, threadIdx.x, dir);
-        if constexpr (NBLK > 1) cl_stage_block<ALG, C, TB1, true>(Cd.b[1], smem + TB0::total, threadIdx.x, dir);
+        ClStage<ALG, C, TB0, true> st0;
+        ClStage<ALG, C, TB1, true> st1;
+        st0.load(Cd.b[0], threadIdx.x, dir);
+        if constexpr (NBLK > 1) st1.load(Cd.b[1], threadIdx.x, dir);
+        st0.store(smem, threadIdx.x);
+        if constexpr (NBLK > 1) st1.store(smem + TB0::total, threadIdx.x);
     }
     __syncthreads();
     stamp(0);
     const long ntiles = (io.rows + ClMap<C>::RPW - 1) / ClMap<C>::RPW;
-    const bool single = ntiles <= (long)gridDim.x * kClWaves;   // one tile per wave: the hand-over stays in registers
-    ClCarry carry{f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};
-    if constexpr (NBLK > 1) {
-        carry = cl_bwd_block<ALG, C, MODE, NBLK, NA, 1, SAVES>(io, smem + TB0::total, smem + tabs, carry, single, stamp);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's hand-over rows have left for L2
-        __syncthreads();                                   // ... and every wave is done with the images
-    }
-    cl_bwd_block<ALG, C, MODE, NBLK, NA, 0, SAVES>(io, smem, smem + tabs, carry, single, stamp);
+    // one tile per wave (uniform over the grid): the hand-over stays in registers, every block's rows are requested ahead
+    if (ntiles <= (long)gridDim.x * kClWaves) cl_bwd_blocks<ALG, C, MODE, NBLK, NA, SAVES, true>(io, smem, T0, req, stamp);
+    else cl_bwd_blocks<ALG, C, MODE, NBLK, NA, SAVES, false>(io, smem, T0, req, stamp);
     stamp.flush(io.stamps, threadIdx.x & 63);
 }
 

@@ -4,7 +4,11 @@ forbid overlaps across phases. Backward stages: both block launches add into the
 import ctypes, importlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "clifford-group-equivariant-simplicial-message-passing-networks_amd"
-os.environ["CSMPN_LIB"] = os.path.join(ROOT, "tools", "_bin", "libcsmpn_hip_stamps.so")
+# CSMPN_STAMPS_LIB when set, else the `make -C <pkg>/csrc stamps` library when it is there, else the one
+# tools/cl_stamps_build.sh leaves
+_MADE = os.path.join(ROOT, PKG, "csmpn_hip", "libcsmpn_hip_stamps.so")
+os.environ["CSMPN_LIB"] = os.environ.get("CSMPN_STAMPS_LIB") or (
+    _MADE if os.path.exists(_MADE) else os.path.join(ROOT, "tools", "_bin", "libcsmpn_hip_stamps.so"))
 sys.path.insert(0, ROOT)
 import torch
 pkg = importlib.import_module(PKG)
@@ -15,7 +19,8 @@ FWD = ["setup(stage tables)", "loads(wait)", "W1 mix b0", "silu b0", "linR/L b0"
        "W1 mix b1", "silu b1", "linR/L b1", "norm b1", "gp b1", "layernorm b1", "store/scatter"]
 BWD = ["setup(stage tables)", "loads(wait)", "r:W1 mix", "r:silu", "r:linR/L", "r:norm", "r:gp", "r:layernorm",
        "b:layernorm", "b:linL^T", "b:gp", "b:norm", "b:linR^T", "b:wgradRL(mfma)", "b:silu", "b:wgradW1(mfma)",
-       "b:W1^T+store/scatter", "end-of-kernel sums"]
+       "b:W1^T+store/scatter", "end: image add + slice store", "between blocks: store drain", "between blocks: barrier",
+       "tile indices + row requests", "end: sums -> wave image", "end: barrier"]
 
 CM_FWD = ["setup(stage tables)", "loads(wait)", "W1 mix b0", "silu b0", "linR/L b0", "norm+gp b0", "layernorm b0", "", "W1 mix b1",
           "silu b1", "linR/L b1", "norm+gp b1", "layernorm b1", "", "issue next + store/scatter"]
