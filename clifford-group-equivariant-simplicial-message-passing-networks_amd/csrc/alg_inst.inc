@@ -2,34 +2,15 @@
 // CSMPN_ALG_N, CSMPN_ALG_NEG and CSMPN_ALG_TAG defined.
 #include "cemlp_kernel.hpp"
 #include "cemlp_ps.hpp"
-#include "launch.hpp"
-
-#include <atomic>
+#include "launch_unit.hpp"
 
 namespace csmpn {
 namespace {
-constexpr int kMaxDevices = 64;
 using ALG_T = Alg<CSMPN_ALG_N, CSMPN_ALG_NEG>;
 
 template <int MODE, int VAR, int H, bool BWD>
 hipError_t launch_one(unsigned grid, unsigned block, size_t lds, hipStream_t st, const DevCemlp& C, const RowIO& io) {
-    auto kern = cemlp_kernel<ALG_T, MODE, VAR, H, BWD>;
-    // dynamic LDS beyond 64 KB must be enabled per kernel; grow-only, and only as far as
-    // needed (a kernel may also own static LDS, e.g. compiler-promoted private arrays)
-    // (the attribute is per device: one slot per device ordinal, guarded for concurrent callers)
-    static std::atomic<size_t> lds_enabled[kMaxDevices];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-    size_t cur = lds_enabled[dev].load(std::memory_order_relaxed);
-    if (cur < 64 * 1024) cur = 64 * 1024;
-    if (lds > cur) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_enabled[dev].store(lds, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, st, C, io);
-    return hipGetLastError();
+    return launch_kernel<cemlp_kernel<ALG_T, MODE, VAR, H, BWD>>(grid, block, lds, st, C, io);
 }
 
 // H = 2 (32-row tiles for <= 8 channels) is instantiated for the small algebras only: with
@@ -49,6 +30,7 @@ hipError_t launch_mode(int var, int h, bool bwd, unsigned grid, unsigned block, 
                        : launch_one<MODE, VAR_WAVE, 1, false>(grid, block, lds, st, C, io);
         case VAR_GROUP: return bwd ? launch_one<MODE, VAR_GROUP, 1, true>(grid, block, lds, st, C, io)
                                    : launch_one<MODE, VAR_GROUP, 1, false>(grid, block, lds, st, C, io);
+        // deliberate: the forward of VAR_GROUP_NM is the VAR_GROUP instantiation - the variants differ only in the backward's mirror
         case VAR_GROUP_NM: return bwd ? launch_one<MODE, VAR_GROUP_NM, 1, true>(grid, block, lds, st, C, io)
                                       : launch_one<MODE, VAR_GROUP, 1, false>(grid, block, lds, st, C, io);
         default: return bwd ? launch_one<MODE, VAR_GLOBAL, 1, true>(grid, block, lds, st, C, io)
@@ -62,28 +44,12 @@ constexpr bool kHasPS = (CSMPN_ALG_N % 2) == 1;
 template <int MODE, bool BWD>
 hipError_t launch_ps_one(unsigned grid, unsigned block, size_t lds, hipStream_t st, const DevCemlp& C, const RowIO& io) {
     if constexpr (kHasPS) {
-        auto kern = cemlp_ps_kernel<ALG_T, MODE, BWD>;
-        static std::atomic<size_t> lds_enabled[kMaxDevices];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-        size_t cur = lds_enabled[dev].load(std::memory_order_relaxed);
-        if (cur < 64 * 1024) cur = 64 * 1024;
-        if (lds > cur) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            lds_enabled[dev].store(lds, std::memory_order_relaxed);
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, st, C, io);
-        return hipGetLastError();
+        return launch_kernel<cemlp_ps_kernel<ALG_T, MODE, BWD>>(grid, block, lds, st, C, io);
     } else {
         return hipErrorInvalidValue;
     }
 }
 }  // namespace
-
-#define CSMPN_CAT2(a, b) a##b
-#define CSMPN_CAT(a, b) CSMPN_CAT2(a, b)
 
 hipError_t CSMPN_CAT(launch_cemlp_, CSMPN_ALG_TAG)(int mode, int var, int h, bool bwd, unsigned grid,
                                                    unsigned block, size_t lds, hipStream_t st, const DevCemlp& C, const RowIO& io) {

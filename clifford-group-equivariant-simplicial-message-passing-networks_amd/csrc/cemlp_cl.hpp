@@ -930,7 +930,7 @@ constexpr size_t cl_fwd_lds_bytes() {
 
 // ---------------------------------------------------------------------------------
 // backward of block K (launched last block first). d/d(out of block K) comes from io.gy (last block; the edge program
-// gathers it by target) or from the hand-over rows io.plw_g1; d/d(input of block K) goes to the hand-over rows (K > 0)
+// gathers it by target) or from the hand-over rows io.handover; d/d(input of block K) goes to the hand-over rows (K > 0)
 // or to the program's gradient targets (K = 0). Block K > 0 reads its input from the saved rows.
 struct ClCarry { f4 a, b; };
 // What the first tile of a block reads from global memory, requested BEFORE the block starts: the last block's ahead of the
@@ -1012,7 +1012,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
     ClRaw<ALG, C, MODE, NA>& raw = cur.raw;
     auto issue = [&](const ClTile<C, MODE>& Tl) {
         const float* gsrc = (kLast ? io.gy + (size_t)(MODE == MODE_EDGE ? (long)Tl.i_dst : Tl.lrow) * ROW
-                                   : io.plw_g1 + (size_t)Tl.lrow * ROW) + c * D;
+                                   : io.handover + (size_t)Tl.lrow * ROW) + c * D;
         if constexpr (kLast || !single) {
             g0 = ld4(gsrc); g1 = ld4(gsrc + 4);
         } else {   // one tile per wave: d/d(out) of this block stayed in registers
@@ -1108,7 +1108,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
             if constexpr (single) {
                 carry_a = f4{gx[0], gx[1], gx[2], gx[3]}; carry_b = f4{gx[4], gx[5], gx[6], gx[7]};
             } else if (Tc.valid) {
-                CL_GST8(io.plw_g1 + (size_t)Tc.row * ROW + c * D, sc + r * SS + c * D, gx);
+                CL_GST8(io.handover + (size_t)Tc.row * ROW + c * D, sc + r * SS + c * D, gx);
             }
         } else if constexpr (MODE == MODE_EDGE) {
             if (io.gx[0]) {

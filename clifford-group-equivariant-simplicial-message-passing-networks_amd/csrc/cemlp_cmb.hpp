@@ -409,7 +409,7 @@ __device__ void cb_block(const RowIO& io, float* tab, float* work, int* ctr, ClS
         }
         CM_FENCE();
         CmPiece gp;
-        gp.load((kLast ? io.gy + (size_t)(MODE == MODE_EDGE ? (long)T.i_dst : T.lrow) * ROW : io.plw_g1 + (size_t)T.lrow * ROW) + q * D);
+        gp.load((kLast ? io.gy + (size_t)(MODE == MODE_EDGE ? (long)T.i_dst : T.lrow) * ROW : io.handover + (size_t)T.lrow * ROW) + q * D);
         asm volatile("" ::: "memory");
         stamp(1);
         CB_MARK(1);
@@ -599,7 +599,7 @@ __device__ void cb_block(const RowIO& io, float* tab, float* work, int* ctr, ClS
             f4 gx[8];
             gx_of(IC<0>{}, gx);
             next_tile();
-            if (Tc.valid) cm_store_piece(io.plw_g1 + (size_t)Tc.row * ROW + q * D, gx);
+            if (Tc.valid) cm_store_piece(io.handover + (size_t)Tc.row * ROW + q * D, gx);
         } else if constexpr (MODE == MODE_EDGE) {
             if constexpr (NA > 0) {
                 if (io.gx[1]) {

@@ -328,7 +328,7 @@ __device__ void cp_block(const RowIO& io, float* tab, float* slots, float* red, 
         // d/d(out), own half: it travels under the per-channel product phase
         CM_FENCE();
         CmPiece gp;
-        gp.load((kLast ? io.gy + (size_t)(MODE == MODE_EDGE ? (long)T.i_dst : T.lrow) * ROW : io.plw_g1 + (size_t)T.lrow * ROW) +
+        gp.load((kLast ? io.gy + (size_t)(MODE == MODE_EDGE ? (long)T.i_dst : T.lrow) * ROW : io.handover + (size_t)T.lrow * ROW) +
                 (16 * p + q) * D);
         asm volatile("" ::: "memory");
         float nlsum = 0.f;
@@ -524,7 +524,7 @@ __device__ void cp_block(const RowIO& io, float* tab, float* slots, float* red, 
         asm volatile("" ::: "memory");
         const int coff = (16 * p + q) * D;
         if constexpr (K > 0) {
-            if (Tc.valid) cm_store_piece(io.plw_g1 + (size_t)Tc.row * ROW + coff, gx0);
+            if (Tc.valid) cm_store_piece(io.handover + (size_t)Tc.row * ROW + coff, gx0);
         } else if constexpr (MODE == MODE_EDGE) {
             if constexpr (NA > 0) {
                 if (io.gx[1] && p == 1) {   // wave 1 takes the attribute chunk (wave 0 gathers it)

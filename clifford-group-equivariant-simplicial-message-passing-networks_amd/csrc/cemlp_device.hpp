@@ -78,7 +78,7 @@ struct DevCemlp {
                          // where LDS, not registers, limits the resident waves)
     float* gtiles;       // non-null: row-tile buffers live in this global scratch (too big for LDS)
     int det_slice_floats;  // > 0: deterministic mode of the general kernels - the g* pointers are slice 0 of a per-workgroup region
-    int phased;            // 1: backward block by block (outer loop over blocks, last first): mirror of ONE block in LDS, d/d(block input) rows through io.plw_g1
+    int phased;            // 1: backward block by block (outer loop over blocks, last first): mirror of ONE block in LDS, d/d(block input) rows through io.handover
     int CT;                // wide kernel (cemlp_wide.hpp): 16-channel tiles of a row tile = ceil(max O / 16); MT waves run them
     int off_park;          // ... float offset of the parking region inside one row tile's buffers
     DevBlock b[4];
@@ -119,15 +119,15 @@ struct RowIO {
     float* save;
     const float* saved;
     unsigned long long* stamps;   // diagnostic (-DCSMPN_STAMPS) cycle accumulators, else null
-    float* rl_partials;     // row-per-lane backward (cemlp_rl.hpp): one slice of parameter-gradient sums per workgroup
+    float* rl_partials;     // backward of cemlp_cl.hpp, cemlp_cmb.hpp, cemlp_cmp.hpp: one ClPart slice of parameter-gradient sums per workgroup and block (summed by cl_reduce_kernel)
     // deterministic mode (CSMPN_FLAG_DETERMINISTIC, row-per-lane kernels only): EDGE rows are not
     // scattered; `agg` (forward) / `gx[0]` (backward) is an [rows, C, D] table in sorted edge order
     // that a segmented reduction sums afterwards in a fixed order
     int row_store;
     int save_state;         // CSMPN_FLAG_SAVE_STATE (cemlp_cl.hpp): the blocks' outputs in front of the layer norm are saved / available
-    const float* plw_tabs;  // wide parity-lane kernels (cemlp_plw.hpp): rotation tables packed into the workspace
-    float* plw_g1;          // ... backward: d/d(block-1 input) rows handed from the block-1 launch to the block-0 launch
-    float* plw_part;        // ... backward: one slice of weight-gradient tiles per workgroup (added by plw_reduce_kernel)
+    const float* tabs;      // plw, pg, pq: rotation / weight-fragment tables packed into the workspace
+    float* handover;        // block-by-block backwards (every family, the general kernels' phased form): d/d(block input) rows handed from one block's launch to the next
+    float* slices;          // pl, plw, pg, pq backward: one slice of parameter-gradient sums per workgroup (pl: per wave), added by the family's reduce kernel
     // Fused simplex embedding (round 3, MODE_PLAIN of the wide parity-lane kernels; hulls_cssmpnn.py:96-125): row r is vertex
     // order r % emb_nperm of simplex r / emb_nperm; its input channel v * emb_k + k is channel k of the embedded vertex
     // row seg[0].a[emb_verts[r * emb_nv + v]] ([S, emb_k, D]); the emb_nperm consecutive output rows of a simplex are summed

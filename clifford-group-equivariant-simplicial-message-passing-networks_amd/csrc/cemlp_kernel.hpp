@@ -400,7 +400,7 @@ __global__ void __launch_bounds__(BWD ? 256 : 512) cemlp_kernel(const DevCemlp C
     // each over ALL row tiles of the workgroup - the LDS mirror holds ONE block's gradient tensors (flushed between the
     // phases), which leaves room for a second row tile per workgroup where both blocks' mirrors did not (md17's 32
     // channels: 2 instead of 4 waves per CU). A wave keeps its tiles from phase to phase: the rows d/d(block input) it
-    // reads in phase k - 1 are the ones it wrote itself in phase k (io.plw_g1, laid out like the saved inputs).
+    // reads in phase k - 1 are the ones it wrote itself in phase k (io.handover, laid out like the saved inputs).
     const bool phased = BWD && C.phased != 0 && use_saved;
   for (int ph = phased ? C.nblk - 1 : 0; ph >= 0; --ph) {
     TileIdx nidx = load_tile_indices<R>(io, ((long)blockIdx.x * RT + rt) * R, tid_rt);
@@ -496,7 +496,7 @@ __global__ void __launch_bounds__(BWD ? 256 : 512) cemlp_kernel(const DevCemlp C
             const int OL = BL.O;
             const bool handed = phased && ph + 1 < C.nblk;   // d/d(out of block ph) = the rows phase ph + 1 wrote
             const int OG = handed ? C.b[ph].O : OL;
-            const float* gsrc = handed ? io.plw_g1 + save_off(ph + 1) : io.gy;
+            const float* gsrc = handed ? io.handover + save_off(ph + 1) : io.gy;
             f4 gout[D];
             {
                 const int c = NW * mt + ge.cn;
@@ -573,7 +573,7 @@ __global__ void __launch_bounds__(BWD ? 256 : 512) cemlp_kernel(const DevCemlp C
                     if (phased) {   // the rows go to the hand-over region; this wave reads them back in phase k - 1
                         const int ci = NW * mt + ge.cn;
                         if (mt < B.NTi && ci < B.I) {
-                            float* hp = io.plw_g1 + save_off(k);
+                            float* hp = io.handover + save_off(k);
 #pragma unroll
                             for (int v = 0; v < 4; ++v) {
                                 const long grow = row0 + ge.r0 + v;

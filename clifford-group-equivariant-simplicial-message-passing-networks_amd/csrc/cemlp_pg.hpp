@@ -333,7 +333,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
     const int r = lane & 15, c = 4 * wave + (lane >> 4);             // ROW layout
     const bool cvalid = c < C;
     const int cc = cvalid ? c : C - 1;
-    const f4* tabs = reinterpret_cast<const f4*>(io.plw_tabs);   // (re-read per tile: re-read per tile, see the asm statement in the tile loop)
+    const f4* tabs = reinterpret_cast<const f4*>(io.tabs);   // (re-read per tile: re-read per tile, see the asm statement in the tile loop)
     PgStamp stamp(0);
 
     // per-channel parameters and path weights of both blocks -> LDS (zero beyond C)
@@ -608,7 +608,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_fwd_kernel(const DevCe
 // =================================================================================
 // backward
 //
-// One launch per block (K = 1, then K = 0; d/d(block-1 input) travels as rows through io.plw_g1), always on the state the
+// One launch per block (K = 1, then K = 0; d/d(block-1 input) travels as rows through io.handover), always on the state the
 // forward saved (CSMPN_FLAG_SAVE_STATE: y, R, s in ROW-layout lane order): no channel mix and no geometric product is
 // recomputed. Per 16-row tile:
 //   d/d(out) -> A | ROW: z = gate(y) y -> A, layer-norm backward -> ggp -> B | MIX: gz = WL^T ggp (own 4 blades), d/dWL += ggp^T z
@@ -693,7 +693,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int r = lane & 15, c = 4 * wave + (lane >> 4), l16 = lane & 15;
     const bool cvalid = c < C;
-    const f4* tabs = reinterpret_cast<const f4*>(io.plw_tabs);   // (re-read per tile: re-read per tile, see the asm statement in the tile loop)
+    const f4* tabs = reinterpret_cast<const f4*>(io.tabs);   // (re-read per tile: re-read per tile, see the asm statement in the tile loop)
     PgStamp stamp(0);
     {
         const DevBlock& B = Cd.b[K];
@@ -746,7 +746,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
                     const size_t grow = MODE == MODE_EDGE ? (size_t)idx[rr] : (size_t)(tile_ * kPgRows + rr);
                     pre[i] = ld4(io.gy + grow * ROW + 4 * e);
                 } else {
-                    pre[i] = ld4(io.plw_g1 + (size_t)(tile_ * kPgRows + rr) * ROW + 4 * e);
+                    pre[i] = ld4(io.handover + (size_t)(tile_ * kPgRows + rr) * ROW + 4 * e);
                 }
             }
         }
@@ -1081,7 +1081,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
         if constexpr (K == 1) {
             for (int p = tid; p < kPgRows * PPR; p += kPgThreads) {
                 const int rr = p / PPR, e = p % PPR;
-                if (row0 + rr < io.rows) st4(io.plw_g1 + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pg_off(e >> 3, rr, e & 7)));
+                if (row0 + rr < io.rows) st4(io.handover + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pg_off(e >> 3, rr, e & 7)));
             }
         } else if constexpr (MODE == MODE_EDGE) {
             if (io.gx[0]) {
@@ -1142,7 +1142,7 @@ __global__ void __launch_bounds__(kPgThreads, 2) cemlp_pg_bwd_kernel(const DevCe
         stamp(8);
     }
     // ---- this workgroup's slice: every element has one owner
-    float* slice = io.plw_part + (size_t)blockIdx.x * CF::slice_floats(K);
+    float* slice = io.slices + (size_t)blockIdx.x * CF::slice_floats(K);
     {
         const int half = wave & 1, tl = wave >> 1, ot = tl >> 1, ct = tl & 1;
         pg_store_unit<2>(slice + CF::woff(K, mL), accL, ot, ct, half, lane);

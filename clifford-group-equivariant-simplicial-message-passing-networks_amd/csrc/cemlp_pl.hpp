@@ -1195,7 +1195,7 @@ __global__ void __launch_bounds__(64 * kPlWaves, BWD ? CSMPN_PL_BWD_WAVES : CSMP
 
     if constexpr (BWD) {
         using PP = PlPart<LY>;
-        float* slice = io.plw_part + ((size_t)blockIdx.x * kPlWaves + wave) * PP::slice;
+        float* slice = io.slices + ((size_t)blockIdx.x * kPlWaves + wave) * PP::slice;
         static_for<0, NCH0>([&](auto chc) { pl_store_tile<ALG>(slice, decltype(chc)::value, aW1_0[decltype(chc)::value], ge.lane); });
         pl_store_tile<ALG>(slice, NCH0, aWR_0, ge.lane);
         pl_store_tile<ALG>(slice, NCH0 + 1, aWL_0, ge.lane);

@@ -330,7 +330,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? (CF::fwd_total * 4 
     const int wave = threadIdx.x >> 6;
     const PlGeo<ALG> ge(threadIdx.x & 63);
     const bool cvalid = 8 * wave + ge.c < C;
-    const float* tabs = io.plw_tabs;
+    const float* tabs = io.tabs;
     float* stg = lds + CF::st_off;
     // per-channel parameters -> LDS (zero beyond C)
     static_for<0, CF::NBLK>([&](auto kk) {
@@ -755,7 +755,7 @@ __global__ void __launch_bounds__(64 * kPlReduceSubs) plw_reduce_kernel(const De
     if (sub == 0 && live) *dst += pl_reduce_combine(red, threadIdx.x);
 }
 
-// BLK = 1: gout -> block-1 backward -> d/d(block-1 input) rows to io.plw_g1.   BLK = 0: io.plw_g1 -> block-0
+// BLK = 1: gout -> block-1 backward -> d/d(block-1 input) rows to io.handover.   BLK = 0: io.handover -> block-0
 // backward -> input gradients (scatter / rows). Parameter gradients of block BLK.
 // SAVES: the forward ran with CSMPN_FLAG_SAVE_STATE (regions 2 .. 7 of the saved buffer hold the blocks' s, y, R): a
 // compile-time choice, as in cemlp_pl.hpp / cemlp_cl.hpp.
@@ -773,7 +773,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? CF::WG_PER_CU_BWD :
     const PlGeo<ALG> ge(threadIdx.x & 63);
     const bool cvalid = 8 * wave + ge.c < C;
     const int cch = (cvalid ? 8 * wave + ge.c : 0) * D;   // this lane's channel offset inside a C-wide row
-    const float* tabs = io.plw_tabs;
+    const float* tabs = io.tabs;
     float* stg = lds + CF::st_off;
     float* tot = lds + CF::tot_off + threadIdx.x;
     {
@@ -871,7 +871,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? CF::WG_PER_CU_BWD :
                 const long rr = tile * kPlRows + r;
                 if (rr < io.rows)
                     for (int e = 4 * threadIdx.x; e < ROW; e += 4 * NT)
-                        *reinterpret_cast<f4*>(io.plw_g1 + (size_t)rr * ROW + e) = ld4(stg + r * RS + e);
+                        *reinterpret_cast<f4*>(io.handover + (size_t)rr * ROW + e) = ld4(stg + r * RS + e);
             }
             __syncthreads();
         } else {
@@ -905,7 +905,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? CF::WG_PER_CU_BWD :
             };
             float g1[DL], gy0[DL];
             if constexpr (CF::NBLK > 1) {
-                pl_load<ALG>(g1, io.plw_g1 + (size_t)lrow * ROW + cch, ge.s, von);
+                pl_load<ALG>(g1, io.handover + (size_t)lrow * ROW + cch, ge.s, von);
             } else {   // single block: d/d(out) comes from the caller
                 long grow = MODE == MODE_EDGE ? (long)(valid ? i_dst : 0) : lrow;
                 if (MODE == MODE_PLAIN && io.emb_nperm) grow = lrow / io.emb_nperm;
@@ -1045,7 +1045,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? CF::WG_PER_CU_BWD :
         const DevBlock& B = Cd.b[BLK];
         {
             using PP = PlwPart<CF, BLK>;
-            float* slice = io.plw_part + (size_t)blockIdx.x * PP::slice;
+            float* slice = io.slices + (size_t)blockIdx.x * PP::slice;
             static_for<0, NIN>([&](auto jc) {
                 plw_store_tile<ALG, CF, BLK>(slice, PP::tile_of(0, decltype(jc)::value), aW1[decltype(jc)::value], threadIdx.x);
             });
@@ -1087,7 +1087,7 @@ __global__ void __launch_bounds__(64 * CF::NG, CF::NG >= 3 ? CF::WG_PER_CU_BWD :
                     tot[(SI::wB + q) * NT] * (ge.s ? 1.0f : float(P::t.I2));
             });
             __syncthreads();
-            float* tail = io.plw_part + (size_t)blockIdx.x * PP::slice + PP::w_floats;
+            float* tail = io.slices + (size_t)blockIdx.x * PP::slice + PP::w_floats;
             auto quarters = [&](int l) { return (img[l] + img[L_tot + l]) + (img[2 * L_tot + l] + img[3 * L_tot + l]); };
             for (int e = threadIdx.x; e < PP::i_tot; e += NT) {
                 float v;

@@ -249,7 +249,7 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int r = tid & 15, cq = tid >> 4;                            // ROW layout: channels cq, cq + 16
     const int mp = wave & 1, mot = wave >> 1;                         // MIX layout: piece, output tile
-    const f4* tabs = reinterpret_cast<const f4*>(io.plw_tabs);
+    const f4* tabs = reinterpret_cast<const f4*>(io.tabs);
     PgStamp stamp(0);
 
     // per-channel parameters and path weights of the blocks -> LDS
@@ -593,7 +593,7 @@ __global__ void __launch_bounds__(kPqThreads, 3) cemlp_pq_fwd_kernel(const DevCe
 
 
 // =================================================================================
-// backward: one launch per block (K = 1, then K = 0; d/d(block-1 input) travels as rows through io.plw_g1), on the state the
+// backward: one launch per block (K = 1, then K = 0; d/d(block-1 input) travels as rows through io.handover), on the state the
 // forward saved. Per 16-row tile (phases as cemlp_pg.hpp):
 //   d/d(out) -> A | ROW: z = gate(y) y -> A, layer-norm backward -> ggp -> B | MIX: gz = WL^T ggp, d/dWL += ggp^T z -> gz over ggp in B
 //   | ROW: geometric product + normalisation backward -> gR -> B | MIX: WR^T gR, d/dWR += gR^T z | ROW: MVSiLU backward -> gy -> B,
@@ -747,7 +747,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
     int* sidx_n = sidx + 64;
     constexpr int NPRE = PPR * kPqRows / kPqThreads;               // 16-byte pieces of a C-channel tile per thread
     static_assert(NPRE * kPqThreads == PPR * kPqRows && PPR == 64, "whole pieces per thread, one row per wave and piece index (pq_row_of)");
-    const f4* tabs = reinterpret_cast<const f4*>(io.plw_tabs);
+    const f4* tabs = reinterpret_cast<const f4*>(io.tabs);
     PgStamp stamp(0);
     {
         const DevBlock& B = Cd.b[K];
@@ -808,7 +808,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
                     const size_t grow = MODE == MODE_EDGE ? (size_t)ia[i] : (size_t)(tile_ * kPqRows + rr);
                     pre[i] = ld4(io.gy + grow * ROW + 4 * e);
                 } else {
-                    pre[i] = ld4(io.plw_g1 + (size_t)(tile_ * kPqRows + rr) * ROW + 4 * e);
+                    pre[i] = ld4(io.handover + (size_t)(tile_ * kPqRows + rr) * ROW + 4 * e);
                 }
             }
         }
@@ -1222,7 +1222,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
 #pragma unroll
                 for (int i = 0; i < NPRE; ++i) {
                     const int rr = pq_row_of(tid, i), e = tid & 63;
-                    if (row0 + rr < io.rows) st4(io.plw_g1 + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pq_off(e >> 1, rr, e & 1)));
+                    if (row0 + rr < io.rows) st4(io.handover + (size_t)(row0 + rr) * ROW + 4 * e, ld4(bufB + pq_off(e >> 1, rr, e & 1)));
                 }
             } else if constexpr (PLAIN) {
                 // (every chunk's d/dx rows left in the MIX phase above)
@@ -1289,7 +1289,7 @@ __global__ void __launch_bounds__(kPqThreads, PQ_BWD_WPE) cemlp_pq_bwd_kernel(co
         stamp(8);
     }
     // ---- this workgroup's slice: every element has one owner
-    float* slice = io.plw_part + (size_t)group * CF::slice_floats(K);
+    float* slice = io.slices + (size_t)group * CF::slice_floats(K);
     {
         const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, cq = tid >> 4, l16 = tid & 15;
         const int ot = wave >> 1, ct = wave & 1;

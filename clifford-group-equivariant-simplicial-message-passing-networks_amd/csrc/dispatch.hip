@@ -10,17 +10,26 @@ namespace csmpn {
 
 // ----------------------------------------------------------------------------- sizes of the families' workspace regions
 namespace {
+// the shape of a stage with block 0 reading i0 input channels, as the lane-kernel units key it (launch.hpp)
+LaneShape shape_of(int mode, int nblk, int ch, int i0) {
+    return LaneShape{mode, nblk, ch, mode == MODE_EDGE ? i0 - ch : (mode == MODE_NODE ? i0 - 2 * ch : i0)};
+}
 // 16-row-tile MFMA-mixing kernels for Cl(3,0) (cemlp_pq.hpp): weight-fragment tables + one gradient slice per workgroup
 size_t pq_region_bytes(int nblk, int ch, int i0) {
     size_t best = 0;
     for (int mode : {MODE_EDGE, MODE_NODE, MODE_PLAIN}) {
-        const int na = mode == MODE_EDGE ? i0 - ch : (mode == MODE_NODE ? i0 - 2 * ch : i0);
-        const size_t tf = cemlp_pq_table_floats_n3(mode, nblk, ch, na);
+        const LaneShape s = shape_of(mode, nblk, ch, i0);
+        const size_t tf = cemlp_pq_n3().table_floats(s);
         if (!tf) continue;
-        const size_t b = (tf + cemlp_pq_slice_floats_n3(mode, nblk, ch, na) * kPqGridCap) * sizeof(float) + 1024;
+        const size_t b = (tf + cemlp_pq_n3().slice_floats(s) * kPqGridCap) * sizeof(float) + 1024;
         best = b > best ? b : best;
     }
     return best;
+}
+// floats of one slice of the unit's backward, the larger of the edge and the node stage
+size_t egcl_slice_floats(const LaneUnit& u, int nblk, int ch, int i0) {
+    const size_t e = u.slice_floats(shape_of(MODE_EDGE, nblk, ch, i0)), n = u.slice_floats(shape_of(MODE_NODE, nblk, ch, i0));
+    return n > e ? n : e;
 }
 }  // namespace
 // standalone CEMLPs served by the same family (MODE_PLAIN of cemlp_pq.hpp: the md17 embeddings and head): their saved buffer holds,
@@ -29,7 +38,7 @@ bool pq_plain_shape(int n, const csmpn_block_params* blocks, int nblk) {
     if (n != 3 || nblk < 1 || nblk > 2 || sw().no_pq || sw().no_cm || sw().no_cm_bwd) return false;
     for (int k = 0; k < nblk; ++k)
         if (blocks[k].out_features != 32 || (k > 0 && blocks[k].in_features != 32)) return false;
-    return cemlp_pq_table_floats_n3(MODE_PLAIN, nblk, 32, blocks[0].in_features) != 0;
+    return cemlp_pq_n3().table_floats(LaneShape{MODE_PLAIN, nblk, 32, blocks[0].in_features}) != 0;
 }
 namespace {
 size_t rl_partial_bytes(int n, const csmpn_block_params* blocks, int nblk) {
@@ -39,15 +48,9 @@ size_t rl_partial_bytes(int n, const csmpn_block_params* blocks, int nblk) {
         if (blocks[k].out_features != ch || (k > 0 && blocks[k].in_features != ch)) return 0;
     // (row, channel)-per-lane backward (cemlp_cl.hpp): one slice per workgroup
     const int i0 = blocks[0].in_features;
-    size_t clf = cemlp_cl_partial_floats_n3(MODE_EDGE, nblk, ch, i0);
-    const size_t cln = cemlp_cl_partial_floats_n3(MODE_NODE, nblk, ch, i0);
-    clf = cln > clf ? cln : clf;
-    size_t cl = clf * sizeof(float) * kClMaxBwdGroups;
+    const size_t cl = egcl_slice_floats(cemlp_cl_n3(), nblk, ch, i0) * sizeof(float) * kClMaxBwdGroups;
     // channel-MFMA backward (cemlp_cmb.hpp / cemlp_cmp.hpp): the same region and slice layout
-    size_t cmf = cemlp_cm_partial_floats_n3(MODE_EDGE, nblk, ch, i0);
-    const size_t cmn = cemlp_cm_partial_floats_n3(MODE_NODE, nblk, ch, i0);
-    cmf = cmn > cmf ? cmn : cmf;
-    const size_t cm = cmf * sizeof(float) * kCmSliceCap;
+    const size_t cm = egcl_slice_floats(cemlp_cm_n3(), nblk, ch, i0) * sizeof(float) * kClMaxBwdGroups;
     const size_t lane = cm > cl ? cm : cl;
     const size_t pq = pq_region_bytes(nblk, ch, i0);   // the same region serves whichever family takes the launch
     return pq > lane ? pq : lane;
@@ -58,8 +61,8 @@ bool cl_shape(int n, const csmpn_block_params* blocks, int nblk) {
     if (n != 3 || nblk != 2) return false;
     const int ch = blocks[0].out_features, i0 = blocks[0].in_features;
     if (blocks[1].out_features != ch || blocks[1].in_features != ch) return false;
-    if (has_cemlp_cl_n3(MODE_EDGE, nblk, ch, i0) || has_cemlp_cl_n3(MODE_NODE, nblk, ch, i0)) return true;
-    return !sw().no_cm_bwd && (has_cemlp_cm_n3(MODE_EDGE, nblk, ch, i0, true) || has_cemlp_cm_n3(MODE_NODE, nblk, ch, i0, true));
+    if (egcl_slice_floats(cemlp_cl_n3(), nblk, ch, i0)) return true;
+    return !sw().no_cm_bwd && egcl_slice_floats(cemlp_cm_n3(), nblk, ch, i0);
 }
 }  // namespace
 
@@ -79,28 +82,14 @@ bool general_phased_shape(int n, const csmpn_block_params* blocks, int nblk) {
 }
 
 namespace {
-// bytes of the wide parity-lane kernels' rotation tables (cemlp_plw.hpp), also carved from the END of the workspace
-// (never together with the row-per-lane region: different algebras). Upper bound over the entry points.
-// ... and of the backward's partial buffer: one slice of weight-gradient MFMA tiles per workgroup (upper bound)
-size_t plw_part_bytes(int ch) {
-    const size_t NG = (ch + 7) / 8, nch0 = 2 * NG + 1;
-    const size_t image = 8 * NG * (3 + 3 * 6 + 64) + 16;   // per-channel sums (CP x (3 + 3 G + P)), generous
-    const size_t per_cu = 4 / NG > 0 ? 4 / NG : 1;
-    size_t bytes = ((nch0 + 2 * NG) * 12 * 64 * NG + image) * sizeof(float) * kPlwMaxGroups * per_cu + 256;
-    if (ch == 8) {   // the 8-channel parity-lane backward (cemlp_pl.hpp): one slice per wave, 4 waves x 256 workgroups
-        const size_t pl = (size_t)(8 * 768 + 2 * 640) * sizeof(float) * 4 * kPlMaxBwdGroups + 256;
-        bytes = pl > bytes ? pl : bytes;
-    }
-    return bytes;
-}
+// bytes of the wide parity-lane kernels' rotation tables (cemlp_plw.hpp) and gradient slices, also carved from the END of
+// the workspace (never together with the row-per-lane region: different algebras). Upper bounds over the entry points (launch.hpp).
 size_t plw_table_bytes(int n, const csmpn_block_params* blocks, int nblk) {
     if (n != 5 || nblk < 1 || nblk > 2) return 0;
     const int ch = blocks[0].out_features;
     if (ch < 8 || ch > 32) return 0;
     if (nblk == 2 && (blocks[1].out_features != ch || blocks[1].in_features != ch)) return 0;
-    const size_t NG = (ch + 7) / 8, nch0 = 2 * NG + 1;
-    // (+ 64 KB: the weight-fragment tables of cemlp_pg.hpp, carved from the same region, are up to 368 KB at 28 / 32 channels)
-    return ((2 * NG * nch0 + 4 * NG * NG) + (2 * NG * NG + 4 * NG * NG)) * 384 * sizeof(float) + 256 + plw_part_bytes(ch) + (ch > 16 ? 65536 : 0);
+    return plw_tables_bytes(ch) + 256 + plw_part_bytes(ch) + (ch > 16 ? kPgTablesExtraBytes : 0);
 }
 }  // namespace
 
@@ -122,8 +111,7 @@ size_t state_channels(int n, const csmpn_block_params* blocks, int n_blocks) {
     // (17 .. 32 channels: 32 - the 16-row-tile kernels of cemlp_pg.hpp keep 4 channels per wave, 8 waves per tile)
     if (plw_table_bytes(n, blocks, n_blocks)) return (size_t)3 * n_blocks * (ch > 16 ? 32 : (ch + 7) / 8 * 8);
     if (cl_shape(n, blocks, n_blocks)) {
-        if (has_cemlp_cl_n3(MODE_EDGE, n_blocks, (int)ch, blocks[0].in_features) || has_cemlp_cl_n3(MODE_NODE, n_blocks, (int)ch, blocks[0].in_features))
-            return (size_t)n_blocks * ch;
+        if (egcl_slice_floats(cemlp_cl_n3(), n_blocks, (int)ch, blocks[0].in_features)) return (size_t)n_blocks * ch;
         // the state regions of the 32-channel kernels exist only while their pair backward is enabled
         if (ch == 32 && !sw().no_cm_bwd) return (size_t)3 * n_blocks * 32;
     }
@@ -190,6 +178,7 @@ struct Launch {   // one run_rows call as the families see it
     StageShape S;
     float* handover;   // hand-over rows behind the saved block inputs (saved_layout)
 };
+LaneShape lane_shape(const Launch& x) { return LaneShape{x.mode, x.S.nblk, x.S.ch, x.S.na}; }
 bool egcl(const Launch& x) { return x.mode != MODE_PLAIN && x.S.ok; }
 bool two_uniform_blocks(const Launch& x) { return x.S.nblk == 2 && x.S.uniform_width && x.S.all_w1_sub; }
 bool fits(const Plan& plan, size_t bytes) { return plan.workspace && plan.workspace_bytes >= bytes; }
@@ -203,7 +192,7 @@ struct Family {
     unsigned (*grid)(const Launch& x, long rows);
     // the family's regions at the end of the workspace and in the saved buffer; *tabs: its weight tables
     int (*regions)(const Launch& x, RowIO& io, float** tabs);
-    hipError_t (*launch)(const Launch& x, unsigned grid, hipStream_t st, const RowIO& io, float* tabs, bool* handled);
+    const LaneUnit* (*unit)(const AlgOps& A);   // the instantiation unit that launches (null: the algebra has none)
     void (*kernel_label)(const Launch& x, const RowIO& io);
 };
 
@@ -216,7 +205,7 @@ bool pq_eligible(const Launch& x, const RowIO& io) {
     if (S.ch != 32 || !S.uniform_width || !S.all_w1_sub || !S.ok) return false;
     // standalone CEMLP: one contiguous input of I0 channels; not the fused embedding
     if (x.mode == MODE_PLAIN && (io.nseg != 1 || io.emb_nperm != 0 || io.seg[0].ch != S.i0)) return false;
-    if (!cemlp_pq_table_floats_n3(x.mode, S.nblk, S.ch, S.na) || !fits(x.plan, pq_region_bytes(S.nblk, S.ch, S.i0))) return false;
+    if (!cemlp_pq_n3().table_floats(lane_shape(x)) || !fits(x.plan, pq_region_bytes(S.nblk, S.ch, S.i0))) return false;
     // the backward runs on the state its forward saved (CSMPN_FLAG_SAVE_STATE, in ITS lane order); without the flag the
     // forward still serves (it writes the row-major block-1 inputs) and the wave-pair backward (cemlp_cmp.hpp) recomputes
     return !x.bwd || (io.saved && io.save_state && !sw().no_cm_bwd);
@@ -228,14 +217,10 @@ unsigned pq_grid(const Launch&, long rows) {
     return capped((rows + 15) / 16, kPqGridCap);
 }
 int pq_regions(const Launch& x, RowIO& io, float** tabs) {
-    const StageShape& S = x.S;
-    *tabs = reinterpret_cast<float*>(tail_region(x.plan, cemlp_pq_table_floats_n3(x.mode, S.nblk, S.ch, S.na) * sizeof(float) + 16, 256));
-    io.plw_part = reinterpret_cast<float*>(reinterpret_cast<char*>(*tabs) - cemlp_pq_slice_floats_n3(x.mode, S.nblk, S.ch, S.na) * sizeof(float) * kPqGridCap);
-    if (x.bwd) io.plw_g1 = x.handover;
+    *tabs = reinterpret_cast<float*>(tail_region(x.plan, cemlp_pq_n3().table_floats(lane_shape(x)) * sizeof(float) + 16, 256));
+    io.slices = reinterpret_cast<float*>(reinterpret_cast<char*>(*tabs) - cemlp_pq_n3().slice_floats(lane_shape(x)) * sizeof(float) * kPqGridCap);
+    if (x.bwd) io.handover = x.handover;
     return CSMPN_OK;
-}
-hipError_t pq_launch(const Launch& x, unsigned grid, hipStream_t st, const RowIO& io, float* tabs, bool* handled) {
-    return launch_cemlp_pq_n3(x.mode, x.S.nblk, x.S.ch, x.S.na, x.bwd, !(x.bwd && x.tables_ready), grid, st, x.plan.C, io, tabs, handled);
 }
 void pq_label(const Launch& x, const RowIO&) {
     note_kernel("csmpn::cemlp_pq_%s_kernel<%s, ...> (mode %d, %d channels, %d %s channels, %d block%s)", x.bwd ? "bwd" : "fwd", x.A.name,
@@ -245,24 +230,20 @@ void pq_label(const Launch& x, const RowIO&) {
 // 16-row-tile MFMA-mixing kernels (cemlp_pg.hpp): Cl(5,0) / Cl(4,1), two blocks of 24 / 28 / 32 channels, EGCL edge / node programs
 bool pg_eligible(const Launch& x, const RowIO& io) {
     const StageShape& S = x.S;
-    if (sw().no_pg || !x.A.launch_pg || !two_uniform_blocks(x) || S.ch <= 16 || S.ch > 32 || !egcl(x)) return false;
-    if (!x.A.has_pg(x.mode, S.ch, S.na, x.bwd)) return false;
-    const size_t tf = x.A.pg_table_floats(x.mode, S.ch, S.na);
+    if (sw().no_pg || !x.A.pg || !two_uniform_blocks(x) || S.ch <= 16 || S.ch > 32 || !egcl(x)) return false;
+    const size_t tf = x.A.pg->table_floats(lane_shape(x));
     if (tf == 0 || !fits(x.plan, tf * sizeof(float) + plw_part_bytes(S.ch) + 1024)) return false;
     // the backward of this family runs on the state its forward saved (CSMPN_FLAG_SAVE_STATE, in ITS lane order): without
     // the flag the forward still serves (it writes the row-major block-1 inputs every backward reads) and the wide
     // parity-lane backward recomputes from them
     return !x.bwd || (io.saved && io.save_state);
 }
-unsigned pg_grid(const Launch&, long rows) { return capped((rows + 15) / 16, 256); }   // one 16-row tile per workgroup iteration, one 8-wave workgroup per CU
+unsigned pg_grid(const Launch&, long rows) { return capped((rows + 15) / 16, kPgGridCap); }   // one 16-row tile per workgroup iteration, one 8-wave workgroup per CU
 int pg_regions(const Launch& x, RowIO& io, float** tabs) {
-    *tabs = reinterpret_cast<float*>(tail_region(x.plan, x.A.pg_table_floats(x.mode, x.S.ch, x.S.na) * sizeof(float) + 16, 256));
-    io.plw_part = reinterpret_cast<float*>(reinterpret_cast<char*>(*tabs) - plw_part_bytes(x.S.ch));
-    if (x.bwd) io.plw_g1 = x.handover;
+    *tabs = reinterpret_cast<float*>(tail_region(x.plan, x.A.pg->table_floats(lane_shape(x)) * sizeof(float) + 16, 256));
+    io.slices = reinterpret_cast<float*>(reinterpret_cast<char*>(*tabs) - plw_part_bytes(x.S.ch));
+    if (x.bwd) io.handover = x.handover;
     return CSMPN_OK;
-}
-hipError_t pg_launch(const Launch& x, unsigned grid, hipStream_t st, const RowIO& io, float* tabs, bool* handled) {
-    return x.A.launch_pg(x.mode, x.S.ch, x.S.na, x.bwd, !(x.bwd && x.tables_ready), grid, st, x.plan.C, io, tabs, handled);
 }
 void pg_label(const Launch& x, const RowIO&) {
     note_kernel("csmpn::cemlp_pg_%s_kernel<%s, ...> (mode %d, %d channels, %d attribute channels)", x.bwd ? "bwd" : "fwd", x.A.name, x.mode,
@@ -273,13 +254,13 @@ void pg_label(const Launch& x, const RowIO&) {
 // programs and standalone CEMLPs of at most 8 input channels (the one input chunk; with the embed descriptor: the fused embedding)
 bool plw_eligible(const Launch& x, const RowIO& io) {
     const StageShape& S = x.S;
-    if (sw().no_plw || !x.A.launch_plw || S.nblk < 1 || S.nblk > 2) return false;
+    if (sw().no_plw || !x.A.plw || S.nblk < 1 || S.nblk > 2) return false;
     // 8 channels belong to cemlp_pl.hpp; the one-group wide kernels take them only on request (round 2 measured them 4-5x
     // slower - compiled for four waves per SIMD by mistake, 1.3 KB of scratch; with the launch bounds repaired they are on a
     // par: S3 1.339 against 1.333 ms)
     if ((S.ch <= 8 && !(S.ch == 8 && sw().plw8)) || S.ch > 32 || !S.uniform_width || !S.all_w1_sub || !S.ok) return false;
     if (x.mode == MODE_PLAIN && (S.na < 1 || S.na > 8 || io.nseg != 1)) return false;
-    const size_t tf = x.A.plw_table_floats(x.mode, S.ch, S.na, S.nblk);
+    const size_t tf = x.A.plw->table_floats(lane_shape(x));
     if (tf == 0 || !fits(x.plan, tf * sizeof(float) + plw_part_bytes(S.ch) + 1024)) return false;
     return !(x.bwd && S.nblk > 1 && !io.saved);
 }
@@ -289,13 +270,10 @@ unsigned plw_grid(const Launch& x, long rows) {
     return capped((rows + 3) / 4, (x.bwd ? kPlwMaxGroups : 2 * kPlwMaxGroups) * per_cu);
 }
 int plw_regions(const Launch& x, RowIO& io, float** tabs) {
-    *tabs = reinterpret_cast<float*>(tail_region(x.plan, x.A.plw_table_floats(x.mode, x.S.ch, x.S.na, x.S.nblk) * sizeof(float) + 16, 256));
-    io.plw_part = reinterpret_cast<float*>(reinterpret_cast<char*>(*tabs) - plw_part_bytes(x.S.ch));
-    if (x.bwd && x.S.nblk > 1) io.plw_g1 = x.handover;
+    *tabs = reinterpret_cast<float*>(tail_region(x.plan, x.A.plw->table_floats(lane_shape(x)) * sizeof(float) + 16, 256));
+    io.slices = reinterpret_cast<float*>(reinterpret_cast<char*>(*tabs) - plw_part_bytes(x.S.ch));
+    if (x.bwd && x.S.nblk > 1) io.handover = x.handover;
     return CSMPN_OK;
-}
-hipError_t plw_launch(const Launch& x, unsigned grid, hipStream_t st, const RowIO& io, float* tabs, bool* handled) {
-    return x.A.launch_plw(x.mode, x.S.ch, x.S.na, x.S.nblk, x.bwd, grid, st, x.plan.C, io, tabs, handled);
 }
 void plw_label(const Launch& x, const RowIO&) {   // the wide kernels' template arguments live in plw_inst.inc: family + shape
     note_kernel("csmpn::cemlp_plw_%s_kernel<%s, ...> (mode %d, %d channels, %d attribute channels, %d blocks)", x.bwd ? "bwd" : "fwd",
@@ -304,9 +282,9 @@ void plw_label(const Launch& x, const RowIO&) {   // the wide kernels' template 
 
 // parity-lane kernels (cemlp_pl.hpp): Cl(5,0) / Cl(4,1), two blocks of 8 channels, the EGCL attribute widths of S3
 bool pl_eligible(const Launch& x, const RowIO& io) {
-    if (sw().no_pl || !x.A.launch_pl || !two_uniform_blocks(x) || x.S.ch != 8 || !egcl(x)) return false;
+    if (sw().no_pl || !x.A.pl || !two_uniform_blocks(x) || x.S.ch != 8 || !egcl(x)) return false;
     if (x.bwd && !io.saved) return false;
-    return x.A.has_pl(x.mode, x.S.nblk, 8, x.S.i0);
+    return serves(*x.A.pl, lane_shape(x));
 }
 unsigned pl_grid(const Launch& x, long rows) {
     const long tiles = (rows + 3) / 4;   // 4 rows per wave tile; one / two 4-wave workgroups per CU
@@ -317,11 +295,8 @@ int pl_regions(const Launch& x, RowIO& io, float**) {
     // per-wave slices of parameter-gradient sums: at the end of the workspace (as the wide kernels' region)
     const size_t pb = plw_part_bytes(8);
     if (!fits(x.plan, pb + 1024)) return fail(CSMPN_ERR_INVALID, "workspace too small for the parity-lane backward");
-    io.plw_part = reinterpret_cast<float*>(tail_region(x.plan, pb + 16, 256));
+    io.slices = reinterpret_cast<float*>(tail_region(x.plan, pb + 16, 256));
     return CSMPN_OK;
-}
-hipError_t pl_launch(const Launch& x, unsigned grid, hipStream_t st, const RowIO& io, float*, bool* handled) {
-    return x.A.launch_pl(x.mode, x.S.nblk, 8, x.S.i0, x.bwd, grid, st, x.plan.C, io, handled);
 }
 void pl_label(const Launch& x, const RowIO& io) {
     note_kernel("csmpn::cemlp_pl_kernel<%s, %d, %d, %d, %s, %s>", x.A.name, x.mode, x.S.nblk, x.S.i0, x.bwd ? "true" : "false",
@@ -334,8 +309,8 @@ bool cl_eligible(const Launch& x, const RowIO& io) {
     const StageShape& S = x.S;
     if (sw().no_cl || x.plan.id != ALG_N3 || !two_uniform_blocks(x) || !egcl(x)) return false;
     if (x.bwd && !io.saved) return false;
-    if (!has_cemlp_cl_n3(x.mode, S.nblk, S.ch, S.i0)) return false;
-    return !x.bwd || fits(x.plan, cemlp_cl_partial_floats_n3(x.mode, S.nblk, S.ch, S.i0) * sizeof(float) * kClMaxBwdGroups);
+    if (!serves(cemlp_cl_n3(), lane_shape(x))) return false;
+    return !x.bwd || fits(x.plan, cemlp_cl_n3().slice_floats(lane_shape(x)) * sizeof(float) * kClMaxBwdGroups);
 }
 unsigned cl_grid(const Launch& x, long rows) {
     const long rows_per_wave = 64 / x.S.ch;
@@ -351,13 +326,10 @@ unsigned cl_grid(const Launch& x, long rows) {
 }
 int cl_regions(const Launch& x, RowIO& io, float**) {
     if (!x.bwd) return CSMPN_OK;
-    const size_t pb = cemlp_cl_partial_floats_n3(x.mode, x.S.nblk, x.S.ch, x.S.i0) * sizeof(float) * kClMaxBwdGroups;
+    const size_t pb = cemlp_cl_n3().slice_floats(lane_shape(x)) * sizeof(float) * kClMaxBwdGroups;
     io.rl_partials = reinterpret_cast<float*>(tail_region(x.plan, pb, 16));
-    io.plw_g1 = x.handover;
+    io.handover = x.handover;
     return CSMPN_OK;
-}
-hipError_t cl_launch(const Launch& x, unsigned grid, hipStream_t st, const RowIO& io, float*, bool* handled) {
-    return launch_cemlp_cl_n3(x.mode, x.S.nblk, x.S.ch, x.S.i0, x.bwd, grid, st, x.plan.C, io, handled);
 }
 void cl_label(const Launch& x, const RowIO& io) {
     note_kernel("csmpn::cemlp_cl_%s_kernel<%s, %d, %d, %d, %d%s>", x.bwd ? "bwd" : "fwd", x.A.name, x.S.ch, x.mode, x.S.nblk, x.S.na,
@@ -371,8 +343,8 @@ bool cm_eligible(const Launch& x, const RowIO& io) {
     const StageShape& S = x.S;
     if (sw().no_cm || x.plan.id != ALG_N3 || !two_uniform_blocks(x) || !egcl(x)) return false;
     if (x.bwd && !io.saved) return false;
-    if (!has_cemlp_cm_n3(x.mode, S.nblk, S.ch, S.i0, x.bwd)) return false;
-    return !x.bwd || (!sw().no_cm_bwd && fits(x.plan, cemlp_cm_partial_floats_n3(x.mode, S.nblk, S.ch, S.i0) * sizeof(float) * kCmSliceCap));
+    if (!serves(cemlp_cm_n3(), lane_shape(x))) return false;
+    return !x.bwd || (!sw().no_cm_bwd && fits(x.plan, cemlp_cm_n3().slice_floats(lane_shape(x)) * sizeof(float) * kClMaxBwdGroups));
 }
 unsigned cm_grid(const Launch& x, long rows) {
     const long tiles = (rows + 15) / 16;   // tile t (16 rows) belongs to wave t % (4 grid)
@@ -385,13 +357,10 @@ unsigned cm_grid(const Launch& x, long rows) {
 }
 int cm_regions(const Launch& x, RowIO& io, float**) {
     if (!x.bwd) return CSMPN_OK;
-    const size_t pb = cemlp_cm_partial_floats_n3(x.mode, x.S.nblk, x.S.ch, x.S.i0) * sizeof(float) * kCmSliceCap;
+    const size_t pb = cemlp_cm_n3().slice_floats(lane_shape(x)) * sizeof(float) * kClMaxBwdGroups;
     io.rl_partials = reinterpret_cast<float*>(tail_region(x.plan, pb, 16));
-    io.plw_g1 = x.handover;
+    io.handover = x.handover;
     return CSMPN_OK;
-}
-hipError_t cm_launch(const Launch& x, unsigned grid, hipStream_t st, const RowIO& io, float*, bool* handled) {
-    return launch_cemlp_cm_n3(x.mode, x.S.nblk, x.S.ch, x.S.i0, x.bwd, grid, st, x.plan.C, io, handled);
 }
 void cm_label(const Launch& x, const RowIO& io) {
     note_kernel("csmpn::cemlp_%s_kernel<%s, %d, %d, %d, %d%s>", !x.bwd ? "cm_fwd" : (x.S.ch == 32 ? "cmp" : "cmb"), x.A.name, x.S.ch, x.mode,
@@ -400,12 +369,12 @@ void cm_label(const Launch& x, const RowIO& io) {
 
 // In dispatch order: the first eligible family whose launcher has the instantiation takes the launch.
 const Family kFamilies[] = {
-    {"pq", kChannelsAttr, pq_eligible, pq_grid, pq_regions, pq_launch, pq_label},
-    {"pg", kChannelsAttr, pg_eligible, pg_grid, pg_regions, pg_launch, pg_label},
-    {"plw", kChannelsAttr, plw_eligible, plw_grid, plw_regions, plw_launch, plw_label},
-    {"pl", kI0, pl_eligible, pl_grid, pl_regions, pl_launch, pl_label},
-    {"cl", kChannelsI0, cl_eligible, cl_grid, cl_regions, cl_launch, cl_label},
-    {"cm", kChannelsI0, cm_eligible, cm_grid, cm_regions, cm_launch, cm_label},
+    {"pq", kChannelsAttr, pq_eligible, pq_grid, pq_regions, [](const AlgOps&) { return &cemlp_pq_n3(); }, pq_label},
+    {"pg", kChannelsAttr, pg_eligible, pg_grid, pg_regions, [](const AlgOps& A) { return A.pg; }, pg_label},
+    {"plw", kChannelsAttr, plw_eligible, plw_grid, plw_regions, [](const AlgOps& A) { return A.plw; }, plw_label},
+    {"pl", kI0, pl_eligible, pl_grid, pl_regions, [](const AlgOps& A) { return A.pl; }, pl_label},
+    {"cl", kChannelsI0, cl_eligible, cl_grid, cl_regions, [](const AlgOps&) { return &cemlp_cl_n3(); }, cl_label},
+    {"cm", kChannelsI0, cm_eligible, cm_grid, cm_regions, [](const AlgOps&) { return &cemlp_cm_n3(); }, cm_label},
 };
 
 void debug_line(const Family& F, const Launch& x, unsigned grid, long rows) {
@@ -444,7 +413,8 @@ int run_rows(const Plan& plan, int mode, bool bwd, const RowIO& io_in, hipStream
         if (rc) return rc;
         if (sw().debug) debug_line(F, x, grid, io.rows);
         bool handled = false;
-        HIP_TRY(F.launch(x, grid, st, io, tabs, &handled));
+        // the 16-row-tile families' weight tables: packed unless the stage's forward left them in this workspace
+        HIP_TRY(F.unit(A)->launch(lane_shape(x), bwd, !(bwd && tables_ready), grid, st, plan.C, io, tabs, &handled));
         if (handled) {
             F.kernel_label(x, io);
             return CSMPN_OK;
@@ -472,7 +442,7 @@ int run_rows(const Plan& plan, int mode, bool bwd, const RowIO& io_in, hipStream
         const int rc = det_slices(plan, io.row_store != 0, det);
         if (rc) return rc;
     }
-    if (bwd && plan.C.phased) io.plw_g1 = handover;   // hand-over region of the phased backward: behind the saved inputs, laid out like them
+    if (bwd && plan.C.phased) io.handover = handover;   // hand-over region of the phased backward: behind the saved inputs, laid out like them
     // general row-tile kernels from here on: they read packed weight fragments (the lane kernels above do not)
     if (need_pack) {
         const int rcp = run_pack(plan, st);

@@ -1,5 +1,5 @@
-// Host-visible launcher declarations of every kernel family, one set per compiled algebra, and the launch caps the host
-// sizes the families' workspace regions by.
+// Host-visible launchers of every kernel family, one set per compiled algebra, and the launch caps and slice bounds the host
+// sizes and positions the families' workspace regions by (each unit asserts them against its kernels' own constants).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,65 +28,78 @@ CSMPN_DECLARE_ALG(n5)      // Cl(5,0)
 CSMPN_DECLARE_ALG(n5m)     // Cl(4,1): metric (1,1,1,1,-1)
 CSMPN_DECLARE_ALG(n4m)     // Cl(3,1): metric (1,1,1,-1)
 
+// ----------------------------------------------------------------------------- lane-kernel families
+// The shape a lane-kernel family serves a CEMLP launch by: channels = width of every block's output; attr = attribute
+// channels of an EGCL stage (block 0 reads channels + attr input channels in MODE_EDGE, 2 channels + attr in MODE_NODE), under
+// MODE_PLAIN the input channels of block 0.
+struct LaneShape { int mode, nblk, channels, attr; };
+// What one instantiation unit (family x algebra) exports. Both size queries return 0 for a shape the unit does not serve.
+struct LaneUnit {
+    size_t (*table_floats)(const LaneShape&);   // weight tables the launch packs into the workspace (0: the family has none)
+    // one gradient slice of a backward (per workgroup; pl: per wave), all blocks that coexist. dispatch.hip sizes the cl, cm and
+    // pq regions by it; the pl, plw and pg regions are sized by the bounds below, which those units assert against their
+    // slices: there it marks the shape as served and states the exact figure, nothing reads it for sizing
+    size_t (*slice_floats)(const LaneShape&);
+    // pack: write the weight tables first (pg, pq; plw always does). *handled = false: shape not served, nothing launched.
+    hipError_t (*launch)(const LaneShape&, bool bwd, bool pack, unsigned grid, hipStream_t st, const DevCemlp& C, const RowIO& io,
+                         float* tabs, bool* handled);
+};
+inline bool serves(const LaneUnit& u, const LaneShape& s) { return u.table_floats(s) != 0 || u.slice_floats(s) != 0; }
+// (an accessor, not an object: a namespace-scope constant would also be emitted into the device code object)
+#define CSMPN_DECLARE_LANE_UNIT(family, tag) const LaneUnit& cemlp_##family##_##tag();
+
 // (row, channel)-per-lane kernels (cemlp_cl.hpp)
 constexpr int kClMaxFwdGroups = 1024;   // 4-wave workgroups of a forward launch: four per CU (4 waves per SIMD)
-constexpr int kClMaxBwdGroups = 512;    // ... of a backward launch: two per CU; one slice of partial sums each (= kClSliceCap of cemlp_cl.hpp)
-#define CSMPN_DECLARE_CL(tag)                                                                                  \
-    bool has_cemlp_cl_##tag(int mode, int nblk, int channels, int i0);                                          \
-    size_t cemlp_cl_partial_floats_##tag(int mode, int nblk, int channels, int i0);                             \
-    hipError_t launch_cemlp_cl_##tag(int mode, int nblk, int channels, int i0, bool bwd, unsigned grid,         \
-                                     hipStream_t st, const DevCemlp& C, const RowIO& io, bool* handled);
-CSMPN_DECLARE_CL(n3)
+// ... of a backward launch: two per CU. One slice of partial sums each: the partial buffer of the cl AND the channel-MFMA
+// backwards is laid out for this many slices per block (block 1's start behind them: kClSliceCap of cemlp_cl.hpp)
+constexpr int kClMaxBwdGroups = 512;
+CSMPN_DECLARE_LANE_UNIT(cl, n3)
 
 // channel-MFMA kernels (cemlp_cm.hpp)
 constexpr int kCmMaxFwdGroups = 768;   // 4-wave workgroups of a forward launch: three per CU
 constexpr int kCmMaxBwdGroups = 256;   // ... of a backward launch (one per CU: 512 registers); one slice of partial sums each
-constexpr int kCmSliceCap = 512;       // slices the partial buffer is laid out for (block 1's start behind kCmSliceCap of block 0: = kClSliceCap)
-#define CSMPN_DECLARE_CM(tag)                                                                                  \
-    bool has_cemlp_cm_##tag(int mode, int nblk, int channels, int i0, bool bwd);                                \
-    size_t cemlp_cm_partial_floats_##tag(int mode, int nblk, int channels, int i0);                             \
-    hipError_t launch_cemlp_cm_##tag(int mode, int nblk, int channels, int i0, bool bwd, unsigned grid,         \
-                                     hipStream_t st, const DevCemlp& C, const RowIO& io, bool* handled);
-CSMPN_DECLARE_CM(n3)
+CSMPN_DECLARE_LANE_UNIT(cm, n3)
 
 // parity-lane kernels (cemlp_pl.hpp): D = 32 algebras with an odd number of generators, every block 8 output channels
 constexpr int kPlMaxBwdGroups = 256;   // one 4-wave workgroup per CU in the backward
-#define CSMPN_DECLARE_PL(tag)                                                                                 \
-    bool has_cemlp_pl_##tag(int mode, int nblk, int channels, int i0);                                         \
-    size_t cemlp_pl_slice_floats_##tag(int mode, int nblk, int channels, int i0);                              \
-    hipError_t launch_cemlp_pl_##tag(int mode, int nblk, int channels, int i0, bool bwd, unsigned grid,        \
-                                     hipStream_t st, const DevCemlp& C, const RowIO& io, bool* handled);
-CSMPN_DECLARE_PL(n5)
-CSMPN_DECLARE_PL(n5m)
+CSMPN_DECLARE_LANE_UNIT(pl, n5)
+CSMPN_DECLARE_LANE_UNIT(pl, n5m)
 
 // wide parity-lane kernels (cemlp_plw.hpp)
 constexpr int kPlwMaxGroups = 256;   // one workgroup per CU
-// floats of the rotation tables for (mode, channels, attribute channels | input channels of MODE_PLAIN, blocks); 0: shape not served
-#define CSMPN_DECLARE_PLW(tag)                                                                               \
-    size_t cemlp_plw_table_floats_##tag(int mode, int channels, int attr, int nblk);                          \
-    hipError_t launch_cemlp_plw_##tag(int mode, int channels, int attr, int nblk, bool bwd, unsigned grid,    \
-                                      hipStream_t st, const DevCemlp& C, const RowIO& io, float* tabs, bool* handled);
-CSMPN_DECLARE_PLW(n5)
-CSMPN_DECLARE_PLW(n5m)
+CSMPN_DECLARE_LANE_UNIT(plw, n5)
+CSMPN_DECLARE_LANE_UNIT(plw, n5m)
 
 // 16-row-tile MFMA-mixing kernels for D = 32 (cemlp_pg.hpp)
-// floats of the weight-fragment tables for (mode, channels, attribute channels); 0: shape not served
-#define CSMPN_DECLARE_PG(tag)                                                                                       \
-    size_t cemlp_pg_table_floats_##tag(int mode, int channels, int attr);                                            \
-    size_t cemlp_pg_slice_floats_##tag(int mode, int channels, int attr);                                            \
-    bool has_cemlp_pg_##tag(int mode, int channels, int attr, bool bwd);                                            \
-    hipError_t launch_cemlp_pg_##tag(int mode, int channels, int attr, bool bwd, bool pack, unsigned grid, hipStream_t st,      \
-                                     const DevCemlp& C, const RowIO& io, float* tabs, bool* handled);
-CSMPN_DECLARE_PG(n5)
-CSMPN_DECLARE_PG(n5m)
+constexpr int kPgGridCap = 256;      // one 8-wave workgroup per CU = gradient slices the kernels index (kPgMaxGroups of cemlp_pg.hpp)
+CSMPN_DECLARE_LANE_UNIT(pg, n5)
+CSMPN_DECLARE_LANE_UNIT(pg, n5m)
 
 // 16-row-tile MFMA-mixing kernels for Cl(3,0) at 32 channels (cemlp_pq.hpp)
-// workgroups a launch may have = gradient slices the workspace region holds (three 4-wave workgroups per CU)
+// workgroups a launch may have = gradient slices the workspace region holds (three 4-wave workgroups per CU; kPqMaxGroups of cemlp_pq.hpp)
 constexpr unsigned kPqGridCap = 768;
-// floats of the weight-fragment tables / of one workgroup's gradient slices (all blocks: each block's launch has its own region) for
-// (mode, blocks, channels, attribute channels - MODE_PLAIN: input channels of block 0); 0: shape not served
-size_t cemlp_pq_table_floats_n3(int mode, int nblk, int channels, int attr);
-size_t cemlp_pq_slice_floats_n3(int mode, int nblk, int channels, int attr);
-hipError_t launch_cemlp_pq_n3(int mode, int nblk, int channels, int attr, bool bwd, bool pack, unsigned grid, hipStream_t st, const DevCemlp& C,
-                              const RowIO& io, float* tabs, bool* handled);
+CSMPN_DECLARE_LANE_UNIT(pq, n3)
+
+// ----------------------------------------------------------------------------- the D = 32 families' region at the end of the workspace
+// Upper bounds by channel count, not the kernels' exact sizes: pl_inst.inc, plw_inst.inc and pg_inst.inc assert for every
+// shape they serve that its backward and reduce kernels stay inside them at the grid cap.
+// the 8-channel parity-lane backward (cemlp_pl.hpp): one slice per wave, 4 waves x kPlMaxBwdGroups workgroups
+constexpr size_t pl_part_bytes() { return (size_t)(8 * 768 + 2 * 640) * sizeof(float) * 4 * kPlMaxBwdGroups + 256; }
+// gradient slices of the wide parity-lane backward (one slice of weight-gradient MFMA tiles per workgroup), of the pg backward
+// (positioned and sized by the same bound) and, at 8 channels, of the parity-lane backward
+constexpr size_t plw_part_bytes(int ch) {
+    const size_t NG = (ch + 7) / 8, nch0 = 2 * NG + 1;
+    const size_t image = 8 * NG * (3 + 3 * 6 + 64) + 16;   // per-channel sums (CP x (3 + 3 G + P)), generous
+    const size_t per_cu = 4 / NG > 0 ? 4 / NG : 1;
+    const size_t bytes = ((nch0 + 2 * NG) * 12 * 64 * NG + image) * sizeof(float) * kPlwMaxGroups * per_cu + 256;
+    return ch == 8 && pl_part_bytes() > bytes ? pl_part_bytes() : bytes;
+}
+// rotation tables of the wide parity-lane kernels: both blocks at the node stage's width
+constexpr size_t plw_tables_bytes(int ch) {
+    const size_t NG = (ch + 7) / 8, nch0 = 2 * NG + 1;
+    return ((2 * NG * nch0 + 4 * NG * NG) + (2 * NG * NG + 4 * NG * NG)) * 384 * sizeof(float);
+}
+// ... from 17 channels on 64 KB more: the weight-fragment tables of cemlp_pg.hpp, carved from the same region, are up to
+// 368 KB at 28 / 32 channels
+constexpr size_t kPgTablesExtraBytes = 65536;
 }  // namespace csmpn

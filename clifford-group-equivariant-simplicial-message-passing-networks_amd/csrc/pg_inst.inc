@@ -1,83 +1,52 @@
 // 16-row-tile MFMA-mixing kernel instantiations (cemlp_pg.hpp) for one algebra. Included by k_pg_<tag>.hip with
 // CSMPN_ALG_N, CSMPN_ALG_NEG and CSMPN_ALG_TAG defined.
 #include "cemlp_pg.hpp"
-#include "launch.hpp"
+#include "launch_unit.hpp"
 
 namespace csmpn {
 namespace {
 using ALG_T = Alg<CSMPN_ALG_N, CSMPN_ALG_NEG>;
+static_assert(kPgMaxGroups == kPgGridCap, "the host caps the grid at the slices the kernels index");
 
-template <class KERN>
-hipError_t pg_enable_lds(KERN kern, size_t lds) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// block K's backward, then the fixed-order sum of its workgroups' slices
+template <class CF, int K>
+hipError_t pg_launch_bwd(unsigned grid, hipStream_t st, const DevCemlp& Cd, const RowIO& io) {
+    const hipError_t e = launch_kernel<cemlp_pg_bwd_kernel<ALG_T, CF, K>>(grid, kPgThreads, sizeof(float) * CF::bwd_lds_floats, st, Cd, io);
+    if (e != hipSuccess) return e;
+    return launch_kernel<pg_reduce_kernel<ALG_T, CF, K>>((CF::slice_floats(K) + 63) / 64, 256, 0, st, Cd, (const float*)io.slices, (int)grid);
 }
 
-template <int C, int MODE, int NA>
+template <class CF>
 hipError_t pg_launch(bool bwd, bool pack, unsigned grid, hipStream_t st, const DevCemlp& Cd, const RowIO& io_in, float* tabs) {
-    using CF = PgCfg<ALG_T, C, MODE, NA>;
+    static_assert((size_t)CF::slice_max * kPgMaxGroups * sizeof(float) <= plw_part_bytes(CF::C),
+                  "one slice per workgroup at the grid cap: inside the region the host reserves in front of the tables");
+    // At 24 channels the tables, 312 KB edge / 360 KB node, exceed the 262 KB the tail reserves for them by up to 100352 B and
+    // reach into the general kernels' front part of the workspace, which pg_eligible's fits() counts in (DESIGN.md section 6):
+    // a known gap, held at today's overshoot so that it cannot widen unnoticed.
+    constexpr size_t known_overshoot = CF::C == 24 ? 100352 : 0;
+    static_assert(CF::tab_floats * sizeof(float) <= plw_tables_bytes(CF::C) + kPgTablesExtraBytes + known_overshoot,
+                  "weight-fragment tables: inside the region the host reserves");
     RowIO io = io_in;
-    io.plw_tabs = tabs;
-    if (pack) hipLaunchKernelGGL((pg_pack_kernel<CF, ALG_T>), dim3((CF::tab_floats + 255) / 256), dim3(256), 0, st, Cd, tabs);
-    if (!bwd) {
-        auto kern = cemlp_pg_fwd_kernel<ALG_T, CF>;
-        constexpr size_t lds = sizeof(float) * CF::lds_floats;
-        hipError_t e = pg_enable_lds(kern, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kPgThreads), lds, st, Cd, io);
-        return hipGetLastError();
-    }
-    // one launch per block (last block first), each followed by the fixed-order sum of its workgroups' slices
-    constexpr size_t lds = sizeof(float) * CF::bwd_lds_floats;
-    auto k1 = cemlp_pg_bwd_kernel<ALG_T, CF, 1>;
-    hipError_t e = pg_enable_lds(k1, lds);
+    io.tabs = tabs;
+    hipError_t e = hipSuccess;
+    if (pack) e = launch_kernel<pg_pack_kernel<CF, ALG_T>>((CF::tab_floats + 255) / 256, 256, 0, st, Cd, tabs);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k1, dim3(grid), dim3(kPgThreads), lds, st, Cd, io);
-    hipLaunchKernelGGL((pg_reduce_kernel<ALG_T, CF, 1>), dim3((CF::slice_floats(1) + 63) / 64), dim3(256), 0, st, Cd, (const float*)io.plw_part, (int)grid);
-    auto k0 = cemlp_pg_bwd_kernel<ALG_T, CF, 0>;
-    e = pg_enable_lds(k0, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k0, dim3(grid), dim3(kPgThreads), lds, st, Cd, io);
-    hipLaunchKernelGGL((pg_reduce_kernel<ALG_T, CF, 0>), dim3((CF::slice_floats(0) + 63) / 64), dim3(256), 0, st, Cd, (const float*)io.plw_part, (int)grid);
-    return hipGetLastError();
+    if (!bwd) return launch_kernel<cemlp_pg_fwd_kernel<ALG_T, CF>>(grid, kPgThreads, sizeof(float) * CF::lds_floats, st, Cd, io);
+    // one launch per block (last block first), each followed by the sum of its slices: the blocks' slices take turns in one region
+    e = pg_launch_bwd<CF, 1>(grid, st, Cd, io);
+    return e != hipSuccess ? e : pg_launch_bwd<CF, 0>(grid, st, Cd, io);
 }
+
+// served shapes: 24 / 28 / 32 channels x {edge with 6 attribute channels, node with 3}
+template <int C, int MODE, int NA>
+constexpr LaneEntry pg_entry() {
+    using CF = PgCfg<ALG_T, C, MODE, NA>;
+    return {{MODE, 2, C, NA}, CF::tab_floats, CF::slice_max, pg_launch<CF>};
+}
+#define CSMPN_PG_EGCL(C) pg_entry<C, MODE_EDGE, 6>(), pg_entry<C, MODE_NODE, 3>()
+constexpr LaneEntry kShapes[] = {CSMPN_PG_EGCL(24), CSMPN_PG_EGCL(28), CSMPN_PG_EGCL(32)};
+#undef CSMPN_PG_EGCL
 }  // namespace
 
-#define CSMPN_CAT2(a, b) a##b
-#define CSMPN_CAT(a, b) CSMPN_CAT2(a, b)
-
-// served widths x {edge with 6 attribute channels, node with 3}
-#define CSMPN_PG_SHAPES(X) X(24) X(28) X(32)
-
-size_t CSMPN_CAT(cemlp_pg_table_floats_, CSMPN_ALG_TAG)(int mode, int channels, int attr) {
-#define X(CH)                                                                                                  \
-    if (channels == CH && mode == MODE_EDGE && attr == 6) return PgCfg<ALG_T, CH, MODE_EDGE, 6>::tab_floats;   \
-    if (channels == CH && mode == MODE_NODE && attr == 3) return PgCfg<ALG_T, CH, MODE_NODE, 3>::tab_floats;
-    CSMPN_PG_SHAPES(X)
-#undef X
-    return 0;
-}
-size_t CSMPN_CAT(cemlp_pg_slice_floats_, CSMPN_ALG_TAG)(int mode, int channels, int attr) {
-#define X(CH)                                                                                                  \
-    if (channels == CH && mode == MODE_EDGE && attr == 6) return PgCfg<ALG_T, CH, MODE_EDGE, 6>::slice_max;    \
-    if (channels == CH && mode == MODE_NODE && attr == 3) return PgCfg<ALG_T, CH, MODE_NODE, 3>::slice_max;
-    CSMPN_PG_SHAPES(X)
-#undef X
-    return 0;
-}
-bool CSMPN_CAT(has_cemlp_pg_, CSMPN_ALG_TAG)(int mode, int channels, int attr, bool bwd) {
-    (void)bwd;
-    return CSMPN_CAT(cemlp_pg_table_floats_, CSMPN_ALG_TAG)(mode, channels, attr) != 0;
-}
-hipError_t CSMPN_CAT(launch_cemlp_pg_, CSMPN_ALG_TAG)(int mode, int channels, int attr, bool bwd, bool pack, unsigned grid, hipStream_t st,
-                                                      const DevCemlp& C, const RowIO& io, float* tabs, bool* handled) {
-    *handled = true;
-#define X(CH)                                                                                                               \
-    if (channels == CH && mode == MODE_EDGE && attr == 6) return pg_launch<CH, MODE_EDGE, 6>(bwd, pack, grid, st, C, io, tabs);   \
-    if (channels == CH && mode == MODE_NODE && attr == 3) return pg_launch<CH, MODE_NODE, 3>(bwd, pack, grid, st, C, io, tabs);
-    CSMPN_PG_SHAPES(X)
-#undef X
-    *handled = false;
-    return hipSuccess;
-}
+const LaneUnit& CSMPN_CAT(cemlp_pg_, CSMPN_ALG_TAG)() { return LaneUnitOf<kShapes>::unit; }
 }  // namespace csmpn

@@ -28,9 +28,7 @@ AlgId alg_id(const float* metric, int n) {
 #define CSMPN_ALG_OPS(tag, N, NEG, ...)                                                                                \
     {N, 1 << N, Alg<N, NEG>::P, has_h2_##tag(), has_ps_##tag(), "csmpn::Alg<" #N ", " #NEG ">", launch_cemlp_##tag,     \
      launch_cemlp_ps_##tag, launch_cemlp_wide_##tag, launch_gp_##tag, __VA_ARGS__}
-#define CSMPN_D32_OPS(tag)                                                                                             \
-    has_cemlp_pl_##tag, launch_cemlp_pl_##tag, cemlp_plw_table_floats_##tag, launch_cemlp_plw_##tag, has_cemlp_pg_##tag, \
-        cemlp_pg_table_floats_##tag, launch_cemlp_pg_##tag
+#define CSMPN_D32_OPS(tag) &cemlp_pl_##tag(), &cemlp_plw_##tag(), &cemlp_pg_##tag()
 const AlgOps& alg_ops(AlgId id) {
     static const AlgOps ops[ALG_COUNT] = {   // in AlgId order
         CSMPN_ALG_OPS(n2, 2, 0u),

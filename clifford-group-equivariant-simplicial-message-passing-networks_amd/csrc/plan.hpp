@@ -67,16 +67,7 @@ struct AlgOps {
                                     const RowIO& io);
     hipError_t (*launch_gp)(bool bwd, const float* a, const float* b, const float* gout, float* out, float* ga, float* gb, long rows,
                             hipStream_t st);
-    bool (*has_pl)(int mode, int nblk, int channels, int i0);
-    hipError_t (*launch_pl)(int mode, int nblk, int channels, int i0, bool bwd, unsigned grid, hipStream_t st, const DevCemlp& C,
-                            const RowIO& io, bool* handled);
-    size_t (*plw_table_floats)(int mode, int channels, int attr, int nblk);
-    hipError_t (*launch_plw)(int mode, int channels, int attr, int nblk, bool bwd, unsigned grid, hipStream_t st, const DevCemlp& C,
-                             const RowIO& io, float* tabs, bool* handled);
-    bool (*has_pg)(int mode, int channels, int attr, bool bwd);
-    size_t (*pg_table_floats)(int mode, int channels, int attr);
-    hipError_t (*launch_pg)(int mode, int channels, int attr, bool bwd, bool pack, unsigned grid, hipStream_t st, const DevCemlp& C,
-                            const RowIO& io, float* tabs, bool* handled);
+    const LaneUnit *pl, *plw, *pg;   // parity-lane, wide parity-lane, 16-row-tile MFMA-mixing units
 };
 const AlgOps& alg_ops(AlgId id);
 
