@@ -616,6 +616,41 @@ class HipBackend:
             gh.data_ptr(), _ptr(g_ea), _ptr(saved), ws.data_ptr(), ws.numel(), flags, _stream(dev)))
         return g_ea, views
 
+    @staticmethod
+    @_on_device_of(2)
+    def layer_backward(spec, csr, h, agg, edge_attr, node_attr, pe, pn, gout, want_gea, want_gna, state_e=None, state_n=None,
+                       gflat_e=None, gflat_n=None, fused_e=None, fused_n=None):
+        """node_backward, then edge_backward, as ONE C-ABI call (csmpn_egcl_backward): same results, and the Cl(3,0)
+        8-channel kernels sum both stages' gradient slices in one launch behind the edge stage. Whole adjacency, no
+        deterministic request (the callers' business). Returns (gh, g_ea, g_na, views_e, views_n)."""
+        e, nd = spec.edge, spec.node
+        e.bind(pe)
+        nd.bind(pn)
+        N, D, dev = h.shape[0], nd.D, h.device
+        _fe, views_e = e.new_grads(pe, dev, gflat_e, fused_into=fused_e)
+        _fn, views_n = nd.new_grads(pn, dev, gflat_n, fused_into=fused_n)
+        gh = torch.empty_like(h)
+        g_agg = torch.empty(N, spec.O, D, dtype=torch.float32, device=dev)
+        g_na = torch.empty_like(node_attr) if (node_attr is not None and want_gna) else None
+        g_ea = torch.empty_like(edge_attr) if (edge_attr is not None and want_gea) else None
+
+        def stage(binding, state):
+            ws, saved = state if state is not None else (binding.workspace(dev), None)
+            flags = native.FLAG_WEIGHTS_PACKED if state is not None else 0
+            if getattr(saved, "csmpn_save_state", False):
+                flags |= native.FLAG_SAVE_STATE
+            return ws, saved, flags
+
+        ws_e, saved_e, fl_e = stage(e, state_e)
+        ws_n, saved_n, fl_n = stage(nd, state_n)
+        check(native.lib().csmpn_egcl_backward(
+            e.metric_arr, e.n, e.params, e.grads, e.nblk, nd.params, nd.grads, nd.nblk, h.data_ptr(), spec.C,
+            agg.data_ptr(), spec.O, _ptr(edge_attr), spec.A, _ptr(node_attr), spec.T, csr.perm.data_ptr(),
+            csr.src.data_ptr(), csr.dst.data_ptr(), csr.deg.data_ptr(), spec.mean, spec.residual, csr.n_edges, N,
+            gout.data_ptr(), gh.data_ptr(), g_agg.data_ptr(), _ptr(g_ea), _ptr(g_na), None, _ptr(saved_e),
+            ws_e.data_ptr(), ws_e.numel(), fl_e, _ptr(saved_n), ws_n.data_ptr(), ws_n.numel(), fl_n, _stream(dev)))
+        return gh, g_ea, g_na, views_e, views_n
+
 
 # CSMPN_FLAG_SAVE_STATE (round 4): the EGCL stage forwards also store every block's output in front of its layer norm and the
 # backwards read it instead of recomputing linear_left + the geometric product. Honoured by the Cl(3,0) 8-channel kernels
@@ -692,6 +727,11 @@ class _EgclFn(torch.autograd.Function):
         ctx.gflats = None   # zeroed once: a second backward through the same graph allocates afresh
         refs = ctx.param_refs
         fuse = _fusable(refs, h.device)
+        if isinstance(csr, Csr) and not deterministic_request():
+            gh, g_ea, g_na, views_e, views_n = HipBackend.layer_backward(
+                spec, csr, h, agg, edge_attr, node_attr, pe, pn, gout, ctx.needs_input_grad[1], ctx.needs_input_grad[2],
+                ctx.st_e, ctx.st_n, gfe, gfn, refs[:ne] if fuse else None, refs[ne:] if fuse else None)
+            return (gh, g_ea, g_na, None, None, *views_e, *views_n)
         gh, g_agg, g_na, views_n = HipBackend.node_backward(spec, csr.deg, h, agg, node_attr, pn, gout,
                                                             ctx.needs_input_grad[2], ctx.st_n, gfn,
                                                             fused_into=refs[ne:] if fuse else None)

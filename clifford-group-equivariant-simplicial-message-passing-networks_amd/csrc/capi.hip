@@ -316,12 +316,13 @@ int csmpn_egcl_edge_forward(const float* metric, int n, const csmpn_block_params
     return run_rows(plan, MODE_EDGE, false, io, (hipStream_t)stream, need_pack);
 }
 
-int csmpn_egcl_edge_backward(const float* metric, int n, const csmpn_block_params* blocks,
-                             const csmpn_block_grads* grads, int n_blocks, const float* h, int32_t channels,
-                             const float* edge_attr, int32_t attr_channels, const int32_t* perm,
-                             const int32_t* src_sorted, const int32_t* dst_sorted, int64_t E, int64_t N,
-                             const float* g_agg, float* gh, float* g_edge_attr, const float* saved_inputs, void* workspace,
-                             size_t workspace_bytes, uint32_t flags, void* stream) {
+// deferred: run_rows (plan.hpp)
+static int edge_backward(const float* metric, int n, const csmpn_block_params* blocks,
+                         const csmpn_block_grads* grads, int n_blocks, const float* h, int32_t channels,
+                         const float* edge_attr, int32_t attr_channels, const int32_t* perm,
+                         const int32_t* src_sorted, const int32_t* dst_sorted, int64_t E, int64_t N,
+                         const float* g_agg, float* gh, float* g_edge_attr, const float* saved_inputs, void* workspace,
+                         size_t workspace_bytes, uint32_t flags, void* stream, SliceSet* deferred) {
     const AlgId id = alg_id(metric, n);
     if (id == ALG_NONE) return fail(CSMPN_ERR_UNSUPPORTED, "metric not supported by the HIP path");
     RowIO io;
@@ -335,7 +336,17 @@ int csmpn_egcl_edge_backward(const float* metric, int n, const csmpn_block_param
     const bool need_pack = true;
     io.gy = g_agg; io.gx[0] = gh; io.gx[1] = g_edge_attr; io.saved = saved_inputs;
     (void)N;
-    return run_rows(plan, MODE_EDGE, true, io, (hipStream_t)stream, need_pack, (flags & CSMPN_FLAG_WEIGHTS_PACKED) != 0);
+    return run_rows(plan, MODE_EDGE, true, io, (hipStream_t)stream, need_pack, (flags & CSMPN_FLAG_WEIGHTS_PACKED) != 0, deferred);
+}
+
+int csmpn_egcl_edge_backward(const float* metric, int n, const csmpn_block_params* blocks,
+                             const csmpn_block_grads* grads, int n_blocks, const float* h, int32_t channels,
+                             const float* edge_attr, int32_t attr_channels, const int32_t* perm,
+                             const int32_t* src_sorted, const int32_t* dst_sorted, int64_t E, int64_t N,
+                             const float* g_agg, float* gh, float* g_edge_attr, const float* saved_inputs, void* workspace,
+                             size_t workspace_bytes, uint32_t flags, void* stream) {
+    return edge_backward(metric, n, blocks, grads, n_blocks, h, channels, edge_attr, attr_channels, perm, src_sorted, dst_sorted, E, N,
+                         g_agg, gh, g_edge_attr, saved_inputs, workspace, workspace_bytes, flags, stream, nullptr);
 }
 
 static int node_io(const csmpn_block_params* blocks, int n_blocks, const float* h, int channels, const float* agg,
@@ -377,12 +388,12 @@ int csmpn_egcl_node_forward(const float* metric, int n, const csmpn_block_params
     return run_rows(plan, MODE_NODE, false, io, (hipStream_t)stream, need_pack);
 }
 
-int csmpn_egcl_node_backward(const float* metric, int n, const csmpn_block_params* blocks,
-                             const csmpn_block_grads* grads, int n_blocks, const float* h, int32_t channels,
-                             const float* agg, int32_t agg_channels, const float* node_attr, int32_t attr_channels,
-                             const int32_t* in_degree, int32_t mean_aggr, int32_t residual, int64_t N,
-                             const float* g_out, float* gh, float* g_agg, float* g_node_attr, const float* saved_inputs, void* workspace,
-                             size_t workspace_bytes, uint32_t flags, void* stream) {
+static int node_backward(const float* metric, int n, const csmpn_block_params* blocks,
+                         const csmpn_block_grads* grads, int n_blocks, const float* h, int32_t channels,
+                         const float* agg, int32_t agg_channels, const float* node_attr, int32_t attr_channels,
+                         const int32_t* in_degree, int32_t mean_aggr, int32_t residual, int64_t N,
+                         const float* g_out, float* gh, float* g_agg, float* g_node_attr, const float* saved_inputs, void* workspace,
+                         size_t workspace_bytes, uint32_t flags, void* stream, SliceSet* deferred) {
     const AlgId id = alg_id(metric, n);
     if (id == ALG_NONE) return fail(CSMPN_ERR_UNSUPPORTED, "metric not supported by the HIP path");
     RowIO io;
@@ -399,7 +410,57 @@ int csmpn_egcl_node_backward(const float* metric, int n, const csmpn_block_param
     io.resid_bwd = residual ? 1 : 0; io.saved = saved_inputs;
     io.row_store = (flags & CSMPN_FLAG_DETERMINISTIC) ? 1 : 0;
     io.save_state = (flags & CSMPN_FLAG_SAVE_STATE) ? 1 : 0;
-    return run_rows(plan, MODE_NODE, true, io, (hipStream_t)stream, need_pack, (flags & CSMPN_FLAG_WEIGHTS_PACKED) != 0);
+    return run_rows(plan, MODE_NODE, true, io, (hipStream_t)stream, need_pack, (flags & CSMPN_FLAG_WEIGHTS_PACKED) != 0, deferred);
+}
+
+int csmpn_egcl_node_backward(const float* metric, int n, const csmpn_block_params* blocks,
+                             const csmpn_block_grads* grads, int n_blocks, const float* h, int32_t channels,
+                             const float* agg, int32_t agg_channels, const float* node_attr, int32_t attr_channels,
+                             const int32_t* in_degree, int32_t mean_aggr, int32_t residual, int64_t N,
+                             const float* g_out, float* gh, float* g_agg, float* g_node_attr, const float* saved_inputs, void* workspace,
+                             size_t workspace_bytes, uint32_t flags, void* stream) {
+    return node_backward(metric, n, blocks, grads, n_blocks, h, channels, agg, agg_channels, node_attr, attr_channels, in_degree, mean_aggr,
+                         residual, N, g_out, gh, g_agg, g_node_attr, saved_inputs, workspace, workspace_bytes, flags, stream, nullptr);
+}
+
+// Both backwards of one layer. Where both stages end in a slice sum their unit can defer (LaneUnit::sum_slices: the
+// (row, channel)-per-lane family), the node program's sum does not run in front of the edge backward, which needs only g_agg
+// and gh: one launch behind the edge backward sums both programs' slices. The node workspace holds the node slices until
+// then: nothing between the two stages touches it. Every other pair of families, and the deterministic mode: the two
+// stages exactly as the separate entry points run them.
+int csmpn_egcl_backward(const float* metric, int n, const csmpn_block_params* edge_blocks, const csmpn_block_grads* edge_grads,
+                        int n_edge_blocks, const csmpn_block_params* node_blocks, const csmpn_block_grads* node_grads,
+                        int n_node_blocks, const float* h, int32_t channels, const float* agg, int32_t agg_channels,
+                        const float* edge_attr, int32_t edge_attr_channels, const float* node_attr, int32_t node_attr_channels,
+                        const int32_t* perm, const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* in_degree,
+                        int32_t mean_aggr, int32_t residual, int64_t E, int64_t N, const float* g_out, float* gh, float* g_agg,
+                        float* g_edge_attr, float* g_node_attr, float* g_edge_rows, const float* edge_saved, void* edge_workspace,
+                        size_t edge_workspace_bytes, uint32_t edge_flags, const float* node_saved, void* node_workspace,
+                        size_t node_workspace_bytes, uint32_t node_flags, void* stream) {
+    const bool det = ((edge_flags | node_flags) & CSMPN_FLAG_DETERMINISTIC) != 0;
+    if ((edge_flags & CSMPN_FLAG_DETERMINISTIC) && !g_edge_rows)
+        return fail(CSMPN_ERR_INVALID, "CSMPN_FLAG_DETERMINISTIC: g_edge_rows ([E, C, D], csmpn_egcl_edge_backward's gh) is null");
+    // the node slices wait in the node workspace while the edge backward runs: only if that one works elsewhere
+    const char *we = static_cast<const char*>(edge_workspace), *wn = static_cast<const char*>(node_workspace);
+    const bool apart = we && wn && (we + edge_workspace_bytes <= wn || wn + node_workspace_bytes <= we);
+    SliceSet node_set, edge_set;
+    node_set.unit = edge_set.unit = nullptr;
+    const bool defer = !det && apart;
+    int rc = node_backward(metric, n, node_blocks, node_grads, n_node_blocks, h, channels, agg, agg_channels, node_attr,
+                           node_attr_channels, in_degree, mean_aggr, residual, N, g_out, gh, g_agg, g_node_attr, node_saved,
+                           node_workspace, node_workspace_bytes, node_flags, stream, defer ? &node_set : nullptr);
+    if (rc) return rc;
+    // (a node stage that deferred nothing: the edge stage sums for itself as ever)
+    rc = edge_backward(metric, n, edge_blocks, edge_grads, n_edge_blocks, h, channels, edge_attr, edge_attr_channels, perm, src_sorted,
+                       dst_sorted, E, N, g_agg, (edge_flags & CSMPN_FLAG_DETERMINISTIC) ? g_edge_rows : gh, g_edge_attr, edge_saved,
+                       edge_workspace, edge_workspace_bytes, edge_flags, stream, node_set.unit ? &edge_set : nullptr);
+    if (node_set.unit) {
+        // owed whatever became of the edge stage: the node gradients are complete when this entry returns without a HIP error
+        const SliceSet* const other = (!rc && edge_set.unit == node_set.unit) ? &edge_set : nullptr;
+        HIP_TRY(node_set.unit->sum_slices(node_set, other, (hipStream_t)stream));
+        if (!rc && edge_set.unit && !other) HIP_TRY(edge_set.unit->sum_slices(edge_set, nullptr, (hipStream_t)stream));
+    }
+    return rc;
 }
 
 }  // extern "C"

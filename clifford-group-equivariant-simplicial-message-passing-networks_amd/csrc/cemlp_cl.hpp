@@ -1333,15 +1333,15 @@ __global__ void __launch_bounds__(64 * kClWaves, 2) cemlp_cl_bwd_kernel(const De
 // The slices of block 1 start slice_cap * (slice length of block 0) floats behind those of block 0. A workgroup takes 16
 // consecutive elements (64-byte pieces of every slice); thread (j = tid & 15, w = tid >> 4) adds the slices w, w + 16,
 // ... sixteen loads in flight at a time; the 16 partial sums of an element meet in LDS and are added in order.
+// `group`: the workgroup's index within this backward's element range (the launch may hold the ranges of two backwards).
 template <class ALG, int C, int I0, int NBLK>
-__global__ void __launch_bounds__(256) cl_reduce_kernel(const DevCemlp Cd, const float* part, int nslices, int slice_cap) {
+CSMPN_DEV void cl_reduce_group(const DevCemlp& Cd, const float* part, int nslices, int slice_cap, int group, float (*red)[17]) {
     constexpr int G = ALG::G;
     using P0 = ClPart<ALG, C, I0>;
     using P1 = ClPart<ALG, C, C>;
     constexpr int total = P0::total + (NBLK > 1 ? P1::total : 0);
-    __shared__ float red[16][17];
     const int j = threadIdx.x & 15, w = threadIdx.x >> 4;
-    int e = blockIdx.x * 16 + j;
+    int e = group * 16 + j;
     const bool live = e < total;
     if (!live) e = 0;
     const int k = (NBLK > 1 && e >= P0::total) ? 1 : 0;
@@ -1383,6 +1383,24 @@ __global__ void __launch_bounds__(256) cl_reduce_kernel(const DevCemlp Cd, const
         else dst = B.gla + (f - P0::qla);
     }
     if (dst) *dst += s;
+}
+template <class ALG, int C, int I0, int NBLK>
+constexpr int cl_reduce_groups() { return (ClPart<ALG, C, I0>::total + (NBLK > 1 ? ClPart<ALG, C, C>::total : 0) + 15) / 16; }
+template <class ALG, int C, int I0, int NBLK>
+__global__ void __launch_bounds__(256) cl_reduce_kernel(const DevCemlp Cd, const float* part, int nslices, int slice_cap) {
+    __shared__ float red[16][17];
+    cl_reduce_group<ALG, C, I0, NBLK>(Cd, part, nslices, slice_cap, blockIdx.x, red);
+}
+// The slice sums of TWO backwards in one launch (csmpn_egcl_backward: the node program's sum, deferred, beside the edge
+// program's): the first cl_reduce_groups<A> workgroups take backward A's elements, the rest backward B's. Every element is
+// summed exactly as cl_reduce_kernel sums it; the two ranges touch disjoint slices and gradient tensors.
+template <class ALG, int C, int I0A, int NBLKA, int I0B, int NBLKB>
+__global__ void __launch_bounds__(256) cl_reduce2_kernel(const DevCemlp CdA, const float* partA, int nslicesA, const DevCemlp CdB,
+                                                         const float* partB, int nslicesB, int slice_cap) {
+    __shared__ float red[16][17];
+    constexpr int groupsA = cl_reduce_groups<ALG, C, I0A, NBLKA>();
+    if ((int)blockIdx.x < groupsA) cl_reduce_group<ALG, C, I0A, NBLKA>(CdA, partA, nslicesA, slice_cap, blockIdx.x, red);
+    else cl_reduce_group<ALG, C, I0B, NBLKB>(CdB, partB, nslicesB, slice_cap, (int)blockIdx.x - groupsA, red);
 }
 
 }  // namespace csmpn

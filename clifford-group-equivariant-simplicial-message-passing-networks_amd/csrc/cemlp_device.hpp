@@ -113,7 +113,7 @@ struct RowIO {
     const float* gy;        // PLAIN/NODE: [rows, O, D]; EDGE: g_agg [N, O, D] gathered by dst
     float* gx[3];           // per segment gradient target (nullable)
     int resid_bwd;          // NODE: add gy to gx[0]
-    int pad2_;
+    int defer_sum;          // host side only: a backward launcher whose unit has sum_slices (launch.hpp) leaves its slice sum to the caller
     // inputs of blocks 1..nblk-1 ([rows, O_{k-1}, D] each, back to back): written by the
     // forward when non-null, read by the backward instead of recomputing the earlier blocks
     float* save;

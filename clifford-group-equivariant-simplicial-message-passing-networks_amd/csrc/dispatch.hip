@@ -394,7 +394,9 @@ bool plw_serves(const Plan& plan, int mode, bool bwd, const RowIO& io) {
     return plw_eligible(make_launch(plan, mode, bwd, false, io, nullptr), io);
 }
 
-int run_rows(const Plan& plan, int mode, bool bwd, const RowIO& io_in, hipStream_t st, bool need_pack, bool tables_ready) {
+int run_rows(const Plan& plan, int mode, bool bwd, const RowIO& io_in, hipStream_t st, bool need_pack, bool tables_ready,
+             SliceSet* deferred) {
+    if (deferred) deferred->unit = nullptr;
     if (io_in.rows <= 0) return CSMPN_OK;
     const AlgOps& A = alg_ops(plan.id);
     RowIO io = io_in;
@@ -413,9 +415,12 @@ int run_rows(const Plan& plan, int mode, bool bwd, const RowIO& io_in, hipStream
         if (rc) return rc;
         if (sw().debug) debug_line(F, x, grid, io.rows);
         bool handled = false;
+        const LaneUnit* const unit = F.unit(A);
+        io.defer_sum = (bwd && deferred && unit->sum_slices && io.rl_partials) ? 1 : 0;
         // the 16-row-tile families' weight tables: packed unless the stage's forward left them in this workspace
-        HIP_TRY(F.unit(A)->launch(lane_shape(x), bwd, !(bwd && tables_ready), grid, st, plan.C, io, tabs, &handled));
+        HIP_TRY(unit->launch(lane_shape(x), bwd, !(bwd && tables_ready), grid, st, plan.C, io, tabs, &handled));
         if (handled) {
+            if (io.defer_sum) *deferred = SliceSet{unit, lane_shape(x), plan.C, io.rl_partials, grid};
             F.kernel_label(x, io);
             return CSMPN_OK;
         }

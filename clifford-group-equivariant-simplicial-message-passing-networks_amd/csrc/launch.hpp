@@ -33,6 +33,16 @@ CSMPN_DECLARE_ALG(n4m)     // Cl(3,1): metric (1,1,1,-1)
 // channels of an EGCL stage (block 0 reads channels + attr input channels in MODE_EDGE, 2 channels + attr in MODE_NODE), under
 // MODE_PLAIN the input channels of block 0.
 struct LaneShape { int mode, nblk, channels, attr; };
+// The slices a backward launched with RowIO::defer_sum left unsummed: its shape, gradient pointers (C), slice region and
+// the slices it wrote (= workgroups of the launch). run_rows fills it; the caller owns the region until sum_slices has run.
+struct LaneUnit;
+struct SliceSet {
+    const LaneUnit* unit;   // null: nothing deferred (the launch left complete gradients)
+    LaneShape shape;
+    DevCemlp C;
+    const float* part;
+    unsigned nslices;
+};
 // What one instantiation unit (family x algebra) exports. Both size queries return 0 for a shape the unit does not serve.
 struct LaneUnit {
     size_t (*table_floats)(const LaneShape&);   // weight tables the launch packs into the workspace (0: the family has none)
@@ -43,6 +53,10 @@ struct LaneUnit {
     // pack: write the weight tables first (pg, pq; plw always does). *handled = false: shape not served, nothing launched.
     hipError_t (*launch)(const LaneShape&, bool bwd, bool pack, unsigned grid, hipStream_t st, const DevCemlp& C, const RowIO& io,
                          float* tabs, bool* handled);
+    // null: the unit's backwards always sum their slices themselves (they ignore RowIO::defer_sum). Else: grads += the
+    // slices of `a` and, if non-null, of `b` (another backward of this unit), in ONE launch where the unit has the pair's
+    // kernel; every element summed as the backward's own last kernel would have summed it.
+    hipError_t (*sum_slices)(const SliceSet& a, const SliceSet* b, hipStream_t st);
 };
 inline bool serves(const LaneUnit& u, const LaneShape& s) { return u.table_floats(s) != 0 || u.slice_floats(s) != 0; }
 // (an accessor, not an object: a namespace-scope constant would also be emitted into the device code object)

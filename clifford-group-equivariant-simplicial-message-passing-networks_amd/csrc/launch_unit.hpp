@@ -40,7 +40,7 @@ struct LaneEntry {
 };
 
 // The LaneUnit of a unit's shape table: every query and the launch look the shape up in that one table.
-template <const auto& Table>
+template <const auto& Table, hipError_t (*SumSlices)(const SliceSet&, const SliceSet*, hipStream_t) = nullptr>
 struct LaneUnitOf {
     static const LaneEntry* find(const LaneShape& s) {
         for (const LaneEntry& e : Table)
@@ -62,6 +62,6 @@ struct LaneUnitOf {
         *handled = e != nullptr;
         return e ? e->launch(bwd, pack, grid, st, C, io, tabs) : hipSuccess;
     }
-    static constexpr LaneUnit unit{table_floats, slice_floats, launch};
+    static constexpr LaneUnit unit{table_floats, slice_floats, launch, SumSlices};
 };
 }  // namespace csmpn

@@ -141,7 +141,10 @@ size_t family_tail_bytes(int n, const csmpn_block_params* blocks, int nblk);   /
 
 // tables_ready: CSMPN_FLAG_WEIGHTS_PACKED on a backward entry point - the weight-fragment tables of the 16-row-tile families,
 // written by the stage's forward into the same workspace, are still there and the backward does not pack again.
-int run_rows(const Plan& plan, int mode, bool bwd, const RowIO& io_in, hipStream_t st, bool need_pack, bool tables_ready = false);
+// deferred (a backward; may be null): where the family's unit can leave its slice sum to the caller (LaneUnit::sum_slices) it
+// does, and *deferred says what is left to sum; deferred->unit stays null where the launch left complete gradients.
+int run_rows(const Plan& plan, int mode, bool bwd, const RowIO& io_in, hipStream_t st, bool need_pack, bool tables_ready = false,
+             SliceSet* deferred = nullptr);
 // the fused embedding is served by the wide parity-lane kernels only
 bool plw_serves(const Plan& plan, int mode, bool bwd, const RowIO& io);
 

@@ -297,6 +297,29 @@ int csmpn_egcl_node_backward(const float* metric_host, int n, const csmpn_block_
                              int32_t residual, int64_t n_nodes, const float* g_out, float* gh, float* g_agg,
                              float* g_node_attr, const float* saved_inputs, void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
 
+/* The whole backward of one EGCL layer: csmpn_egcl_node_backward, then csmpn_egcl_edge_backward on the same stream, with
+ * the arguments the two take between them (g_agg and gh are the hand-over between the stages: g_agg [N,O,D] is overwritten
+ * by the node stage and read by the edge stage, gh [N,C,D] is overwritten by the node stage and accumulated into by the edge
+ * stage). Results are bit-identical to the two separate calls. Each stage has its own saved buffer, workspace and flags
+ * (CSMPN_FLAG_WEIGHTS_PACKED, CSMPN_FLAG_SAVE_STATE as on the separate entry points).
+ * Where both stages end with a sum over per-workgroup gradient slices (the Cl(3,0) 8-channel kernels), the node stage's sum
+ * is not launched in front of the edge stage: one launch behind it sums both stages' slices, every element in the order
+ * the separate calls use. For that the two workspaces must not overlap (the node slices wait in the node workspace; with
+ * overlapping workspaces the stages run as the separate calls do), and nothing else may write the node workspace on
+ * another stream during the call. Every other shape, and CSMPN_FLAG_DETERMINISTIC on either stage: the two stages as
+ * the separate entry points run them; with the flag on the edge stage, g_edge_rows is that stage's [E,C,D] per-edge table
+ * (csmpn_egcl_edge_backward's gh in that mode), else it is unused and may be NULL. */
+int csmpn_egcl_backward(const float* metric_host, int n, const csmpn_block_params* edge_blocks,
+                        const csmpn_block_grads* edge_grads, int n_edge_blocks, const csmpn_block_params* node_blocks,
+                        const csmpn_block_grads* node_grads, int n_node_blocks, const float* h, int32_t channels,
+                        const float* agg, int32_t agg_channels, const float* edge_attr, int32_t edge_attr_channels,
+                        const float* node_attr, int32_t node_attr_channels, const int32_t* perm, const int32_t* src_sorted,
+                        const int32_t* dst_sorted, const int32_t* in_degree, int32_t mean_aggr, int32_t residual,
+                        int64_t n_edges, int64_t n_nodes, const float* g_out, float* gh, float* g_agg, float* g_edge_attr,
+                        float* g_node_attr, float* g_edge_rows, const float* edge_saved_inputs, void* edge_workspace,
+                        size_t edge_workspace_bytes, uint32_t edge_flags, const float* node_saved_inputs, void* node_workspace,
+                        size_t node_workspace_bytes, uint32_t node_flags, void* stream);
+
 /* Input rows of the simplex feature embedding (hulls_cssmpnn.py:96-125, md17_cssmpnn.py:85-120):
  * row r lists verts_per_row vertices (rows of the per-simplex feature tensors) in ONE vertex order;
  * block b contributes verts_per_row * channels_b channels (vertex by vertex), embedded at its grade:
