@@ -23,7 +23,8 @@
 //    r0 = r0' (half of the tile, the other half is discarded). One MFMA per (matrix, blade), no LDS transposition,
 //    accumulators (4 grades x f4 per matrix) persistent over the tile loop.
 //  * per-channel parameter gradients are lane-private running sums in LDS (the lane's channel is fixed; ClSums);
-//    the sum over the rows of a wave happens ONCE per block, at its end.
+//    the sum over the rows of the WORKGROUP happens once per block, at its end, behind the barrier the end phase has anyway:
+//    owner threads read the 32 sums of a channel (4 waves x 8 rows) where they lie and write the slice's entry.
 //  * the backward is ONE launch for all blocks, run block by block (last block first): 48-80 accumulator registers +
 //    35 running sums are alive per block instead of both blocks' at once; d/d(block input) rows travel through a
 //    [rows, C, D] region behind the saved block inputs (through L2: a wave reads in block k - 1 what it wrote itself
@@ -150,10 +151,6 @@ CSMPN_DEV void cl_pin(f4 (&w)[NK]) {
 template <int C, int NROT, int TOFF, int BATCH = 4>
 CSMPN_DEV void cl_mix(float (&acc)[8], const float (&x)[8], const float* ldsw) {
     static_assert(NROT % BATCH == 0, "whole batches");
-#ifdef CL_X_NOMIX   // timing experiment only (results wrong): rotation 0 alone
-    cl_fmac8<0>(acc, x, ld4(ldsw + TOFF));
-    return;
-#endif
     constexpr int NB = NROT / BATCH;
     f4 w[BATCH];
 #pragma unroll
@@ -666,11 +663,6 @@ CSMPN_DEV void cl_st8(float* p, const float (&x)[8]) {
     st4(p, f4{x[0], x[1], x[2], x[3]});
     st4(p + 4, f4{x[4], x[5], x[6], x[7]});
 }
-#ifdef CL_X_NOOUT   // timing experiment only (results wrong): row stores go to the wave's LDS scratch
-#define CL_GST8(gp, lp, x) cl_st8(lp, x)
-#else
-#define CL_GST8(gp, lp, x) cl_st8(gp, x)
-#endif
 
 // Rows of a staged tile [RPW][ROWLEN + 4] -> atomic adds into table rows of ROWLEN floats; lane = column. The row
 // targets travel through SGPRs (v_readlane of the channel-0 lane of the row). Adds the rows to table[t_add[row]] (rows
@@ -685,11 +677,7 @@ CSMPN_DEV void cl_scatter(const float* sc, int t_add, int t_sub, float* table, i
         const int colx = 64 * cc + lane;
         const float* col = sc + colx;
         auto flush = [&](int target, float a) {
-#ifndef CL_X_NOOUT   // timing experiment only (results wrong): no atomics
             if (target >= 0) atomicAdd(table + (size_t)target * ROWLEN + colx, a);
-#else
-            if (target == -12345) atomicAdd(table + (size_t)target * ROWLEN + colx, a);
-#endif
         };
         float val[RPW];
 #pragma unroll
@@ -899,11 +887,11 @@ __global__ void __launch_bounds__(64 * kClWaves, 4) cemlp_cl_fwd_kernel(const De
         raw.template issue<T0>(io, T, c);
         Tn.template load<NA>(io, tile + 2 * tstride, r);
         if constexpr (NBLK > 1) {
-            if (io.save && Tc.valid) CL_GST8(io.save + (size_t)Tc.row * ROW + c * D, sc + r * SS + c * D, in1);
+            if (io.save && Tc.valid) cl_st8(io.save + (size_t)Tc.row * ROW + c * D, in1);
         }
         if constexpr (MODE == MODE_EDGE) {
             if (io.row_store) {
-                if (Tc.valid) CL_GST8(io.agg + (size_t)Tc.lrow * ROW + c * D, sc + r * SS + c * D, out);
+                if (Tc.valid) cl_st8(io.agg + (size_t)Tc.lrow * ROW + c * D, out);
             } else {
                 CL_LDS_ORDER();
                 cl_st8(sc + r * SS + c * D, out);
@@ -916,7 +904,7 @@ __global__ void __launch_bounds__(64 * kClWaves, 4) cemlp_cl_fwd_kernel(const De
 #pragma unroll
                 for (int d = 0; d < D; ++d) out[d] += res[d];
             }
-            CL_GST8(io.y + (size_t)Tc.row * ROW + c * D, sc + r * SS + c * D, out);
+            cl_st8(io.y + (size_t)Tc.row * ROW + c * D, out);
         }
         stamp(14);
     }
@@ -1108,7 +1096,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
             if constexpr (single) {
                 carry_a = f4{gx[0], gx[1], gx[2], gx[3]}; carry_b = f4{gx[4], gx[5], gx[6], gx[7]};
             } else if (Tc.valid) {
-                CL_GST8(io.handover + (size_t)Tc.row * ROW + c * D, sc + r * SS + c * D, gx);
+                cl_st8(io.handover + (size_t)Tc.row * ROW + c * D, gx);
             }
         } else if constexpr (MODE == MODE_EDGE) {
             if (io.gx[0]) {
@@ -1117,7 +1105,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
                 for (int d = 0; d < D; ++d) gx[d] = 0.f;
                 cl_mix<C, C, TB::W1T(0)>(gx, gy, ldsw);
                 if (io.row_store) {
-                    if (Tc.valid) CL_GST8(io.gx[0] + (size_t)Tc.lrow * ROW + c * D, sc + r * SS + c * D, gx);
+                    if (Tc.valid) cl_st8(io.gx[0] + (size_t)Tc.lrow * ROW + c * D, gx);
                 } else {
                     CL_LDS_ORDER();
                     cl_st8(sc + r * SS + c * D, gx);
@@ -1131,7 +1119,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
 #pragma unroll
                     for (int d = 0; d < D; ++d) gx[d] = 0.f;
                     cl_mix<C, C, TB::W1T(1)>(gx, gy, ldsw);
-                    if (Tc.valid && c < NA) CL_GST8(io.gx[1] + (size_t)Tc.i_perm * (NA * D) + c * D, sc + r * SS + c * D, gx);
+                    if (Tc.valid && c < NA) cl_st8(io.gx[1] + (size_t)Tc.i_perm * (NA * D) + c * D, gx);
                 }
             }
         } else {
@@ -1150,7 +1138,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
 #pragma unroll
                         for (int d = 0; d < D; ++d) gx[d] += res[d];
                     }
-                    CL_GST8(io.gx[0] + (size_t)Tc.row * ROW + c * D, sc + r * SS + c * D, gx);
+                    cl_st8(io.gx[0] + (size_t)Tc.row * ROW + c * D, gx);
                 }
             }
             if (io.gx[1]) {
@@ -1160,7 +1148,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
                 cl_mix<C, C, TB::W1T(1)>(gx, gy, ldsw);
 #pragma unroll
                 for (int d = 0; d < D; ++d) gx[d] *= Tc.scale();
-                if (Tc.valid) CL_GST8(io.gx[1] + (size_t)Tc.row * ROW + c * D, sc + r * SS + c * D, gx);
+                if (Tc.valid) cl_st8(io.gx[1] + (size_t)Tc.row * ROW + c * D, gx);
             }
             if constexpr (NA > 0) {
                 if (io.gx[2]) {
@@ -1168,7 +1156,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
 #pragma unroll
                     for (int d = 0; d < D; ++d) gx[d] = 0.f;
                     cl_mix<C, C, TB::W1T(2)>(gx, gy, ldsw);
-                    if (Tc.valid && c < NA) CL_GST8(io.gx[2] + (size_t)Tc.row * (NA * D) + c * D, sc + r * SS + c * D, gx);
+                    if (Tc.valid && c < NA) cl_st8(io.gx[2] + (size_t)Tc.row * (NA * D) + c * D, gx);
                 }
             }
         }
@@ -1178,37 +1166,33 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
     // one tile per wave: block K - 1 works on the same tile; its rows travel during this block's end phase
     if constexpr (K > 0 && single) next.template request<K - 1>(io, T0, c);
 
-#ifdef CL_X_NOEND   // timing experiment only (results wrong): the sums are kept alive, nothing else
-    {
-        f4 t = accR[0] + accL[0];
-#pragma unroll
-        for (int g = 0; g < G; ++g) { t += accR[g] + accL[g];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) t += accW1[p][g]; }
-        st4(sc + 4 * lane, t);
-    }
-    if (false)
-#endif
-    // ---- end of the launch: this wave's sums -> image of the slice in its scratch; the workgroup adds its four
-    // images in wave order and writes its slice (coalesced 16-byte stores)
+    // ---- end of the block: the weight-gradient tiles of this wave -> image of the slice in its scratch; behind ONE barrier
+    // the workgroup adds its four images in wave order and writes the matrices of its slice (coalesced 16-byte stores),
+    // and owner threads add the lane-private running sums of the whole workgroup into the slice's per-channel part.
     {
         float* img = sc;
         const int j = lane & 15, q = lane >> 4;
         // MFMA tiles. C = 8: tile element (i = 4q + v, j) = (o = i >> 1, r0 = i & 1) x (c = j >> 1, r0' = j & 1); the
-        // wanted sum is on r0 = r0': even lanes take v = 0, 2 of their own and v = 1, 3 of their odd neighbour.
-        auto put_tile = [&](const f4 (&acc)[G], int base, int I, int coff, int width) {
+        // wanted sum is on r0 = r0': even lanes take v = 0, 2 of their own and v = 1, 3 of their odd neighbour. The pair
+        // adds of ALL matrices are issued before the first store: one exec switch for all image stores of the wave.
+        constexpr int NM = NP + 2;
+        f4 lo[NM], hi[NM];
+        auto pair_tile = [&](const f4 (&acc)[G], int m) {
             if constexpr (C == 8) {
-                float lo[G], hi[G];
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
-                    lo[g] = acc[g][0] + dpp_mov<0xB1>(acc[g][1]);   // quad_perm [1,0,3,2]: the odd neighbour's value
-                    hi[g] = acc[g][2] + dpp_mov<0xB1>(acc[g][3]);
+                    lo[m][g] = acc[g][0] + dpp_mov<0xB1>(acc[g][1]);   // quad_perm [1,0,3,2]: the odd neighbour's value
+                    hi[m][g] = acc[g][2] + dpp_mov<0xB1>(acc[g][3]);
                 }
+            }
+        };
+        auto put_tile = [&](const f4 (&acc)[G], int m, int base, int I, int coff, int width) {
+            if constexpr (C == 8) {
                 const int cc = j >> 1;
                 if ((j & 1) == 0 && cc < width) {
                     float* p0 = img + base + ((2 * q) * I + coff + cc) * G;
-                    st4(p0, f4{lo[0], lo[1], lo[2], lo[3]});
-                    st4(p0 + I * G, f4{hi[0], hi[1], hi[2], hi[3]});
+                    st4(p0, lo[m]);
+                    st4(p0 + I * G, hi[m]);
                 }
             } else {
                 if (j < width) {
@@ -1220,30 +1204,62 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
                 }
             }
         };
-        static_for<0, NP>([&](auto p) { put_tile(accW1[p], 0, TB::I, TB::coff(p), TB::width(p)); });
-        put_tile(accR, PT::pWR, C, 0, C);
-        put_tile(accL, PT::pWL, C, 0, C);
-        // per-channel sums over the rows of the wave: one MFMA with A = 1 adds the lane bits 4-5 (every lane receives
-        // its column's sum), one DPP add the interleaved row pair (C = 8)
-        f4 sv[ClSums<RM::n>::kGroups];
+        static_for<0, NP>([&](auto p) { pair_tile(accW1[p], p); });
+        pair_tile(accR, NP);
+        pair_tile(accL, NP + 1);
+        if constexpr (C == 8) {
 #pragma unroll
-        for (int gq = 0; gq < ClSums<RM::n>::kGroups; ++gq) sv[gq] = ld4(sm.base + gq * (4 * 64 * kClWaves));
-        static_for<0, RM::n>([&](auto idx) {
-            const f4 t = __builtin_amdgcn_mfma_f32_16x16x4f32(1.0f, sv[idx / 4][idx % 4], f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-            float s = t[0];
-            if constexpr (C == 8) s += dpp_mov<0xB1>(s);
-            if (q == 0 && (C == 16 || (lane & 1) == 0)) img[PT::pS + PT::off(idx) + c * PT::stride(idx)] = s;
-        });
+            for (int m = 0; m < NM; ++m) asm volatile("" : "+v"(lo[m]), "+v"(hi[m]) : : "memory");
+        }
+        static_for<0, NP>([&](auto p) { put_tile(accW1[p], p, 0, TB::I, TB::coff(p), TB::width(p)); });
+        put_tile(accR, NP, PT::pWR, C, 0, C);
+        put_tile(accL, NP + 1, PT::pWL, C, 0, C);
         stamp(21);
+        // every wave's image and every thread's running sums are in LDS behind this barrier (a wave without a tile and the
+        // rows behind the last valid one left exact zeros: the sums are zeroed at the top of the block, gout is 0 there)
         __syncthreads();
         stamp(22);
-        if constexpr (K == 1 && single) next.arrived0();
         // block k's slices start behind those of the blocks 0 .. k - 1 (kClSliceCap slices each)
         float* part = io.rl_partials + (K == 0 ? 0 : (size_t)kClSliceCap * ClPart<ALG, C, ClTab<C, MODE, NA, 0, true>::I>::total) +
                       (size_t)blockIdx.x * PT::total;
+        // Per-channel sums. The running sums stay where the tile loop kept them: [group of 4][thread] f4, thread = wave * 64 +
+        // lane, lane = (row, channel). Output (channel oc, group og) = the f4 sum over the kClWaves * RPW (32) threads of
+        // channel oc. Two neighbouring threads own one output: thread `par` adds the rows of parity par, waves 0 .. 3 and
+        // rows par, par + 2, .. in that order (16 independent ds_read_b128: the 16 lanes of 8 channels x 2 parities read 256
+        // consecutive bytes), one DPP add joins the pair. The order is fixed: the sums are bit-identical from run to run.
+        constexpr int KG = ClSums<RM::n>::kGroups, GS = 4 * 64 * kClWaves, HR = RPW / 2;
+        static_assert(2 * C * KG <= 64 * kClWaves, "one pair of owner threads per (channel, group of four sums)");
+        const int par = threadIdx.x & 1, own = threadIdx.x >> 1, oc = own % C, og = own / C;
+        f4 s = f4{0.f, 0.f, 0.f, 0.f};
+        if (own < C * KG) {
+            const float* src = work + kClWaves * scratch + og * GS + 4 * (MP::lane_of_row(par) + oc * MP::ROTL);
+            f4 v[kClWaves * HR];
+#pragma unroll
+            for (int w = 0; w < kClWaves; ++w) {
+#pragma unroll
+                for (int rh = 0; rh < HR; ++rh) v[w * HR + rh] = ld4(src + 4 * (w * 64 + MP::lane_of_row(2 * rh)));
+            }
+            s = v[0];
+#pragma unroll
+            for (int i = 1; i < kClWaves * HR; ++i) s += v[i];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s[i] += dpp_mov<0xB1>(s[i]);   // the other parity's rows (both lanes: the same sum)
+        }
+        // block 0's rows are taken here: they had the tile images, the barrier and the sums to travel, and no store of this
+        // end phase is in front of them
+        if constexpr (K == 1 && single) next.arrived0();
+        if (own < C * KG) {   // the pair's four values: the even thread stores 0 and 1, the odd one 2 and 3
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int idx = 4 * og + 2 * par + i;
+                const float val = par ? s[2 + i] : s[i];
+                if (idx < RM::n) part[PT::pS + PT::off(idx) + oc * PT::stride(idx)] = val;
+            }
+        }
+        // the matrices: four images -> slice
         const float* img0 = work;
-        static_assert(PT::total % 4 == 0, "slice length");
-        for (int e = 4 * threadIdx.x; e < PT::total; e += 4 * 64 * kClWaves) {
+        static_assert(PT::pS % 4 == 0, "matrix part of the slice");
+        for (int e = 4 * threadIdx.x; e < PT::pS; e += 4 * 64 * kClWaves) {
             f4 v = ld4(img0 + e);
 #pragma unroll
             for (int w = 1; w < kClWaves; ++w) v += ld4(img0 + w * scratch + e);

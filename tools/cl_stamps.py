@@ -19,8 +19,8 @@ FWD = ["setup(stage tables)", "loads(wait)", "W1 mix b0", "silu b0", "linR/L b0"
        "W1 mix b1", "silu b1", "linR/L b1", "norm b1", "gp b1", "layernorm b1", "store/scatter"]
 BWD = ["setup(stage tables)", "loads(wait)", "r:W1 mix", "r:silu", "r:linR/L", "r:norm", "r:gp", "r:layernorm",
        "b:layernorm", "b:linL^T", "b:gp", "b:norm", "b:linR^T", "b:wgradRL(mfma)", "b:silu", "b:wgradW1(mfma)",
-       "b:W1^T+store/scatter", "end: image add + slice store", "between blocks: store drain", "between blocks: barrier",
-       "tile indices + row requests", "end: sums -> wave image", "end: barrier"]
+       "b:W1^T+store/scatter", "end: channel sums + image add + slice store", "between blocks: store drain", "between blocks: barrier",
+       "tile indices + row requests", "end: tiles -> wave image", "end: barrier"]
 
 CM_FWD = ["setup(stage tables)", "loads(wait)", "W1 mix b0", "silu b0", "linR/L b0", "norm+gp b0", "layernorm b0", "", "W1 mix b1",
           "silu b1", "linR/L b1", "norm+gp b1", "layernorm b1", "", "issue next + store/scatter"]
@@ -71,7 +71,7 @@ def main(workload="S1", family="cl", nodes=0, edges=0):
         names = (CM_FWD if family == "cm" else FWD) if name.endswith("fwd") else ((CMP_BWD if C == 32 else CMB_BWD) if family == "cm" else BWD)
         for i, nm in enumerate(names):
             if v[i] and nm:
-                print(f"   {nm:24s} {v[i] / waves / 1e3:9.1f} kcyc  {100.0 * v[i] / tot:5.1f}%")
+                print(f"   {nm:44s} {v[i] / waves / 1e3:9.1f} kcyc  {100.0 * v[i] / tot:5.1f}%")
 
 if __name__ == "__main__":
     main(sys.argv[1] if len(sys.argv) > 1 else "S1", sys.argv[2] if len(sys.argv) > 2 else "cl",
