@@ -32,6 +32,8 @@ EXPORTS = (
     "csmpn_cemlp_backward",
     "csmpn_mvlinear_forward",
     "csmpn_mvlinear_backward",
+    "csmpn_mvlinear_backward_det_bytes",
+    "csmpn_mvlinear_backward_det",
     "csmpn_mvsilu_forward",
     "csmpn_mvsilu_backward",
     "csmpn_mvnorm_forward",
@@ -54,6 +56,8 @@ EXPORTS = (
     "csmpn_embed_cemlp_backward",
     "csmpn_type_attr_forward",
     "csmpn_type_attr_backward",
+    "csmpn_type_attr_backward_det_bytes",
+    "csmpn_type_attr_backward_det",
     "csmpn_readout_mse_forward",
     "csmpn_readout_mse_backward",
     "csmpn_readout_traj_forward",
@@ -120,6 +124,8 @@ def _load():
     sig("csmpn_cemlp_backward", C.c_int, [fp, C.c_int, bp, bg, C.c_int, vp, vp, i64, vp, vp, vp, sz, u32, vp])
     sig("csmpn_mvlinear_forward", C.c_int, [C.c_int, vp, vp, vp, i64, i32, i32, i32, vp, vp])
     sig("csmpn_mvlinear_backward", C.c_int, [C.c_int, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp])
+    sig("csmpn_mvlinear_backward_det_bytes", sz, [C.c_int, i64, i32, i32, i32])
+    sig("csmpn_mvlinear_backward_det", C.c_int, [C.c_int, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, sz, vp])
     sig("csmpn_mvsilu_forward", C.c_int, [fp, C.c_int, vp, vp, vp, i64, i32, vp, vp])
     sig("csmpn_mvsilu_backward", C.c_int, [fp, C.c_int, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp])
     sig("csmpn_mvnorm_forward", C.c_int, [fp, C.c_int, vp, vp, i64, i32, vp, vp])
@@ -148,6 +154,8 @@ def _load():
     sig("csmpn_embed_cemlp_backward", C.c_int, [fp, C.c_int, bp, bg, C.c_int, vp, i64, i32, vp, i32, i32, i64, vp, vp, vp, sz, u32, vp])
     sig("csmpn_type_attr_forward", C.c_int, [C.c_int, vp, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp])
     sig("csmpn_type_attr_backward", C.c_int, [C.c_int, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp])
+    sig("csmpn_type_attr_backward_det_bytes", sz, [i32, i32, i64, i64])
+    sig("csmpn_type_attr_backward_det", C.c_int, [C.c_int, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp, sz, vp])
     sig("csmpn_readout_mse_forward", C.c_int, [C.c_int, vp, vp, i32, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp])
     sig("csmpn_readout_mse_backward", C.c_int, [C.c_int, vp, i32, i64, i32, vp, i64, vp, vp, vp])
     sig("csmpn_readout_traj_forward", C.c_int, [C.c_int, vp, i32, vp, i64, vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp])

@@ -214,9 +214,13 @@ class _CemlpFn(torch.autograd.Function):
         want_state = _SAVE_STATE and binding.n == 3 and binding.out_features == 32
         saved = binding.new_saved(rows, x.device, want_state) if any(ctx.needs_input_grad) else None
         ctx.flags = native.FLAG_SAVE_STATE if (want_state and saved is not None) else 0
-        check(native.lib().csmpn_cemlp_forward(binding.metric_arr, binding.n, binding.params, binding.nblk,
-                                               x.data_ptr(), rows, y.data_ptr(), _ptr(saved), ws.data_ptr(),
-                                               ws.numel(), ctx.flags, _stream(x.device)))
+
+        def call(flags):
+            return native.lib().csmpn_cemlp_forward(binding.metric_arr, binding.n, binding.params, binding.nblk,
+                                                    x.data_ptr(), rows, y.data_ptr(), _ptr(saved), ws.data_ptr(),
+                                                    ws.numel(), flags, _stream(x.device))
+
+        _det_call(call, ctx.flags)
         ctx.binding = binding
         ctx.param_refs = params          # the caller's parameter objects (their .grad, for fused accumulation)
         ctx.ws, ctx.saved = ws, saved   # packed weights / block inputs are reused by backward
@@ -237,11 +241,13 @@ class _CemlpFn(torch.autograd.Function):
         flat, views = binding.new_grads(params, x.device, fused_into=fused)
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         ws = ctx.ws
-        check(native.lib().csmpn_cemlp_backward(binding.metric_arr, binding.n, binding.params, binding.grads,
-                                                binding.nblk, x.data_ptr(), gy.data_ptr(), x.shape[0], _ptr(gx),
-                                                _ptr(ctx.saved), ws.data_ptr(), ws.numel(),
-                                                native.FLAG_WEIGHTS_PACKED | ctx.flags,
-                                                _stream(x.device)))
+
+        def call(flags):
+            return native.lib().csmpn_cemlp_backward(binding.metric_arr, binding.n, binding.params, binding.grads,
+                                                     binding.nblk, x.data_ptr(), gy.data_ptr(), x.shape[0], _ptr(gx),
+                                                     _ptr(ctx.saved), ws.data_ptr(), ws.numel(), flags, _stream(x.device))
+
+        _det_call(call, native.FLAG_WEIGHTS_PACKED | ctx.flags)
         return (gx, None, *views)
 
 
@@ -277,6 +283,8 @@ class _EmbedCemlpFn(torch.autograd.Function):
         # validated: the caller has range-checked verts against vertex_feat's rows once (the batch plan); otherwise the entry
         # point does, with one host round trip (not capturable)
         st_flag |= native.FLAG_NO_VALIDATE if validated else 0
+        # no CSMPN_FLAG_DETERMINISTIC here, whatever deterministic_request() says: nothing in the wide parity-lane kernels'
+        # MODE_PLAIN depends on the order of arrival (include/csmpn_hip.h at the flag), the entry points take no such flag
         check(native.lib().csmpn_embed_cemlp_forward(
             binding.metric_arr, binding.n, binding.params, binding.nblk, vertex_feat.data_ptr(), int(vertex_feat.shape[0]),
             int(vertex_feat.shape[1]),
@@ -332,7 +340,9 @@ _warned_soft_det = False
 def set_deterministic(flag):
     """True / False: force the atomic-free aggregation on / off; None: follow the environment
     (CSMPN_DETERMINISTIC=0|1) and otherwise torch.use_deterministic_algorithms, which the reference
-    switches on (engineer/utils/seed.py:30)."""
+    switches on (engineer/utils/seed.py:30). The request reaches the EGCL stages, standalone CEMLPs, the standalone
+    MVLinear backward and the type-attribute backward (everything a step of the four task models runs); the four
+    standalone small layers (mvsilu / mvnorm / mvlayernorm / wgp _apply) have no deterministic form and ignore it."""
     global _DETERMINISTIC
     _DETERMINISTIC = None if flag is None else bool(flag)
 
@@ -358,6 +368,33 @@ def _soft_fallback(rc):
         warnings.warn("csmpn_hip: deterministic aggregation is not available for this layer shape "
                       f"({native.lib().csmpn_last_error().decode()}); using float atomics")
     return True
+
+
+def _det_call(call, flags):
+    """call(flags) of an entry point that accepts CSMPN_FLAG_DETERMINISTIC, under deterministic_request(): a hard request
+    raises on a shape without deterministic kernels, a soft one repeats the call without the flag (as the EGCL stages);
+    no request: exactly call(flags)."""
+    det = deterministic_request()
+    rc = call(flags | (native.FLAG_DETERMINISTIC if det else 0))
+    if det == "soft" and _soft_fallback(rc):
+        rc = call(flags)
+    check(rc)
+
+
+_DET_LAUNCHES = 0
+
+
+def det_launches() -> int:
+    """Calls of csmpn_mvlinear_backward_det / csmpn_type_attr_backward_det so far (tests assert that the deterministic
+    forms ran)."""
+    return _DET_LAUNCHES
+
+
+def _det_scratch(nbytes, device):
+    """Scratch for ONE call of a _det entry point (sized by its _bytes query; needs no initialisation); counts the call."""
+    global _DET_LAUNCHES
+    _DET_LAUNCHES += 1
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
 def _warn_soft_slice():
@@ -822,20 +859,30 @@ class _MVLinearFn(torch.autograd.Function):
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         pw, pb = ctx.param_refs
+        sub = 1 if w.dim() == 3 else 0
+
+        def run(gw_ptr, gb_ptr):
+            if deterministic_request() and (gw_ptr is not None or gb_ptr is not None):
+                # the atomic-free form: per-slab partial sums in scratch, added in a fixed order into the same targets
+                ws = _det_scratch(native.lib().csmpn_mvlinear_backward_det_bytes(ctx.n, rows, I, O, sub), x.device)
+                check(native.lib().csmpn_mvlinear_backward_det(ctx.n, x.data_ptr(), w.data_ptr(), gy.data_ptr(), rows, I, O, sub,
+                                                               _ptr(gx), gw_ptr, gb_ptr, ws.data_ptr(), ws.numel(),
+                                                               _stream(x.device)))
+            else:
+                check(native.lib().csmpn_mvlinear_backward(ctx.n, x.data_ptr(), w.data_ptr(), gy.data_ptr(), rows, I, O, sub,
+                                                           _ptr(gx), gw_ptr, gb_ptr, _stream(x.device)))
+
         if (pw is not None and pb is not False and (need_w or need_b)
                 and _fusable([pw if need_w else None, pb if need_b else None], x.device)
                 and (not need_b or pb.grad.numel() == O)):
-            # fused accumulation (set_fused_grad_accumulation): the kernel's atomics land in the parameters' own .grad - no
-            # zero fills, no AccumulateGrad adds (6 + 6 launches per md17 step)
-            check(native.lib().csmpn_mvlinear_backward(ctx.n, x.data_ptr(), w.data_ptr(), gy.data_ptr(), rows, I, O,
-                                                       1 if w.dim() == 3 else 0, _ptr(gx), pw.grad.data_ptr() if need_w else None,
-                                                       pb.grad.data_ptr() if need_b else None, _stream(x.device)))
+            # fused accumulation (set_fused_grad_accumulation): the kernel's atomics (under a deterministic request: the
+            # fixed-order sum of the slabs) land in the parameters' own .grad - no zero fills, no AccumulateGrad adds
+            # (6 + 6 launches per md17 step)
+            run(pw.grad.data_ptr() if need_w else None, pb.grad.data_ptr() if need_b else None)
             return gx, None, None, None
         gw = torch.zeros_like(w) if need_w else None   # None: frozen weight (bias still gets its gradient)
         gb = torch.zeros(1, O, 1, dtype=torch.float32, device=x.device) if need_b else None
-        check(native.lib().csmpn_mvlinear_backward(ctx.n, x.data_ptr(), w.data_ptr(), gy.data_ptr(), rows, I, O,
-                                                   1 if w.dim() == 3 else 0, _ptr(gx), _ptr(gw), _ptr(gb),
-                                                   _stream(x.device)))
+        run(_ptr(gw), _ptr(gb))
         return gx, gw, gb, None
 
 
@@ -1061,9 +1108,15 @@ class _TypeAttrFn(torch.autograd.Function):
         ref = ctx.table_ref
         fuse = ref is not None and _fusable([ref], types.device)
         g_tab = ref.grad if fuse else torch.zeros(T, K, dtype=torch.float32, device=types.device)
-        check(native.lib().csmpn_type_attr_backward(n, T, K, types.data_ptr(), int(types.shape[0]), src.data_ptr(), dst.data_ptr(),
-                                                    int(src.shape[0]), _ptr(g_node), _ptr(g_edge), g_tab.data_ptr(),
-                                                    _stream(types.device)))
+        S, E = int(types.shape[0]), int(src.shape[0])
+        if deterministic_request() and S + E > 0:
+            ws = _det_scratch(native.lib().csmpn_type_attr_backward_det_bytes(T, K, S, E), types.device)
+            check(native.lib().csmpn_type_attr_backward_det(n, T, K, types.data_ptr(), S, src.data_ptr(), dst.data_ptr(), E,
+                                                            _ptr(g_node), _ptr(g_edge), g_tab.data_ptr(), ws.data_ptr(),
+                                                            ws.numel(), _stream(types.device)))
+        else:
+            check(native.lib().csmpn_type_attr_backward(n, T, K, types.data_ptr(), S, src.data_ptr(), dst.data_ptr(), E,
+                                                        _ptr(g_node), _ptr(g_edge), g_tab.data_ptr(), _stream(types.device)))
         return (None if fuse else g_tab), None, None, None, None
 
 

@@ -14,7 +14,8 @@
 //                               features (md17_cssmpnn.py:122-133, hulls_cssmpnn.py:127-140): one launch each way instead
 //                               of ~20 small PyTorch launches per step
 // HBM-bound gathers / reductions: one pass over the data, coalesced rows, fixed-order sums (no atomics; the 9-element
-// table gradient of csmpn_type_attr_backward is the exception: block sums in LDS, then one float atomic per element and block).
+// table gradient of csmpn_type_attr_backward is the exception: block sums in LDS, then one float atomic per element and block;
+// csmpn_type_attr_backward_det is its atomic-free form).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -161,6 +162,77 @@ __global__ void __launch_bounds__(256) type_attr_bwd_kernel(int K, int TK, const
     }
     __syncthreads();
     if (threadIdx.x < TK && bins[threadIdx.x] != 0.f) atomicAdd(g_table + threadIdx.x, bins[threadIdx.x]);
+}
+
+// Deterministic form (csmpn_type_attr_backward_det): no float atomics, in LDS or in memory. A workgroup takes a contiguous
+// chunk of the n_nodes + n_edges rows, 256 / K of them per pass: thread (row, k) parks the row's one (node) or two (edge:
+// source, target) blade-0 gradients with their type ids in LDS, then the thread of bin (t, k) adds the parked values of its
+// k in ascending row order (source before target) to its running sum. The chunk's sums leave as one partial row of
+// kTypeBins floats (every bin written: nothing stale is read later); type_attr_det_reduce_kernel adds the rows in
+// ascending workgroup order. Chunk size and workgroup count follow from the call's sizes alone.
+constexpr int kTypeDetThreads = 256;
+constexpr long kTypeDetMaxGroups = 256;   // partial rows: at most 256 x 64 floats = 64 KB of scratch
+inline long type_det_group_bound(long rows, int K) {
+    const long rpp = kTypeDetThreads / K;
+    const long passes = (rows + rpp - 1) / rpp;
+    return passes < kTypeDetMaxGroups ? passes : kTypeDetMaxGroups;
+}
+__global__ void __launch_bounds__(kTypeDetThreads) type_attr_bwd_det_kernel(int K, int TK, const int* types, long n_nodes, const int* src,
+                                                                            const int* dst, long n_edges, int D, const float* g_node,
+                                                                            const float* g_edge, long chunk_rows, float* partials) {
+    __shared__ int ty_a[kTypeDetThreads], ty_b[kTypeDetThreads];
+    __shared__ float v_a[kTypeDetThreads], v_b[kTypeDetThreads];
+    const int tid = threadIdx.x;
+    const int T = TK / K;
+    const int rpp = kTypeDetThreads / K;          // rows per pass
+    const int lr = tid / K, k = tid - lr * K;     // this thread's (row of the pass, k); idle where lr >= rpp
+    const int bin_t = tid / K, bin_k = tid - bin_t * K;   // the bin this thread sums (tid < TK)
+    const long total = n_nodes + n_edges;
+    const long row0 = (long)blockIdx.x * chunk_rows;
+    const long row1 = row0 + chunk_rows < total ? row0 + chunk_rows : total;
+    auto ty = [&](long r) { return min(max(types[r], 0), T - 1); };   // as the forward: clamped into the bins
+    float acc = 0.f;
+    for (long base = row0; base < row1; base += rpp) {
+        const long row = base + lr;
+        int ta = -1, tb = -1;
+        float va = 0.f, vb = 0.f;
+        if (lr < rpp && row < row1) {
+            if (row < n_nodes) {
+                if (g_node) { ta = ty(row); va = g_node[(row * K + k) * D]; }
+            } else if (g_edge) {
+                const long e = row - n_nodes;
+                ta = ty(src[e]); va = g_edge[(e * 2 * K + k) * D];
+                tb = ty(dst[e]); vb = g_edge[(e * 2 * K + K + k) * D];
+            }
+        }
+        ty_a[tid] = ta; v_a[tid] = va; ty_b[tid] = tb; v_b[tid] = vb;
+        __syncthreads();
+        if (tid < TK) {
+            for (int j = bin_k; j < rpp * K; j += K) {   // the parked entries of this k, ascending row
+                if (ty_a[j] == bin_t) acc += v_a[j];
+                if (ty_b[j] == bin_t) acc += v_b[j];
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < kTypeBins) partials[(size_t)blockIdx.x * kTypeBins + tid] = tid < TK ? acc : 0.f;
+}
+// g_table[bin] += the workgroups' partial rows in ascending workgroup order, eight rows in flight
+__global__ void __launch_bounds__(kTypeBins) type_attr_det_reduce_kernel(const float* __restrict__ partials, int ngroups, int TK,
+                                                                         float* g_table) {
+    const int b = threadIdx.x;
+    if (b >= TK) return;
+    float s = 0.f;
+    int w = 0;
+    for (; w + 8 <= ngroups; w += 8) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = partials[(size_t)(w + i) * kTypeBins + b];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += v[i];
+    }
+    for (; w < ngroups; ++w) s += partials[(size_t)w * kTypeBins + b];
+    g_table[b] += s;
 }
 
 // ---- trajectory readout + loss (md17 / motion / NBA heads: md17_cssmpnn.py:165-176, motion_cssmpnn.py:150-168,
@@ -462,6 +534,38 @@ int csmpn_type_attr_backward(int n, int32_t n_types, int32_t k, const int32_t* t
     hipLaunchKernelGGL(type_attr_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)k,
                        (int)(n_types * k), (const int*)types, (long)n_nodes, (const int*)src, (const int*)dst, (long)n_edges, 1 << n,
                        g_node_attr, g_edge_attr, g_table);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "type attributes backward: %s", hipGetErrorString(e));
+    return CSMPN_OK;
+}
+
+size_t csmpn_type_attr_backward_det_bytes(int32_t n_types, int32_t k, int64_t n_nodes, int64_t n_edges) {
+    if (n_nodes < 0 || n_edges < 0 || k < 1 || n_types < 1 || n_types * k > kTypeBins || n_nodes + n_edges <= 0) return 0;
+    return (size_t)type_det_group_bound((long)(n_nodes + n_edges), (int)k) * kTypeBins * sizeof(float);
+}
+
+int csmpn_type_attr_backward_det(int n, int32_t n_types, int32_t k, const int32_t* types, int64_t n_nodes, const int32_t* src,
+                                 const int32_t* dst, int64_t n_edges, const float* g_node_attr, const float* g_edge_attr,
+                                 float* g_table, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n < 1 || n > 5) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "n = %d generators not supported", n);
+    if (n_nodes < 0 || n_edges < 0 || k < 1 || n_types < 1 || n_types * k > kTypeBins) return csmpn_fail(CSMPN_ERR_INVALID, "type attributes: bad sizes");
+    if (n_nodes + n_edges == 0 || (!g_node_attr && !g_edge_attr)) return CSMPN_OK;
+    if (!types || !g_table || (n_edges && g_edge_attr && (!src || !dst))) return csmpn_fail(CSMPN_ERR_INVALID, "type attributes: null pointer");
+    const size_t need = csmpn_type_attr_backward_det_bytes(n_types, k, n_nodes, n_edges);
+    if (!workspace || workspace_bytes < need)
+        return csmpn_fail(CSMPN_ERR_INVALID, "csmpn_type_attr_backward_det: workspace %zu bytes < %zu (csmpn_type_attr_backward_det_bytes)",
+                          workspace ? workspace_bytes : (size_t)0, need);
+    const long total = (long)(n_nodes + n_edges);
+    const long rpp = kTypeDetThreads / k;
+    const long passes = (total + rpp - 1) / rpp;
+    const long bound = type_det_group_bound(total, (int)k);
+    const long chunk_rows = (passes + bound - 1) / bound * rpp;      // whole passes per workgroup
+    const long groups = (total + chunk_rows - 1) / chunk_rows;       // <= bound
+    hipLaunchKernelGGL(type_attr_bwd_det_kernel, dim3((unsigned)groups), dim3(kTypeDetThreads), 0, (hipStream_t)stream, (int)k,
+                       (int)(n_types * k), (const int*)types, (long)n_nodes, (const int*)src, (const int*)dst, (long)n_edges, 1 << n,
+                       g_node_attr, g_edge_attr, chunk_rows, (float*)workspace);
+    hipLaunchKernelGGL(type_attr_det_reduce_kernel, dim3(1), dim3(kTypeBins), 0, (hipStream_t)stream, (const float*)workspace,
+                       (int)groups, (int)(n_types * k), g_table);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "type attributes backward: %s", hipGetErrorString(e));
     return CSMPN_OK;

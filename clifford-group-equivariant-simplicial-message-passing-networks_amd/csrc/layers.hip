@@ -426,7 +426,10 @@ inline int mvlinear_slab(long rows, int elem_blocks) {
     long s = (rows + slabs - 1) / slabs;
     return (int)(s < 8 ? 8 : (s > 64 ? 64 : s));
 }
-__global__ void mvlinear_bwd_w_kernel(const MvLinDesc P, int slab) {
+// DET (csmpn_mvlinear_backward_det): the slab's sum is stored to partials[slab][element] instead of added with an atomic;
+// mvlinear_det_reduce_kernel adds the slabs in ascending order. The walk over a slab's rows is the same in both forms.
+template <bool DET>
+__global__ void mvlinear_bwd_w_kernel(const MvLinDesc P, int slab, float* __restrict__ partials) {
     const long r0 = (long)blockIdx.y * slab;
     const long r1 = r0 + slab < P.rows ? r0 + slab : P.rows;
     const int ws = P.sub ? P.G : 1;
@@ -449,12 +452,51 @@ __global__ void mvlinear_bwd_w_kernel(const MvLinDesc P, int slab) {
             const float* xr = P.x + (r * P.I + i) * P.D;
             for (int d = d0; d < d1; ++d) acc = fmaf(gr[d], xr[d], acc);
         }
-        atomicAdd(P.gw + e, acc);
+        if constexpr (DET) partials[(size_t)blockIdx.y * (nw + P.O) + e] = acc;
+        else atomicAdd(P.gw + e, acc);
     } else if (P.gb) {
         const int o = e - nw;
         for (long r = r0; r < r1; ++r) acc += P.gy[(r * P.O + o) * P.D];
-        atomicAdd(P.gb + o, acc);
+        if constexpr (DET) partials[(size_t)blockIdx.y * (nw + P.O) + e] = acc;
+        else atomicAdd(P.gb + o, acc);
     }
+}
+
+// Deterministic form: at most kMvDetMaxSlabs slabs (the scratch is kMvDetMaxSlabs * (weight + bias elements) floats at
+// most, whatever the row count: 2.4 MB for md17's 35 -> 32 feature embedding); slab size and count follow from the call's
+// sizes alone, so that two processes on the same inputs add in the same order.
+constexpr long kMvDetMaxSlabs = 512;
+inline int mvlinear_det_slab(long rows, int elem_blocks) {
+    long s = mvlinear_slab(rows, elem_blocks);
+    const long floor_rows = (rows + kMvDetMaxSlabs - 1) / kMvDetMaxSlabs;
+    if (s < floor_rows) s = floor_rows;
+    return (int)s;
+}
+// an upper bound of the slab count that does not shrink as the rows grow (the count itself wobbles where the slab widens)
+inline long mvlinear_det_slab_bound(long rows) {
+    const long s = (rows + 7) / 8;
+    return s < kMvDetMaxSlabs ? s : kMvDetMaxSlabs;
+}
+// g_weight / g_bias += the slabs' partial sums in ascending slab order: one thread per element (consecutive threads read
+// consecutive words of a slab's row), eight slabs in flight. Elements without a destination were never written: skipped.
+__global__ void __launch_bounds__(256) mvlinear_det_reduce_kernel(const float* __restrict__ partials, int nslabs, int nw, int O,
+                                                                  float* gw, float* gb) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    const int total = nw + O;
+    if (e >= total) return;
+    float* const dst = e < nw ? (gw ? gw + e : nullptr) : (gb ? gb + (e - nw) : nullptr);
+    if (!dst) return;
+    float s = 0.f;
+    int w = 0;
+    for (; w + 8 <= nslabs; w += 8) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = partials[(size_t)(w + i) * total + e];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += v[i];
+    }
+    for (; w < nslabs; ++w) s += partials[(size_t)w * total + e];
+    *dst += s;
 }
 
 int mvlinear_desc(int n, long rows, int I, int O, int sub, MvLinDesc& P) {
@@ -560,8 +602,52 @@ int csmpn_mvlinear_backward(int n, const float* x, const float* weight, const fl
         const int nelem = out_features * in_features * (P.sub ? P.G : 1) + out_features;
         const unsigned eb = (unsigned)((nelem + block - 1) / block);
         const int slab = mvlinear_slab(rows, (int)eb);
-        hipLaunchKernelGGL(mvlinear_bwd_w_kernel, dim3(eb, (unsigned)((rows + slab - 1) / slab)), dim3(block), 0,
-                           (hipStream_t)stream, P, slab);
+        hipLaunchKernelGGL(mvlinear_bwd_w_kernel<false>, dim3(eb, (unsigned)((rows + slab - 1) / slab)), dim3(block), 0,
+                           (hipStream_t)stream, P, slab, (float*)nullptr);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "hipGetLastError(): %s", hipGetErrorString(e));
+    return CSMPN_OK;
+}
+
+size_t csmpn_mvlinear_backward_det_bytes(int n, int64_t rows, int32_t in_features, int32_t out_features, int32_t subspaces) {
+    if (n < 1 || n > 5 || rows <= 0 || in_features < 1 || out_features < 1) return 0;
+    const size_t nelem = (size_t)out_features * in_features * (subspaces ? n + 1 : 1) + out_features;
+    if (nelem > 0x7fffffffu) return 0;
+    return (size_t)mvlinear_det_slab_bound((long)rows) * nelem * sizeof(float);
+}
+
+int csmpn_mvlinear_backward_det(int n, const float* x, const float* weight, const float* gy, int64_t rows,
+                                int32_t in_features, int32_t out_features, int32_t subspaces, float* gx, float* g_weight,
+                                float* g_bias, void* workspace, size_t workspace_bytes, void* stream) {
+    MvLinDesc P;
+    int rc = mvlinear_desc(n, (long)rows, in_features, out_features, subspaces, P);
+    if (rc) return rc;
+    if (rows == 0) return CSMPN_OK;
+    if (!x || !weight || !gy) return csmpn_fail(CSMPN_ERR_INVALID, "MVLinear: null pointer");
+    P.x = x; P.w = weight; P.gy = gy; P.gx = gx; P.gw = g_weight; P.gb = g_bias;
+    const unsigned block = 256;
+    const size_t nelem = (size_t)out_features * in_features * (P.sub ? P.G : 1) + out_features;
+    const size_t need = csmpn_mvlinear_backward_det_bytes(n, rows, in_features, out_features, subspaces);
+    if (g_weight || g_bias) {
+        if (nelem > 0x7fffffffu) return csmpn_fail(CSMPN_ERR_INVALID, "MVLinear: too many weight elements");
+        if (!workspace || workspace_bytes < need)
+            return csmpn_fail(CSMPN_ERR_INVALID, "csmpn_mvlinear_backward_det: workspace %zu bytes < %zu (csmpn_mvlinear_backward_det_bytes)",
+                              workspace ? workspace_bytes : (size_t)0, need);
+    }
+    if (gx) {
+        const long total = (long)rows * in_features * P.D;
+        hipLaunchKernelGGL(mvlinear_bwd_x_kernel, dim3((unsigned)((total + block - 1) / block)), dim3(block), 0,
+                           (hipStream_t)stream, P);
+    }
+    if (g_weight || g_bias) {
+        const unsigned eb = (unsigned)((nelem + block - 1) / block);
+        const int slab = mvlinear_det_slab(rows, (int)eb);
+        const long nslabs = (rows + slab - 1) / slab;   // <= mvlinear_det_slab_bound(rows): slab >= 8 and >= rows / kMvDetMaxSlabs
+        hipLaunchKernelGGL(mvlinear_bwd_w_kernel<true>, dim3(eb, (unsigned)nslabs), dim3(block), 0, (hipStream_t)stream, P, slab,
+                           (float*)workspace);
+        hipLaunchKernelGGL(mvlinear_det_reduce_kernel, dim3(eb), dim3(block), 0, (hipStream_t)stream, (const float*)workspace,
+                           (int)nslabs, (int)(nelem - out_features), (int)out_features, g_weight, g_bias);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "hipGetLastError(): %s", hipGetErrorString(e));

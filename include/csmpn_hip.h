@@ -70,7 +70,23 @@ extern "C" {
                                        default), 65..256 channels included (at most max(128 MiB, 16 copies) of them).
                                        Every other shape returns CSMPN_ERR_UNSUPPORTED. Also accepted by
                                        csmpn_egcl_node_forward/backward and csmpn_cemlp_forward/backward, where it only
-                                       selects the atomic-free parameter sums. */
+                                       selects the atomic-free parameter sums.
+                                       Deterministic coverage of the library (same inputs -> same bits, run after run):
+                                         - the EGCL stages and csmpn_egcl_backward with this flag, on the shapes above;
+                                         - standalone CEMLPs (csmpn_cemlp_forward/backward) with this flag, on the same shapes;
+                                         - csmpn_embed_cemlp_forward/backward WITHOUT any flag: the wide parity-lane kernels
+                                           sum the vertex orders in registers, map tiles to workgroups statically and add
+                                           their parameter gradients from per-workgroup slices in a fixed order - nothing
+                                           in that path depends on the order of arrival, so the entry points take no such flag;
+                                         - csmpn_mvlinear_backward_det and csmpn_type_attr_backward_det (entry points of
+                                           their own: they need scratch the plain forms do not take); every forward,
+                                           csmpn_mvlinear_backward's d/dx, csmpn_simplex_rows, csmpn_segment_reduce and the
+                                           readout entry points have fixed-order sums as they are.
+                                       NOT covered: the four standalone small layers (csmpn_mvsilu_*, csmpn_mvnorm_*,
+                                       csmpn_mvlayernorm_*, csmpn_wgp_*): their parameter gradients - and the row sums in the
+                                       forward of csmpn_mvlayernorm_forward - use float atomics in LDS and in memory. No task
+                                       model calls them alone. csmpn_mvlinear_backward and csmpn_type_attr_backward (the
+                                       plain forms) add d/dW, d/dbias and the table gradient with float atomics. */
 #define CSMPN_FLAG_SAVE_STATE 8u     /* csmpn_egcl_{edge,node}_{forward,backward}, csmpn_embed_cemlp_{forward,backward} (two-block
                                       * modules), round 4; csmpn_cemlp_{forward,backward}, round 5, for the standalone Cl(3,0) CEMLPs
                                       * of 32 channels the 16-row-tile family serves (1 or 2 blocks; 32, 60 or 90 input channels:
@@ -194,6 +210,19 @@ int csmpn_mvlinear_forward(int n, const float* x, const float* weight, const flo
 int csmpn_mvlinear_backward(int n, const float* x, const float* weight, const float* gy, int64_t rows,
                             int32_t in_features, int32_t out_features, int32_t subspaces, float* gx, float* g_weight,
                             float* g_bias, void* stream);
+/* csmpn_mvlinear_backward without float atomics: the (element, row slab) launch stores its partial sums to
+ * workspace[slab][element] and a second launch adds the slabs in ascending order INTO g_weight / g_bias (+=, as above); gx as
+ * above. Slab size and count depend on (rows, in_features, out_features, subspaces) only, so the result is the same bits
+ * in every run and every process. At most 512 slabs: csmpn_mvlinear_backward_det_bytes() =
+ * min(ceil(rows / 8), 512) * (weight elements + out_features) * 4 bytes - non-decreasing in rows, constant from 4089 rows
+ * on (2.4 MB for a 35 -> 32 layer without subspaces, whatever the row count); host-only, 0 for sizes the entry point rejects
+ * and for rows <= 0. The workspace needs no initialisation (every word read was written by the call); NULL or too small:
+ * CSMPN_ERR_INVALID (not needed when g_weight and g_bias are both NULL). rows == 0: CSMPN_OK, nothing touched. Nothing is
+ * allocated. */
+size_t csmpn_mvlinear_backward_det_bytes(int n, int64_t rows, int32_t in_features, int32_t out_features, int32_t subspaces);
+int csmpn_mvlinear_backward_det(int n, const float* x, const float* weight, const float* gy, int64_t rows,
+                                int32_t in_features, int32_t out_features, int32_t subspaces, float* gx, float* g_weight,
+                                float* g_bias, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The four small layers on their own (inside a CEMLP they are fused into the row programs; no
  * reference model calls them alone - these entry points give the nn.Modules a device forward /
@@ -396,6 +425,17 @@ int csmpn_type_attr_forward(int n, const float* table, int32_t n_types, int32_t 
 int csmpn_type_attr_backward(int n, int32_t n_types, int32_t k, const int32_t* types, int64_t n_nodes, const int32_t* src,
                              const int32_t* dst, int64_t n_edges, const float* g_node_attr, const float* g_edge_attr, float* g_table,
                              void* stream);
+/* csmpn_type_attr_backward without float atomics (none in LDS either): every workgroup sums the n_types * K bins of a
+ * contiguous chunk of the n_nodes + n_edges rows in ascending row order (an edge's source before its target) and stores them
+ * as one row of 64 floats in the workspace; a second launch adds the rows in ascending order INTO g_table (+=). Chunk size
+ * and workgroup count depend on (K, n_nodes + n_edges) only. csmpn_type_attr_backward_det_bytes() =
+ * min(ceil((n_nodes + n_edges) / floor(256 / K)), 256) * 256 bytes (at most 64 KB; non-decreasing in the rows, constant
+ * from 256 * floor(256 / K) rows on; host-only; 0 for sizes the entry point rejects and for no rows). Workspace, errors and
+ * the empty call as csmpn_mvlinear_backward_det; type ids are clamped as in the plain form. */
+size_t csmpn_type_attr_backward_det_bytes(int32_t n_types, int32_t k, int64_t n_nodes, int64_t n_edges);
+int csmpn_type_attr_backward_det(int n, int32_t n_types, int32_t k, const int32_t* types, int64_t n_nodes, const int32_t* src,
+                                 const int32_t* dst, int64_t n_edges, const float* g_node_attr, const float* g_edge_attr,
+                                 float* g_table, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Scalar readout + loss of the convex-hulls model (hulls_cssmpnn.py:93,155-164):
  *   pred_g = mean_{s in graph g} (sum_c weight[c * weight_stride] * x[s][c][0]) + bias,  loss_g = (pred_g - target_g)^2
