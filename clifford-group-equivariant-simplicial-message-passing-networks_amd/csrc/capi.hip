@@ -312,7 +312,7 @@ int csmpn_egcl_edge_forward(const float* metric, int n, const csmpn_block_params
                         E, plan, (flags & CSMPN_FLAG_DETERMINISTIC) != 0))) return rc;
     const bool need_pack = !(flags & CSMPN_FLAG_WEIGHTS_PACKED);   // packed fragments are a matter of the general kernels: run_rows
     io.agg = agg; io.save = save_inputs;
-    (void)N;
+    io.gather_rows = N;
     return run_rows(plan, MODE_EDGE, false, io, (hipStream_t)stream, need_pack);
 }
 
@@ -335,7 +335,7 @@ static int edge_backward(const float* metric, int n, const csmpn_block_params* b
     // with LDS-staged raw weights packs nothing): the backward packs for itself; no-op for VAR_WAVE
     const bool need_pack = true;
     io.gy = g_agg; io.gx[0] = gh; io.gx[1] = g_edge_attr; io.saved = saved_inputs;
-    (void)N;
+    io.gather_rows = N;
     return run_rows(plan, MODE_EDGE, true, io, (hipStream_t)stream, need_pack, (flags & CSMPN_FLAG_WEIGHTS_PACKED) != 0, deferred);
 }
 

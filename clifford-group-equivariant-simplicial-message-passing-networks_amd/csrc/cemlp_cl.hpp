@@ -35,6 +35,9 @@
 //    block; cl_reduce_kernel adds the slices of all blocks in a fixed order (no atomics on parameters: bit-reproducible).
 //  * gathers: a lane loads its own 32 bytes of a row (2 x 16 bytes); scatters go through a per-wave LDS tile so that
 //    one atomic instruction covers whole 256-byte rows, equal consecutive targets summed first.
+//  * addressing: every array of a launch is a raw buffer resource and a lane's address a 32-bit byte offset (ClBuf); the
+//    range check of the resource is the tail predication of the stores (no array of a launch above kClMaxArrayBytes: the
+//    launch condition, launch.hpp).
 #pragma once
 #include "cemlp_lane.hpp"
 
@@ -50,6 +53,36 @@ constexpr int kClParStride = 36;     // floats per channel in the per-channel pa
 // them across each other (cemlp_cm.hpp met exactly that). A compiler barrier + the wave-barrier intrinsic (a scheduling
 // barrier, no instruction) state the contract at every such hand-over.
 #define CL_LDS_ORDER() do { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
+
+// ---------------------------------------------------------------------------------
+// Addressing. An array of a launch is a raw buffer resource, built once per kernel from launch-uniform values (base in
+// SGPRs, num_records = its size in bytes); a lane addresses it with a 32-bit BYTE offset: (row or index) * row bytes + the
+// lane's place in the row, the latter worked out once per kernel. An access costs at most one 32-bit multiply-add - the
+// 64-bit address per lane and access of a flat load took three to four vector instructions. The hardware's range check
+// is the tail predication: a store whose offset is not below num_records is dropped (a load reads zero), so the rows
+// behind the last one of a partial tile store without a branch or a select - their offsets lie behind the array, or
+// are kClNoStore where the layout (state regions) interleaves them with valid rows. No offset of a launch wraps:
+// cl_eligible admits arrays of at most kClMaxArrayBytes (launch.hpp).
+typedef unsigned cl_u4 __attribute__((ext_vector_type(4)));
+constexpr unsigned kClNoStore = 0xFF000000u;   // = kClMaxArrayBytes: behind every array, and 16 MiB short of a wrap
+constexpr int kClStream = 2;                   // the instruction's `nt` bit: rows written once and read once (state regions)
+struct ClBuf {
+    __amdgpu_buffer_rsrc_t r;
+    CSMPN_DEV ClBuf() : r(__builtin_amdgcn_make_buffer_rsrc(nullptr, 0, 0, 0x00020000)) {}
+    // bytes <= kClMaxArrayBytes (the launch condition); a null array has no records
+    CSMPN_DEV ClBuf(const void* base, size_t bytes)
+        : r(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, base ? (int)(unsigned)bytes : 0, 0x00020000)) {}
+    template <int AUX = 0>
+    CSMPN_DEV f4 ld4(unsigned off) const { return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, AUX)); }
+    CSMPN_DEV int ldi(unsigned off) const { return (int)__builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0); }
+    template <int AUX = 0>
+    CSMPN_DEV void st4(unsigned off, f4 v) const { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cl_u4, v), r, (int)off, 0, AUX); }
+    // the lane's 8 blades = 32 contiguous bytes of a row
+    CSMPN_DEV void st8(unsigned off, const float (&x)[8]) const {
+        st4(off, f4{x[0], x[1], x[2], x[3]});
+        st4(off + 16, f4{x[4], x[5], x[6], x[7]});
+    }
+};
 
 // diagnostic build only (-DCSMPN_STAMPS, never shipped, never timed): shader-clock cycles per phase, summed per wave.
 // The scheduling barriers at a stamp forbid overlaps across phases (memory operations stay in flight: a phase is
@@ -202,11 +235,11 @@ struct ClTab {
 // forward state of one block kept for its backward
 // offset of (row, channel)'s first piece inside a state region (CSMPN_FLAG_SAVE_STATE, cemlp_device.hpp): a tile is 64 / C rows
 // = 64 (row, channel) positions; piece e (4 blades) of position l lies at (tile * 2 + e) * 256 + 4 l floats
+// In bytes: a tile's pieces start kClStateTile bytes behind the previous tile's; the lane's place cl_state_lane inside
+// piece 0 is fixed for the kernel, piece 1 lies kClStatePiece bytes further.
+constexpr unsigned kClStateTile = 2048, kClStatePiece = 1024;
 template <int C>
-CSMPN_DEV size_t cl_state_off(long row, int c) {
-    constexpr int RPT = 64 / C;
-    return (size_t)(row / RPT) * 512 + 4 * ((int)(row % RPT) * C + c);
-}
+CSMPN_DEV unsigned cl_state_lane(int r, int c) { return 16u * (unsigned)(r * C + c); }
 struct ClFwd {
     float y[8], gate[4], R[8], invden[4], s[8];
     float qs, nl, invMn;
@@ -219,94 +252,94 @@ CSMPN_DEV float cl_smooth_abs_sqrt(float q) { return sqrt_pos(sqrt_pos(__builtin
 // channel c + dir (probed on the device).
 // Two steps - load: every global read of the block requested; store: into LDS - so that a kernel requests the tables of all
 // its blocks before it waits for the first (one global round trip per launch instead of one per block).
+// Every wave of a launch runs this before its first tile, all of them at the same time: it is priced in issue slots like the
+// tile loop. So the work is dealt out in units a wave can address without per-lane decisions. A weight table is a sequence
+// of PIECES of (at most) 64 entries - one rotation-ordered [k][o] image of one matrix (or input pass of W1), plain or
+// transposed - and piece q belongs to wave q mod 4: which matrix, its row stride, its first channel, period and width
+// are scalars chosen by the wave index, the lane's entry is (k, o) = (lane / C, lane mod C) in every piece, and an entry
+// without a source (a replicated attribute channel past the width) is an offset behind the matrix: the range check reads
+// it as the zero the table holds there. The per-channel parameters are dealt out likewise: wave 0 the path weights, wave 1
+// the three gate / normalisation vectors, wave 2 the three per-channel scalars.
 template <class ALG, int C, class TB, bool BWD>
 struct ClStage {
-    static constexpr int G = ALG::G, P = ALG::P, NE = TB::n_entries, NIT = (NE + 64 * kClWaves - 1) / (64 * kClWaves);
-    static constexpr int NPAR = C * kClParStride, NITP = (NPAR + 64 * kClWaves - 1) / (64 * kClWaves);
+    static constexpr int G = ALG::G, P = ALG::P, NP = TB::NP;
     static_assert(G == 4, "the weight of one (o, c) pair is one 16-byte vector of 4 grades");
-    static_assert(16 + P <= kClParStride, "parameter stride");
-    f4 v[NIT];
-    float pv[NITP];
-    bool live[NIT], plive[NITP], sig[NITP];
-    __device__ void load(const DevBlock& B, int tid, int dir) {
-        const float *pW1 = B.W1, *pWR = B.WR, *pWL = B.WL;
-        const float* src[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int e = tid + it * 64 * kClWaves;   // f4 entry
-            src[it] = nullptr;
-            // forward tables: entry (k, o) = W[o][first channel + ((o + dir k) mod period)]
-            static_for<0, TB::NP>([&](auto p) {
-                constexpr int e0 = TB::W1(p) / 4, PER = TB::period(p), n = PER * C;
-                if (e >= e0 && e < e0 + n) {
-                    const int k = (e - e0) / C, o = (e - e0) % C, cs = (o + dir * k) & (PER - 1);
-                    if (cs < TB::width(p)) src[it] = pW1 + ((o * TB::I + TB::coff(p) + cs) * G);
-                }
-            });
-            if (e >= TB::WR / 4 && e < TB::fwd_end / 4) {
-                const int f = e - TB::WR / 4, which = f / (C * C), k = (f % (C * C)) / C, o = f % C, cs = (o + dir * k) & (C - 1);
-                src[it] = (which == 0 ? pWR : pWL) + ((o * C + cs) * G);
-            }
-            if constexpr (BWD) {
-                // transposed tables: entry (k, c) = W[(c + dir k) mod C][first channel + (c mod period)]
-                static_for<0, TB::NP>([&](auto p) {
-                    constexpr int e0 = TB::W1T(p) / 4, PER = TB::period(p);
-                    if (e >= e0 && e < e0 + C * C) {
-                        const int k = (e - e0) / C, c = (e - e0) % C, o = (c + dir * k) & (C - 1), cs = c & (PER - 1);
-                        if (cs < TB::width(p)) src[it] = pW1 + ((o * TB::I + TB::coff(p) + cs) * G);
-                    }
-                });
-                if (e >= TB::WRT / 4 && e < TB::par / 4) {
-                    const int f = e - TB::WRT / 4, which = f / (C * C), k = (f % (C * C)) / C, c = f % C, o = (c + dir * k) & (C - 1);
-                    src[it] = (which == 0 ? pWR : pWL) + ((o * C + c) * G);
-                }
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            // every thread loads (an entry without a source: the first weight, replaced by zero in `store`): a load under a
-            // branch is waited for inside the branch, one round trip per entry
-            live[it] = src[it] != nullptr;
-            v[it] = ld4(live[it] ? src[it] : pW1);
-        }
-        // per-channel parameters: [b1, bL, la, 0 | sa[4] | sb[4] | sigmoid(an)[4] | w[P]] per channel
-        const float *pb1 = B.b1, *pbL = B.bL, *pla = B.la, *psa = B.sa, *psb = B.sb, *pan = B.an, *pw = B.w;
-        const bool has_b1 = B.has_b1 != 0;
-        const float* ps[NITP];
-#pragma unroll
-        for (int it = 0; it < NITP; ++it) {
-            const int e = tid + it * 64 * kClWaves;
-            ps[it] = nullptr;
-            sig[it] = false;
-            if (e < NPAR) {
-                const int ch = e / kClParStride, s = e % kClParStride;
-                if (s == 0) { if (has_b1) ps[it] = pb1 + ch; }
-                else if (s == 1) ps[it] = pbL + ch;
-                else if (s == 2) ps[it] = pla + ch;
-                else if (s >= 4 && s < 8) ps[it] = psa + ch * G + (s - 4);
-                else if (s >= 8 && s < 12) ps[it] = psb + ch * G + (s - 8);
-                else if (s >= 12 && s < 16) { ps[it] = pan + ch * G + (s - 12); sig[it] = true; }
-                else if (s >= 16 && s < 16 + P) ps[it] = pw + ch * P + (s - 16);
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < NITP; ++it) {
-            plive[it] = ps[it] != nullptr;
-            pv[it] = *(plive[it] ? ps[it] : pW1);
+    static_assert(16 + P <= kClParStride && P % 4 == 0, "parameter stride; path weights as 16-byte vectors");
+    static_assert(C * C == 64, "a piece is one wave's worth of entries");
+    static_assert(kClWaves >= 3, "three waves share the per-channel parameters");
+    static_assert(C * P / 4 <= 64, "one wave deals out the path weights, a 16-byte vector per lane");
+    static_assert(16 + P == kClParStride, "a channel's parameter row has no padding behind the path weights: every float of it is staged");
+    static constexpr int NQ = BWD ? 2 * NP + 4 : NP + 2, NSLOT = (NQ + kClWaves - 1) / kClWaves;
+    struct Piece {
+        const float* base;   // the matrix [rows][I][G]
+        unsigned bytes;      // its size
+        int e0, n;           // first f4 entry of the table, entries
+        int stride, coff;    // bytes between rows of the matrix; bytes in front of the pass's first channel
+        int pm, width;       // period - 1 (channel c of a narrow pass sits at c mod period), channels of the pass
+        bool transposed;     // entry (k, c) = W[(c + dir k) mod C][c mod period] instead of (k, o) = W[o][(o + dir k) mod period]
+    };
+    template <int Q>
+    static CSMPN_DEV Piece piece(const DevBlock& B) {
+        static_assert(Q >= 0 && Q < NQ, "piece index");
+        constexpr bool T = Q >= NP + 2;
+        constexpr int q = T ? Q - (NP + 2) : Q;   // 0 .. NP - 1: pass of W1; NP: linear_right; NP + 1: linear_left
+        if constexpr (q < NP) {
+            return Piece{B.W1, (unsigned)(C * TB::I * G * 4), (T ? TB::W1T(q) : TB::W1(q)) / 4, T ? C * C : TB::period(q) * C, TB::I * G * 4,
+                         TB::coff(q) * G * 4, TB::period(q) - 1, TB::width(q), T};
+        } else {
+            constexpr int e0 = (q == NP ? (T ? TB::WRT : TB::WR) : (T ? TB::WLT : TB::WL)) / 4;
+            return Piece{q == NP ? B.WR : B.WL, (unsigned)(C * C * G * 4), e0, C * C, C * G * 4, 0, C - 1, C, T};
         }
     }
-    __device__ void store(float* base, int tid) {
+    f4 v[NSLOT], pw, psa, psb, pan;
+    float pb1, pbL, pla;
+    int dst[NSLOT];   // the lane's f4 entry of slot s (-1: none)
+    // wave: the wave's index as a scalar
+    __device__ void load(const DevBlock& B, int wave, int lane, int dir) {
+        const int o = lane % C, k = lane / C, t = o + dir * k, t7 = t & (C - 1);
+        static_for<0, NSLOT>([&](auto s) {
+            Piece d{B.W1, 0u, 0, 0, 0, 0, 0, 0, false};   // no piece in this slot: no records, no entries
+            static_for<0, kClWaves>([&](auto j) {
+                constexpr int Q = kClWaves * decltype(s)::value + decltype(j)::value;
+                if constexpr (Q < NQ) {
+                    if (wave == j) d = piece<Q>(B);
+                }
+            });
+            const int row = d.transposed ? t7 : o, col = (d.transposed ? o : t) & d.pm;
+            const bool in_piece = lane < d.n;
+            const unsigned off = in_piece && col < d.width ? (unsigned)(row * d.stride + d.coff + col * (G * 4)) : kClNoStore;
+            v[s] = ClBuf(d.base, d.bytes).ld4(off);
+            dst[s] = in_piece ? d.e0 + lane : -1;
+        });
+        // per-channel parameters: [b1, bL, la, 0 | sa[4] | sb[4] | sigmoid(an)[4] | w[P]] per channel. A lane that owns nothing
+        // reads behind the array (no memory access, zeros)
+        constexpr int NW = C * P / 4;   // 16-byte vectors of the path weights [C][P]
+        const unsigned ow = wave == 0 && lane < NW ? 16u * lane : kClNoStore;
+        const unsigned ov = wave == 1 && lane < C ? 16u * lane : kClNoStore;
+        const unsigned os = wave == 2 && lane < C ? 4u * lane : kClNoStore;
+        pw = ClBuf(B.w, C * P * 4).ld4(ow);
+        psa = ClBuf(B.sa, C * G * 4).ld4(ov);
+        psb = ClBuf(B.sb, C * G * 4).ld4(ov);
+        pan = ClBuf(B.an, C * G * 4).ld4(ov);
+        pb1 = __builtin_bit_cast(float, ClBuf(B.has_b1 ? B.b1 : nullptr, C * 4).ldi(os));
+        pbL = __builtin_bit_cast(float, ClBuf(B.bL, C * 4).ldi(os));
+        pla = __builtin_bit_cast(float, ClBuf(B.la, C * 4).ldi(os));
+    }
+    __device__ void store(float* base, int wave, int lane) {
 #pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int e = tid + it * 64 * kClWaves;
-            if (e < NE) st4(base + 4 * e, live[it] ? v[it] : f4{0.f, 0.f, 0.f, 0.f});
+        for (int s = 0; s < NSLOT; ++s) {
+            if (dst[s] >= 0) st4(base + 4 * dst[s], v[s]);
         }
-#pragma unroll
-        for (int it = 0; it < NITP; ++it) {
-            const int e = tid + it * 64 * kClWaves;
-            if (sig[it]) pv[it] = sigmoidf(pv[it]);
-            if (e < NPAR) base[TB::par + e] = plive[it] ? pv[it] : 0.f;
+        float* par = base + TB::par;
+        constexpr int NW = C * P / 4;
+        if (wave == 0 && lane < NW) st4(par + (lane / (P / 4)) * kClParStride + 16 + 4 * (lane % (P / 4)), pw);
+        if (wave == 1 && lane < C) {
+            float* p = par + lane * kClParStride;
+            st4(p + 4, psa);
+            st4(p + 8, psb);
+            st4(p + 12, f4{sigmoidf(pan.x), sigmoidf(pan.y), sigmoidf(pan.z), sigmoidf(pan.w)});
         }
+        if (wave == 2 && lane < C) st4(par + lane * kClParStride, f4{pb1, pbL, pla, 0.f});
     }
 };
 
@@ -655,10 +688,6 @@ CSMPN_DEV void cl_block_backward(const float* ldsw, const float* ldsp, const ClF
 
 // ---------------------------------------------------------------------------------
 // per-lane row access: the lane's 8 blades = 32 contiguous bytes
-CSMPN_DEV void cl_ld8(float (&x)[8], const float* p) {
-    const f4 a = ld4(p), b = ld4(p + 4);
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-}
 CSMPN_DEV void cl_st8(float* p, const float (&x)[8]) {
     st4(p, f4{x[0], x[1], x[2], x[3]});
     st4(p + 4, f4{x[4], x[5], x[6], x[7]});
@@ -701,66 +730,94 @@ CSMPN_DEV void cl_scatter(const float* sc, int t_add, int t_sub, float* table, i
 }
 
 // ---------------------------------------------------------------------------------
+// The input arrays of a launch and the lane's byte offsets into their rows (worked out once per kernel).
+template <class ALG, int C, int MODE, int NA>
+struct ClIn {
+    static constexpr int D = ALG::D, RB = C * D * 4, AB = NA * D * 4;   // bytes of a full row / of an attribute row
+    ClBuf a, b, at;   // edge: h (gathered by target), h (by source), edge attributes (by permutation); node: h, agg, node attributes
+    ClBuf i0, i1, i2; // edge: a row's target, source, permutation; node: i0 = in-degree (no degrees: no records, reads 0 = scale 1)
+    unsigned rows;    // rows of the launch
+    unsigned lo, la;  // the lane's channel in a full row; in an attribute row: channel c mod period, clamped to a valid one
+                      // (its table entries are zero where it is not)
+    bool in_attr;     // c < NA: the lane owns a channel of the attribute gradient
+    // edge program: the attribute table is indexed by the permutation, and a launch may cover a SLICE of the edge list
+    // (graph segments, sharded layers) whose permutation points into the table of the whole list: its size is not the
+    // launch's to know. It keeps a 64-bit address (one multiply-add per tile) and no range check.
+    const float* attr;
+    CSMPN_DEV ClIn(const RowIO& io, int c) {
+        rows = (unsigned)io.rows;
+        lo = (unsigned)c * (D * 4);
+        const int ca = c & (cl_pow2_ge(NA > 0 ? NA : 1) - 1);
+        la = (unsigned)(ca < NA ? ca : NA - 1) * (D * 4);
+        in_attr = c < NA;
+        const size_t rb = (size_t)rows * RB, ib = (size_t)rows * 4;
+        if constexpr (MODE == MODE_EDGE) {
+            const size_t tb = (size_t)io.gather_rows * RB;
+            a = ClBuf(io.seg[0].a, tb); b = ClBuf(io.seg[0].b, tb);
+            i0 = ClBuf(io.seg[0].ia, ib); i1 = ClBuf(io.seg[0].ib, ib);
+            if constexpr (NA > 0) { attr = io.seg[1].a; i2 = ClBuf(io.seg[1].ia, ib); }
+        } else {
+            attr = nullptr;
+            a = ClBuf(io.seg[0].a, rb); b = ClBuf(io.seg[1].a, rb);
+            i0 = ClBuf(io.seg[1].deg, ib);
+            if constexpr (NA > 0) at = ClBuf(io.seg[2].a, (size_t)rows * AB);
+        }
+    }
+    // a lane's offset in a [rows, C, D] array of the launch. A row behind the last one lies behind the array: its store is
+    // dropped, its load reads zero
+    CSMPN_DEV unsigned row_off(unsigned row) const { return row * RB + lo; }
+};
+
 // tile bookkeeping shared by the kernels
-__device__ const int kClNoDegree = 1;   // what a tile reads as its degree when the launch has none (sum aggregation)
 template <int C, int MODE>
 struct ClTile {
-    long row, lrow;
+    unsigned row, lrow;
     bool valid;
     int i_dst, i_src, i_perm, deg;
     // mean aggregation. Worked out where it is used: taken at load time, the division waits out the degree's round trip in
     // front of the row requests that follow the load
     CSMPN_DEV float scale() const { return 1.0f / float(deg > 1 ? deg : 1); }
-    template <int NA>
-    CSMPN_DEV void load(const RowIO& io, long tile, int r) {
+    template <class ALG, int NA>
+    CSMPN_DEV void load(const ClIn<ALG, C, MODE, NA>& in, unsigned tile, int r) {
         row = tile * ClMap<C>::RPW + r;
-        valid = row < io.rows;
+        valid = row < in.rows;
         lrow = valid ? row : 0;   // lanes past the end compute on row 0 and contribute nothing
         i_dst = i_src = i_perm = 0;
         deg = 1;
         if constexpr (MODE == MODE_EDGE) {
-            i_dst = io.seg[0].ia[lrow];
-            i_src = io.seg[0].ib[lrow];
-            if constexpr (NA > 0) i_perm = io.seg[1].ia[lrow];
+            i_dst = in.i0.ldi(4 * lrow);
+            i_src = in.i1.ldi(4 * lrow);
+            if constexpr (NA > 0) i_perm = in.i2.ldi(4 * lrow);
         }
-        if constexpr (MODE == MODE_NODE) {   // mean aggregation
-            // loaded without a branch (no degrees: the constant 1): a load under a branch is waited for at the end of
-            // the branch, in front of the row requests
-            deg = *(io.seg[1].deg ? io.seg[1].deg + lrow : &kClNoDegree);
-        }
+        if constexpr (MODE == MODE_NODE) deg = in.i0.ldi(4 * lrow);   // mean aggregation
     }
 };
 
 // The gathered input passes of block 0, in two steps so that every load of a tile is in flight at once (left to the
 // scheduler, the attribute loads were issued behind the wait for the feature rows: three dependent round trips per
-// tile at two waves per SIMD). issue: raw 16-byte pieces; finish: x[p] = this lane's channel of pass p (attribute
-// passes: channel c mod period, clamped to a valid one - its table entries are zero where it is not).
+// tile at two waves per SIMD). issue: raw 16-byte pieces; finish: x[p] = this lane's channel of pass p.
 template <class ALG, int C, int MODE, int NA>
 struct ClRaw {
     static constexpr int NSEG = MODE == MODE_EDGE ? 2 : 2;   // edge: h[dst], h[src]; node: h, agg
+    using IN = ClIn<ALG, C, MODE, NA>;
     f4 v[2 * (NSEG + (NA > 0 ? 1 : 0))];
-    template <class TB>
-    CSMPN_DEV void issue(const RowIO& io, const ClTile<C, MODE>& T, int c) {
-        constexpr int D = ALG::D, ROW = C * D;
-        const float *p0, *p1, *p2 = nullptr;
+    CSMPN_DEV void issue(const IN& in, const ClTile<C, MODE>& T) {
+        unsigned o0, o1, o2 = 0;
         if constexpr (MODE == MODE_EDGE) {
-            p0 = io.seg[0].a + (size_t)T.i_dst * ROW + c * D;
-            p1 = io.seg[0].b + (size_t)T.i_src * ROW + c * D;
-            if constexpr (NA > 0) {
-                const int ca = c & (TB::period(1) - 1);
-                p2 = io.seg[1].a + (size_t)T.i_perm * (NA * D) + (ca < NA ? ca : NA - 1) * D;
-            }
+            o0 = (unsigned)T.i_dst * IN::RB + in.lo;
+            o1 = (unsigned)T.i_src * IN::RB + in.lo;
         } else {
-            p0 = io.seg[0].a + (size_t)T.lrow * ROW + c * D;
-            p1 = io.seg[1].a + (size_t)T.lrow * ROW + c * D;
-            if constexpr (NA > 0) {
-                const int ca = c & (TB::period(2) - 1);
-                p2 = io.seg[2].a + (size_t)T.lrow * (NA * D) + (ca < NA ? ca : NA - 1) * D;
-            }
+            o0 = o1 = in.row_off(T.lrow);
+            if constexpr (NA > 0) o2 = T.lrow * IN::AB + in.la;
         }
-        v[0] = ld4(p0); v[1] = ld4(p0 + 4);
-        v[2] = ld4(p1); v[3] = ld4(p1 + 4);
-        if constexpr (NA > 0) { v[4] = ld4(p2); v[5] = ld4(p2 + 4); }
+        v[0] = in.a.ld4(o0); v[1] = in.a.ld4(o0 + 16);
+        v[2] = in.b.ld4(o1); v[3] = in.b.ld4(o1 + 16);
+        if constexpr (NA > 0 && MODE == MODE_EDGE) {
+            const float* p2 = in.attr + ((size_t)(unsigned)T.i_perm * (IN::AB / 4) + in.la / 4);
+            v[4] = ld4(p2); v[5] = ld4(p2 + 4);
+        } else if constexpr (NA > 0) {
+            v[4] = in.at.ld4(o2); v[5] = in.at.ld4(o2 + 16);
+        }
     }
     // all of them requested before the first is used
     CSMPN_DEV void pin() {
@@ -805,40 +862,52 @@ __global__ void __launch_bounds__(64 * kClWaves, 4) cemlp_cl_fwd_kernel(const De
     constexpr int kBatch = 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* lds = smem;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // the wave index as the scalar it is: tile numbers, the loop and the tile's part of an offset stay on the scalar unit
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int c = MP::chan(lane), r = MP::row(lane);
     float* sc = lds + tab_floats + wave * (RPW * SS);   // scatter staging tile (edge program)
     ClStamp stamp(0);
+    using IN = ClIn<ALG, C, MODE, NA>;
+    constexpr int RB = IN::RB;
+    const IN in(io, c);
     const float* ldsw0 = lds + 4 * c;
     const float* ldsp0 = lds + kClParStride * c;
     const float* ldsw1 = ldsw0 + T0::total;
     const float* ldsp1 = ldsp0 + T0::total;
 
-    const long ntiles = (io.rows + RPW - 1) / RPW;
-    const long tstride = (long)gridDim.x * kClWaves;
+    const unsigned ntiles = (in.rows + RPW - 1) / RPW;
+    const unsigned tstride = gridDim.x * kClWaves;
     const bool save_s = NBLK > 1 && io.save_state != 0 && io.save != nullptr;
+    // outputs: [rows, C, D] arrays (a row behind the last one is dropped by the range check) and the state regions
+    const size_t row_bytes = (size_t)in.rows * RB, state_bytes = state_rows(io.rows) * (size_t)RB;
+    const ClBuf b_save(io.save, row_bytes);
+    const ClBuf b_s0(save_s ? io.save + state_region<ROW, ROW>(io.rows, 0, 0) : nullptr, state_bytes);
+    const ClBuf b_s1(save_s ? io.save + state_region<ROW, ROW>(io.rows, 0, 1) : nullptr, state_bytes);
+    const ClBuf b_out(MODE == MODE_EDGE ? (io.row_store ? io.agg : nullptr) : io.y, row_bytes);
+    const ClBuf b_res(MODE == MODE_NODE ? io.resid : nullptr, row_bytes);
+    const unsigned st_lane = cl_state_lane<C>(r, c);
     // Software pipeline over the wave's tiles: the row pieces of tile t + 1 are requested (all together) BEFORE the stores
     // and atomics of tile t - vmcnt counts in issue order, a load behind an atomic waits for its acknowledgement
     // (~3000 cycles under load) - and the indices of tile t + 2 travel while tile t + 1 computes.
-    const long tile0 = (long)blockIdx.x * kClWaves + wave;
+    const unsigned tile0 = blockIdx.x * kClWaves + wave;
     ClTile<C, MODE> T, Tn;
-    T.template load<NA>(io, tile0, r);
+    T.load(in, tile0, r);
     ClRaw<ALG, C, MODE, NA> raw;
-    raw.template issue<T0>(io, T, c);
-    Tn.template load<NA>(io, tile0 + tstride, r);
+    raw.issue(in, T);
+    Tn.load(in, tile0 + tstride, r);
     // the first tile's rows travel while the tables are staged
     {
         const int dir = cl_probe_dir<C>(c);
         ClStage<ALG, C, T0, false> st0;
         ClStage<ALG, C, T1, false> st1;
-        st0.load(Cd.b[0], threadIdx.x, dir);
-        if constexpr (NBLK > 1) st1.load(Cd.b[1], threadIdx.x, dir);
-        st0.store(lds, threadIdx.x);
-        if constexpr (NBLK > 1) st1.store(lds + T0::total, threadIdx.x);
+        st0.load(Cd.b[0], wave, lane, dir);
+        if constexpr (NBLK > 1) st1.load(Cd.b[1], wave, lane, dir);
+        st0.store(lds, wave, lane);
+        if constexpr (NBLK > 1) st1.store(lds + T0::total, wave, lane);
     }
     __syncthreads();
     stamp(0);
-    for (long tile = tile0; tile < ntiles; tile += tstride) {
+    for (unsigned tile = tile0; tile < ntiles; tile += tstride) {
         raw.pin();
         stamp(1);
         // the residual row is requested here (most likely a cache hit: the node program has just read it as its first
@@ -846,10 +915,12 @@ __global__ void __launch_bounds__(64 * kClWaves, 4) cemlp_cl_fwd_kernel(const De
         f4 res0, res1;
         if constexpr (MODE == MODE_NODE) {
             if (io.resid) {
-                const float* pr_ = io.resid + (size_t)T.lrow * ROW + c * D;
-                res0 = ld4(pr_); res1 = ld4(pr_ + 4);
+                const unsigned o = in.row_off(T.lrow);
+                res0 = b_res.ld4(o); res1 = b_res.ld4(o + 16);
             }
         }
+        // the lane's place in the tile's state pieces; the rows behind the last one share their tile with valid rows: no store
+        const unsigned st_off = T.valid ? tile * kClStateTile + st_lane : kClNoStore;
         float out[D], in1[D];
         {
             float x[T0::NP][D];
@@ -860,10 +931,9 @@ __global__ void __launch_bounds__(64 * kClWaves, 4) cemlp_cl_fwd_kernel(const De
             static_for<0, T0::NP>([&](auto p) { cl_mix<C, T0::period(p), T0::W1(p), kBatch>(S.y, x[p], ldsw0); });
             stamp(2);
             cl_block_tail<ALG, C, T0, kBatch>(ldsw0, ldsp0, S, out, stamp, 3);
-            if (save_s && T.valid) {   // CSMPN_FLAG_SAVE_STATE: s of block 0 -> its state region (cemlp_device.hpp): whole tiles, two pieces per lane
-                float* ps_ = io.save + state_region<ROW, ROW>(io.rows, 0, 0) + cl_state_off<C>(T.row, c);
-                __builtin_nontemporal_store(f4{S.s[0], S.s[1], S.s[2], S.s[3]}, reinterpret_cast<f4*>(ps_));       // streaming: read once, by the backward
-                __builtin_nontemporal_store(f4{S.s[4], S.s[5], S.s[6], S.s[7]}, reinterpret_cast<f4*>(ps_ + 256));
+            if (save_s) {   // CSMPN_FLAG_SAVE_STATE: s of block 0 -> its state region (cemlp_device.hpp): whole tiles, two pieces per lane
+                b_s0.template st4<kClStream>(st_off, f4{S.s[0], S.s[1], S.s[2], S.s[3]});       // streaming: read once, by the backward
+                b_s0.template st4<kClStream>(st_off + kClStatePiece, f4{S.s[4], S.s[5], S.s[6], S.s[7]});
             }
         }
         if constexpr (NBLK > 1) {
@@ -875,36 +945,36 @@ __global__ void __launch_bounds__(64 * kClWaves, 4) cemlp_cl_fwd_kernel(const De
             cl_mix<C, C, T1::W1(0), kBatch>(S.y, in1, ldsw1);
             stamp(8);
             cl_block_tail<ALG, C, T1, kBatch>(ldsw1, ldsp1, S, out, stamp, 9);
-            if (save_s && T.valid) {   // ... s of block 1
-                float* ps_ = io.save + state_region<ROW, ROW>(io.rows, 0, 1) + cl_state_off<C>(T.row, c);
-                __builtin_nontemporal_store(f4{S.s[0], S.s[1], S.s[2], S.s[3]}, reinterpret_cast<f4*>(ps_));       // streaming: read once, by the backward
-                __builtin_nontemporal_store(f4{S.s[4], S.s[5], S.s[6], S.s[7]}, reinterpret_cast<f4*>(ps_ + 256));
+            if (save_s) {   // ... s of block 1
+                b_s1.template st4<kClStream>(st_off, f4{S.s[0], S.s[1], S.s[2], S.s[3]});
+                b_s1.template st4<kClStream>(st_off + kClStatePiece, f4{S.s[4], S.s[5], S.s[6], S.s[7]});
             }
         }
         // next tile's rows, then this tile's stores
         const ClTile<C, MODE> Tc = T;
         T = Tn;
-        raw.template issue<T0>(io, T, c);
-        Tn.template load<NA>(io, tile + 2 * tstride, r);
+        raw.issue(in, T);
+        Tn.load(in, tile + 2 * tstride, r);
+        const unsigned o_row = in.row_off(Tc.row);
         if constexpr (NBLK > 1) {
-            if (io.save && Tc.valid) cl_st8(io.save + (size_t)Tc.row * ROW + c * D, in1);
+            if (io.save) b_save.st8(o_row, in1);
         }
         if constexpr (MODE == MODE_EDGE) {
             if (io.row_store) {
-                if (Tc.valid) cl_st8(io.agg + (size_t)Tc.lrow * ROW + c * D, out);
+                b_out.st8(o_row, out);
             } else {
                 CL_LDS_ORDER();
                 cl_st8(sc + r * SS + c * D, out);
                 CL_LDS_ORDER();
                 cl_scatter<C, ROW, false>(sc, Tc.valid ? Tc.i_dst : -1, -1, io.agg, lane);
             }
-        } else if (Tc.valid) {
+        } else {
             if (io.resid) {
                 const float res[D] = {res0.x, res0.y, res0.z, res0.w, res1.x, res1.y, res1.z, res1.w};
 #pragma unroll
                 for (int d = 0; d < D; ++d) out[d] += res[d];
             }
-            cl_st8(io.y + (size_t)Tc.row * ROW + c * D, out);
+            b_out.st8(o_row, out);
         }
         stamp(14);
     }
@@ -921,6 +991,35 @@ constexpr size_t cl_fwd_lds_bytes() {
 // gathers it by target) or from the hand-over rows io.handover; d/d(input of block K) goes to the hand-over rows (K > 0)
 // or to the program's gradient targets (K = 0). Block K > 0 reads its input from the saved rows.
 struct ClCarry { f4 a, b; };
+// The arrays of a backward launch beside its inputs, and the lane's offsets into them.
+template <class ALG, int C, int MODE, int NA>
+struct ClBwdIn : ClIn<ALG, C, MODE, NA> {
+    using IN = ClIn<ALG, C, MODE, NA>;
+    static constexpr int ROW = C * ALG::D;
+    // d/d(out) (edge: [N] rows gathered by target) and the state regions. The arrays one block alone touches - saved block
+    // inputs, hand-over rows, gradient targets - are built by that block: resources are four scalar registers each, and
+    // with all of a launch's alive at once the backward runs out of them
+    ClBuf gy, st0, st1;
+    unsigned st_lane, st_row0;      // the lane's place in a tile's state piece; row 0's place (the rows behind the last one read it)
+    CSMPN_DEV ClBwdIn(const RowIO& io, int c, int r) : IN(io, c) {
+        const size_t rb = (size_t)this->rows * IN::RB, sb = state_rows(io.rows) * (size_t)IN::RB;
+        gy = ClBuf(io.gy, MODE == MODE_EDGE ? (size_t)io.gather_rows * IN::RB : rb);
+        st0 = ClBuf(io.saved + state_region<ROW, ROW>(io.rows, 0, 0), io.save_state ? sb : 0);
+        st1 = ClBuf(io.saved + state_region<ROW, ROW>(io.rows, 0, 1), io.save_state ? sb : 0);
+        st_lane = cl_state_lane<C>(r, c);
+        st_row0 = cl_state_lane<C>(0, c);
+    }
+    // d/d(out) of the last block: a row behind the last one reads zero (it contributes nothing to any sum)
+    CSMPN_DEV unsigned gy_off(const ClTile<C, MODE>& T) const {
+        if constexpr (MODE == MODE_EDGE) return T.valid ? (unsigned)T.i_dst * IN::RB + this->lo : kClNoStore;
+        else return this->row_off(T.row);
+    }
+    template <int K>
+    CSMPN_DEV const ClBuf& state() const { if constexpr (K == 0) return st0; else return st1; }
+    CSMPN_DEV unsigned state_off(const ClTile<C, MODE>& T) const {
+        return T.valid ? (T.row / ClMap<C>::RPW) * kClStateTile + st_lane : st_row0;
+    }
+};
 // What the first tile of a block reads from global memory, requested BEFORE the block starts: the last block's ahead of the
 // table staging (as the forward does), block 0's - with one tile per wave - ahead of the end phase of the block in front
 // of it. With one tile per wave every global round trip is exposed once per launch; here they travel behind work that
@@ -930,22 +1029,22 @@ struct ClBwdReq {
     f4 g0, g1, s0, s1, t0, t1;
     ClRaw<ALG, C, MODE, NA> raw;
     template <int K>
-    CSMPN_DEV void request(const RowIO& io, const ClTile<C, MODE>& Tl, int c) {
-        constexpr int D = ALG::D, ROW = C * D;
+    CSMPN_DEV void request(const RowIO& io, const ClBwdIn<ALG, C, MODE, NA>& in, const ClTile<C, MODE>& Tl) {
         if constexpr (K == NBLK - 1) {
-            const float* gsrc = io.gy + (size_t)(MODE == MODE_EDGE ? (long)Tl.i_dst : Tl.lrow) * ROW + c * D;
-            g0 = ld4(gsrc); g1 = ld4(gsrc + 4);
+            const unsigned o = in.gy_off(Tl);
+            g0 = in.gy.ld4(o); g1 = in.gy.ld4(o + 16);
         }
         if constexpr (K == 0) {
-            raw.template issue<ClTab<C, MODE, NA, 0, true>>(io, Tl, c);
+            raw.issue(in, Tl);
         } else {
-            const float* sp = io.saved + (size_t)Tl.lrow * ROW + c * D;
-            s0 = ld4(sp); s1 = ld4(sp + 4);
+            const ClBuf saved(io.saved, (size_t)in.rows * ClBwdIn<ALG, C, MODE, NA>::RB);
+            const unsigned o = in.row_off(Tl.lrow);
+            s0 = saved.ld4(o); s1 = saved.ld4(o + 16);
         }
         if constexpr (SAVES) {   // the block's saved state (row 0's for a wave without a tile: never used)
-            const float* ps_ = io.saved + state_region<ROW, ROW>(io.rows, 0, K) + cl_state_off<C>(Tl.lrow, c);
-            t0 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ps_));
-            t1 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ps_ + 256));
+            const unsigned o = in.state_off(Tl);
+            t0 = in.template state<K>().template ld4<kClStream>(o);
+            t1 = in.template state<K>().template ld4<kClStream>(o + kClStatePiece);
         }
     }
     // block 0's requests have arrived (placed in front of stores whose acknowledgement nobody has to wait for: vmcnt counts
@@ -960,7 +1059,7 @@ struct ClBwdReq {
 // per launch). cur: the block's row registers; they hold the requests of T0 already for the last block and, when SINGLE,
 // for every block. next: when SINGLE, receives the requests of T0 for block K - 1.
 template <class ALG, int C, int MODE, int NBLK, int NA, int K, bool SAVES, bool SINGLE>
-CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const ClTile<C, MODE>& T0,
+CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, const ClBwdIn<ALG, C, MODE, NA>& in, float* tab, float* work, const ClTile<C, MODE>& T0,
                                ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES>& cur,
                                ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES>& next, const ClCarry carry_in, ClStamp& stamp) {
     constexpr bool single = SINGLE, have_pre = SINGLE || K == NBLK - 1;
@@ -976,7 +1075,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
     constexpr int img_max = NBLK > 1 && ClPart<ALG, C, C>::total > ClPart<ALG, C, ClTab<C, MODE, NA, 0, true>::I>::total
                                 ? ClPart<ALG, C, C>::total : ClPart<ALG, C, ClTab<C, MODE, NA, 0, true>::I>::total;
     constexpr int scratch = (RPW * SS > img_max ? RPW * SS : img_max);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int c = MP::chan(lane), r = MP::row(lane);
     float* sc = work + wave * scratch;
     const float* ldsw = tab + 4 * c;
@@ -993,36 +1092,48 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
         for (int p = 0; p < NP; ++p) accW1[p][g] = f4{0.f, 0.f, 0.f, 0.f};
     }
 
-    const long ntiles = (io.rows + RPW - 1) / RPW;
-    const long tstride = (long)gridDim.x * kClWaves;
+    using IN = ClBwdIn<ALG, C, MODE, NA>;
+    // this block's own arrays: saved block inputs and hand-over rows; gradient targets written by row (edge gx[0]: the
+    // deterministic mode's [rows] table)
+    const size_t row_bytes = (size_t)in.rows * IN::RB, attr_bytes = (size_t)in.rows * IN::AB;
+    const ClBuf b_saved(K > 0 ? io.saved : nullptr, row_bytes);
+    const ClBuf b_hand(NBLK > 1 && !single ? io.handover : nullptr, row_bytes);
+    const ClBuf b_gx0(K > 0 ? nullptr : (MODE == MODE_EDGE && !io.row_store ? nullptr : io.gx[0]), row_bytes);
+    const ClBuf b_gx1(K > 0 || MODE == MODE_EDGE ? nullptr : io.gx[1], row_bytes);
+    const ClBuf b_gx2(K > 0 || MODE == MODE_EDGE ? nullptr : io.gx[2], attr_bytes);
+    const unsigned ntiles = (in.rows + RPW - 1) / RPW;
+    const unsigned tstride = gridDim.x * kClWaves;
     // Software pipeline as in the forward: the rows of tile t + 1 are requested in front of the stores / atomics of tile t.
     f4 &g0 = cur.g0, &g1 = cur.g1, &s0 = cur.s0, &s1 = cur.s1, &t0 = cur.t0, &t1 = cur.t1;
     ClRaw<ALG, C, MODE, NA>& raw = cur.raw;
     auto issue = [&](const ClTile<C, MODE>& Tl) {
-        const float* gsrc = (kLast ? io.gy + (size_t)(MODE == MODE_EDGE ? (long)Tl.i_dst : Tl.lrow) * ROW
-                                   : io.handover + (size_t)Tl.lrow * ROW) + c * D;
-        if constexpr (kLast || !single) {
-            g0 = ld4(gsrc); g1 = ld4(gsrc + 4);
+        // d/d(out): zero for a row behind the last one (the hand-over rows end where the rows end)
+        if constexpr (kLast) {
+            const unsigned o = in.gy_off(Tl);
+            g0 = in.gy.ld4(o); g1 = in.gy.ld4(o + 16);
+        } else if constexpr (!single) {
+            const unsigned o = in.row_off(Tl.row);
+            g0 = b_hand.ld4(o); g1 = b_hand.ld4(o + 16);
         } else {   // one tile per wave: d/d(out) of this block stayed in registers
             g0 = carry_a; g1 = carry_b;
         }
         if constexpr (K == 0) {
-            raw.template issue<TB>(io, Tl, c);
+            raw.issue(in, Tl);
         } else {
-            const float* sp = io.saved + (size_t)Tl.lrow * ROW + c * D;
-            s0 = ld4(sp); s1 = ld4(sp + 4);
+            const unsigned o = in.row_off(Tl.lrow);
+            s0 = b_saved.ld4(o); s1 = b_saved.ld4(o + 16);
         }
     };
-    const long tile0 = (long)blockIdx.x * kClWaves + wave;
+    const unsigned tile0 = blockIdx.x * kClWaves + wave;
     ClTile<C, MODE> T = T0, Tn = T0;
     if constexpr (have_pre) {
         if constexpr (!kLast) { g0 = carry_a; g1 = carry_b; }
     } else {
         issue(T);
     }
-    if constexpr (!single) Tn.template load<NA>(io, tile0 + tstride, r);
+    if constexpr (!single) Tn.load(in, tile0 + tstride, r);
     stamp(20);
-    for (long tile = tile0; tile < ntiles; tile += tstride) {
+    for (unsigned tile = tile0; tile < ntiles; tile += tstride) {
         if constexpr (K == 0) {
             asm volatile("" : "+v"(g0), "+v"(g1));
             raw.pin();
@@ -1038,10 +1149,6 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
         } else {
             x[0][0] = s0.x; x[0][1] = s0.y; x[0][2] = s0.z; x[0][3] = s0.w; x[0][4] = s1.x; x[0][5] = s1.y; x[0][6] = s1.z; x[0][7] = s1.w;
         }
-        if (!Tc.valid) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) gout[d] = 0.f;
-        }
         float gy[D];
         {
             ClFwd S;
@@ -1050,9 +1157,9 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
             constexpr bool have_s = SAVES;   // compile time: a run-time switch between the two recomputes spills the node program
             if constexpr (have_s) {   // CSMPN_FLAG_SAVE_STATE: the block's output in front of the layer norm, saved by the forward
                 if (!have_pre || (!single && tile != tile0)) {
-                    const float* ps_ = io.saved + state_region<ROW, ROW>(io.rows, 0, K) + cl_state_off<C>(Tc.lrow, c);
-                    t0 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ps_));
-                    t1 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ps_ + 256));
+                    const unsigned o = in.state_off(Tc);
+                    t0 = in.template state<K>().template ld4<kClStream>(o);
+                    t1 = in.template state<K>().template ld4<kClStream>(o + kClStatePiece);
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { S.s[i] = t0[i]; S.s[4 + i] = t1[i]; }
@@ -1068,8 +1175,8 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
         f4 res0, res1;
         if constexpr (K == 0 && MODE == MODE_NODE && single) {
             if (io.gx[0] && io.resid_bwd) {
-                const float* pr_ = io.gy + (size_t)Tc.lrow * ROW + c * D;
-                res0 = ld4(pr_); res1 = ld4(pr_ + 4);
+                const unsigned o = in.row_off(Tc.row);
+                res0 = in.gy.ld4(o); res1 = in.gy.ld4(o + 16);
             }
         }
         // MVLinear weight gradient: A = gy, B = the pass's input blade
@@ -1085,9 +1192,11 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
         if constexpr (!single) {
             T = Tn;
             issue(T);
-            Tn.template load<NA>(io, tile + 2 * tstride, r);
+            Tn.load(in, tile + 2 * tstride, r);
         }
-        // d/d(input)
+        // d/d(input): a row behind the last one lies behind its array (no store); the attribute gradient is stored by the
+        // lanes that own one of its channels
+        const unsigned o_row = in.row_off(Tc.row);
         if constexpr (K > 0) {
             float gx[D];
 #pragma unroll
@@ -1095,8 +1204,8 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
             cl_mix<C, C, TB::W1T(0)>(gx, gy, ldsw);
             if constexpr (single) {
                 carry_a = f4{gx[0], gx[1], gx[2], gx[3]}; carry_b = f4{gx[4], gx[5], gx[6], gx[7]};
-            } else if (Tc.valid) {
-                cl_st8(io.handover + (size_t)Tc.row * ROW + c * D, gx);
+            } else {
+                b_hand.st8(o_row, gx);
             }
         } else if constexpr (MODE == MODE_EDGE) {
             if (io.gx[0]) {
@@ -1105,7 +1214,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
                 for (int d = 0; d < D; ++d) gx[d] = 0.f;
                 cl_mix<C, C, TB::W1T(0)>(gx, gy, ldsw);
                 if (io.row_store) {
-                    if (Tc.valid) cl_st8(io.gx[0] + (size_t)Tc.lrow * ROW + c * D, gx);
+                    b_gx0.st8(o_row, gx);
                 } else {
                     CL_LDS_ORDER();
                     cl_st8(sc + r * SS + c * D, gx);
@@ -1119,7 +1228,8 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
 #pragma unroll
                     for (int d = 0; d < D; ++d) gx[d] = 0.f;
                     cl_mix<C, C, TB::W1T(1)>(gx, gy, ldsw);
-                    if (Tc.valid && c < NA) cl_st8(io.gx[1] + (size_t)Tc.i_perm * (NA * D) + c * D, gx);
+                    // by permutation into a table the launch may cover a slice of (ClIn::attr): 64-bit address, one branch
+                    if (Tc.valid && in.in_attr) cl_st8(io.gx[1] + ((size_t)(unsigned)Tc.i_perm * (NA * D) + c * D), gx);
                 }
             }
         } else {
@@ -1128,18 +1238,13 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
 #pragma unroll
                 for (int d = 0; d < D; ++d) gx[d] = 0.f;
                 cl_mix<C, C, TB::W1T(0)>(gx, gy, ldsw);
-                if (Tc.valid) {
-                    if (io.resid_bwd) {
-                        if constexpr (!single) {
-                            const float* pr_ = io.gy + (size_t)Tc.row * ROW + c * D;
-                            res0 = ld4(pr_); res1 = ld4(pr_ + 4);
-                        }
-                        const float res[D] = {res0.x, res0.y, res0.z, res0.w, res1.x, res1.y, res1.z, res1.w};
+                if (io.resid_bwd) {
+                    if constexpr (!single) { res0 = in.gy.ld4(o_row); res1 = in.gy.ld4(o_row + 16); }
+                    const float res[D] = {res0.x, res0.y, res0.z, res0.w, res1.x, res1.y, res1.z, res1.w};
 #pragma unroll
-                        for (int d = 0; d < D; ++d) gx[d] += res[d];
-                    }
-                    cl_st8(io.gx[0] + (size_t)Tc.row * ROW + c * D, gx);
+                    for (int d = 0; d < D; ++d) gx[d] += res[d];
                 }
+                b_gx0.st8(o_row, gx);
             }
             if (io.gx[1]) {
                 float gx[D];
@@ -1148,7 +1253,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
                 cl_mix<C, C, TB::W1T(1)>(gx, gy, ldsw);
 #pragma unroll
                 for (int d = 0; d < D; ++d) gx[d] *= Tc.scale();
-                if (Tc.valid) cl_st8(io.gx[1] + (size_t)Tc.row * ROW + c * D, gx);
+                b_gx1.st8(o_row, gx);
             }
             if constexpr (NA > 0) {
                 if (io.gx[2]) {
@@ -1156,7 +1261,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
 #pragma unroll
                     for (int d = 0; d < D; ++d) gx[d] = 0.f;
                     cl_mix<C, C, TB::W1T(2)>(gx, gy, ldsw);
-                    if (Tc.valid && c < NA) cl_st8(io.gx[2] + (size_t)Tc.row * (NA * D) + c * D, gx);
+                    b_gx2.st8(in.in_attr ? Tc.row * IN::AB + in.lo : kClNoStore, gx);
                 }
             }
         }
@@ -1164,7 +1269,7 @@ CSMPN_DEV ClCarry cl_bwd_block(const RowIO& io, float* tab, float* work, const C
         if constexpr (single) break;
     }
     // one tile per wave: block K - 1 works on the same tile; its rows travel during this block's end phase
-    if constexpr (K > 0 && single) next.template request<K - 1>(io, T0, c);
+    if constexpr (K > 0 && single) next.template request<K - 1>(io, in, T0);
 
     // ---- end of the block: the weight-gradient tiles of this wave -> image of the slice in its scratch; behind ONE barrier
     // the workgroup adds its four images in wave order and writes the matrices of its slice (coalesced 16-byte stores),
@@ -1281,7 +1386,7 @@ constexpr size_t cl_bwd_lds_bytes() {
 }
 // the blocks of a backward launch, last block first
 template <class ALG, int C, int MODE, int NBLK, int NA, bool SAVES, bool SINGLE>
-CSMPN_DEV void cl_bwd_blocks(const RowIO& io, float* smem, const ClTile<C, MODE>& T0, ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES>& req,
+CSMPN_DEV void cl_bwd_blocks(const RowIO& io, const ClBwdIn<ALG, C, MODE, NA>& in, float* smem, const ClTile<C, MODE>& T0, ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES>& req,
                              ClStamp& stamp) {
     using TB0 = ClTab<C, MODE, NA, 0, true>;
     using TB1 = ClTab<C, MODE, NA, 1, true>;
@@ -1292,17 +1397,17 @@ CSMPN_DEV void cl_bwd_blocks(const RowIO& io, float* smem, const ClTile<C, MODE>
         // ahead of its end phase when SINGLE, else block 0 requests into them itself. Block 0 has no block behind it: the
         // struct passed as its `next` is never written.
         ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES> req0;
-        carry = cl_bwd_block<ALG, C, MODE, NBLK, NA, 1, SAVES, SINGLE>(io, smem + TB0::total, smem + tabs, T0, req, req0, carry, stamp);
+        carry = cl_bwd_block<ALG, C, MODE, NBLK, NA, 1, SAVES, SINGLE>(io, in, smem + TB0::total, smem + tabs, T0, req, req0, carry, stamp);
         // this wave's hand-over rows have left for L2. With one tile per wave there are none: the only stores in flight
         // are the workgroup's block-1 slice, which nobody reads in this launch
         if constexpr (!SINGLE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         stamp(18);
         __syncthreads();                                   // ... and every wave is done with the images
         stamp(19);
-        cl_bwd_block<ALG, C, MODE, NBLK, NA, 0, SAVES, SINGLE>(io, smem, smem + tabs, T0, req0, req, carry, stamp);
+        cl_bwd_block<ALG, C, MODE, NBLK, NA, 0, SAVES, SINGLE>(io, in, smem, smem + tabs, T0, req0, req, carry, stamp);
     } else {
         // one block: it is the last one, `req` holds its requests; `next` (the same struct) is never written
-        cl_bwd_block<ALG, C, MODE, NBLK, NA, 0, SAVES, SINGLE>(io, smem, smem + tabs, T0, req, req, carry, stamp);
+        cl_bwd_block<ALG, C, MODE, NBLK, NA, 0, SAVES, SINGLE>(io, in, smem, smem + tabs, T0, req, req, carry, stamp);
     }
 }
 // The backward kernel: the blocks one after the other (last block first) in ONE launch. A wave keeps its tiles from
@@ -1319,29 +1424,29 @@ __global__ void __launch_bounds__(64 * kClWaves, 2) cemlp_cl_bwd_kernel(const De
     using TB1 = ClTab<C, MODE, NA, 1, true>;
     constexpr int tabs = TB0::total + (NBLK > 1 ? TB1::total : 0);
     // the wave's first tile: its indices once for all blocks, the last block's rows on their way while the tables are staged
+    const int lane = threadIdx.x & 63;
+    const ClBwdIn<ALG, C, MODE, NA> in(io, ClMap<C>::chan(lane), ClMap<C>::row(lane));
     ClTile<C, MODE> T0;
     ClBwdReq<ALG, C, MODE, NBLK, NA, SAVES> req;
-    {
-        const int lane = threadIdx.x & 63;
-        T0.template load<NA>(io, (long)blockIdx.x * kClWaves + (threadIdx.x >> 6), ClMap<C>::row(lane));
-        req.template request<NBLK - 1>(io, T0, ClMap<C>::chan(lane));
-    }
+    T0.load(in, blockIdx.x * kClWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), ClMap<C>::row(lane));
+    req.template request<NBLK - 1>(io, in, T0);
     // the tables of every block are staged up front (one prologue per launch)
     {
-        const int dir = cl_probe_dir<C>(ClMap<C>::chan(threadIdx.x & 63));
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const int dir = cl_probe_dir<C>(ClMap<C>::chan(lane));
         ClStage<ALG, C, TB0, true> st0;
         ClStage<ALG, C, TB1, true> st1;
-        st0.load(Cd.b[0], threadIdx.x, dir);
-        if constexpr (NBLK > 1) st1.load(Cd.b[1], threadIdx.x, dir);
-        st0.store(smem, threadIdx.x);
-        if constexpr (NBLK > 1) st1.store(smem + TB0::total, threadIdx.x);
+        st0.load(Cd.b[0], wave, lane, dir);
+        if constexpr (NBLK > 1) st1.load(Cd.b[1], wave, lane, dir);
+        st0.store(smem, wave, lane);
+        if constexpr (NBLK > 1) st1.store(smem + TB0::total, wave, lane);
     }
     __syncthreads();
     stamp(0);
-    const long ntiles = (io.rows + ClMap<C>::RPW - 1) / ClMap<C>::RPW;
+    const unsigned ntiles = (in.rows + ClMap<C>::RPW - 1) / ClMap<C>::RPW;
     // one tile per wave (uniform over the grid): the hand-over stays in registers, every block's rows are requested ahead
-    if (ntiles <= (long)gridDim.x * kClWaves) cl_bwd_blocks<ALG, C, MODE, NBLK, NA, SAVES, true>(io, smem, T0, req, stamp);
-    else cl_bwd_blocks<ALG, C, MODE, NBLK, NA, SAVES, false>(io, smem, T0, req, stamp);
+    if (ntiles <= gridDim.x * kClWaves) cl_bwd_blocks<ALG, C, MODE, NBLK, NA, SAVES, true>(io, in, smem, T0, req, stamp);
+    else cl_bwd_blocks<ALG, C, MODE, NBLK, NA, SAVES, false>(io, in, smem, T0, req, stamp);
     stamp.flush(io.stamps, threadIdx.x & 63);
 }
 

@@ -134,6 +134,9 @@ struct RowIO {
     // and stored as row r / emb_nperm of y; the backward reads d/d(out) there. emb_nperm = 0: off.
     const int* emb_verts;
     int emb_nperm, emb_nv, emb_k, emb_nrows;   // emb_nrows = S: vertex ids are clamped into [0, S) (memory safety; the entry point range-checks)
+    // EDGE: rows N of the node tables the program gathers from (seg[0]) and scatters into (agg, g_agg, gx[0]). cemlp_cl.hpp
+    // addresses every array with 32-bit byte offsets: its eligibility check and its buffer ranges need the tables' size.
+    long gather_rows;
 };
 
 // Storage variants of the row-tile buffers (compile time, so that the LDS variants use

@@ -7,6 +7,10 @@ namespace csmpn {
 namespace {
 using ALG_T = Alg<CSMPN_ALG_N, CSMPN_ALG_NEG>;
 static_assert(kClSliceCap == kClMaxBwdGroups, "the host sizes the partial buffer for the slices the kernels lay it out for");
+static_assert(kClNoStore >= kClMaxArrayBytes && kClNoStore <= 0xFFFFFFFFull - 0xFFFF, "the no-store offset lies behind every admitted array and does not wrap");
+// the furthest offset a launch forms: a backward wave requests the rows of the tile two grid strides behind its last one
+// (8 rows of 256 bytes per tile), plus a partial tile, the lane's place and the immediate offset
+static_assert(kClMaxArrayBytes + (2ull * kClMaxBwdGroups * kClWaves + 3) * 8 * 256 + 4096 <= 0x100000000ull, "no offset of a launch wraps");
 
 // floats of one slice of every block launch together (the region holds kClSliceCap of them)
 template <int C, int MODE, int NBLK, int NA>

@@ -310,6 +310,12 @@ bool cl_eligible(const Launch& x, const RowIO& io) {
     if (sw().no_cl || x.plan.id != ALG_N3 || !two_uniform_blocks(x) || !egcl(x)) return false;
     if (x.bwd && !io.saved) return false;
     if (!serves(cemlp_cl_n3(), lane_shape(x))) return false;
+    // 32-bit byte offsets (launch.hpp): the row arrays of the launch (the state regions round the rows up to 16) and, in
+    // the edge program, the node tables it gathers from and scatters into. Larger launches go to the general kernels.
+    const int row_floats = S.ch * x.A.D;
+    if (!cl_array_fits(io.rows + 16, row_floats)) return false;
+    // (a caller that does not state the tables' rows is not served: a resource of no records reads zeros)
+    if (x.mode == MODE_EDGE && (io.gather_rows <= 0 || !cl_array_fits(io.gather_rows, row_floats))) return false;
     return !x.bwd || fits(x.plan, cemlp_cl_n3().slice_floats(lane_shape(x)) * sizeof(float) * kClMaxBwdGroups);
 }
 unsigned cl_grid(const Launch& x, long rows) {

@@ -67,6 +67,16 @@ constexpr int kClMaxFwdGroups = 1024;   // 4-wave workgroups of a forward launch
 // ... of a backward launch: two per CU. One slice of partial sums each: the partial buffer of the cl AND the channel-MFMA
 // backwards is laid out for this many slices per block (block 1's start behind them: kClSliceCap of cemlp_cl.hpp)
 constexpr int kClMaxBwdGroups = 512;
+// These kernels address every array of a launch with a 32-bit byte offset from its base (cemlp_cl.hpp, "addressing"): an
+// array may hold at most this many bytes - 4 GiB less a 16 MiB margin for a partial last tile, a lane's place in its row,
+// the instruction's immediate offset and the rows a backward wave requests ahead of its last tile (two grid strides of
+// tiles: cl_inst.inc checks the sum), so that no offset of a launch wraps. cl_array_fits is the launch condition per array.
+constexpr unsigned long long kClMaxArrayBytes = 0xFF000000ull;
+constexpr bool cl_array_fits(long rows, int row_floats) {
+    return rows >= 0 && (unsigned long long)rows * (unsigned long long)row_floats * 4ull <= kClMaxArrayBytes;
+}
+static_assert(cl_array_fits(16711680, 64) && !cl_array_fits(16711681, 64), "8 channels of Cl(3,0): 256-byte rows, 16 711 680 of them");
+static_assert(cl_array_fits(0, 64) && !cl_array_fits(-1, 64) && !cl_array_fits(1L << 40, 64), "no wrap in the check itself");
 CSMPN_DECLARE_LANE_UNIT(cl, n3)
 
 // channel-MFMA kernels (cemlp_cm.hpp)
