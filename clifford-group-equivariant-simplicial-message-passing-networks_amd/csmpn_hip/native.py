@@ -18,6 +18,7 @@ FLAG_NO_VALIDATE = 2
 FLAG_DETERMINISTIC = 4
 FLAG_SAVE_STATE = 8
 ERR_UNSUPPORTED, ERR_INVALID, ERR_HIP = 1, 2, 3
+LAYER_MVSILU, LAYER_MVNORM, LAYER_MVLAYERNORM, LAYER_WGP = 0, 1, 2, 3   # `op` of csmpn_small_layer_det_bytes
 
 # every symbol include/csmpn_hip.h declares
 EXPORTS = (
@@ -42,6 +43,12 @@ EXPORTS = (
     "csmpn_mvlayernorm_backward",
     "csmpn_wgp_forward",
     "csmpn_wgp_backward",
+    "csmpn_small_layer_det_bytes",
+    "csmpn_mvsilu_backward_det",
+    "csmpn_mvnorm_backward_det",
+    "csmpn_mvlayernorm_forward_det",
+    "csmpn_mvlayernorm_backward_det",
+    "csmpn_wgp_backward_det",
     "csmpn_csr_workspace_bytes",
     "csmpn_csr_build",
     "csmpn_csr_source_order",
@@ -134,6 +141,12 @@ def _load():
     sig("csmpn_mvlayernorm_backward", C.c_int, [fp, C.c_int, vp, vp, vp, i64, i32, vp, vp, vp])
     sig("csmpn_wgp_forward", C.c_int, [fp, C.c_int, vp, vp, vp, i64, i32, vp, vp])
     sig("csmpn_wgp_backward", C.c_int, [fp, C.c_int, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp])
+    sig("csmpn_small_layer_det_bytes", sz, [C.c_int, C.c_int, i64, i32])
+    sig("csmpn_mvsilu_backward_det", C.c_int, [fp, C.c_int, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, sz, vp])
+    sig("csmpn_mvnorm_backward_det", C.c_int, [fp, C.c_int, vp, vp, vp, i64, i32, vp, vp, vp, sz, vp])
+    sig("csmpn_mvlayernorm_forward_det", C.c_int, [fp, C.c_int, vp, vp, i64, i32, vp, vp])
+    sig("csmpn_mvlayernorm_backward_det", C.c_int, [fp, C.c_int, vp, vp, vp, i64, i32, vp, vp, vp, sz, vp])
+    sig("csmpn_wgp_backward_det", C.c_int, [fp, C.c_int, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, sz, vp])
     sig("csmpn_csr_workspace_bytes", sz, [i64, i64])
     sig("csmpn_csr_build", C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, vp, sz, u32, vp])
     sig("csmpn_csr_source_order", C.c_int, [vp, i64, i64, vp, vp, vp, sz, vp])

@@ -341,8 +341,9 @@ def set_deterministic(flag):
     """True / False: force the atomic-free aggregation on / off; None: follow the environment
     (CSMPN_DETERMINISTIC=0|1) and otherwise torch.use_deterministic_algorithms, which the reference
     switches on (engineer/utils/seed.py:30). The request reaches the EGCL stages, standalone CEMLPs, the standalone
-    MVLinear backward and the type-attribute backward (everything a step of the four task models runs); the four
-    standalone small layers (mvsilu / mvnorm / mvlayernorm / wgp _apply) have no deterministic form and ignore it."""
+    MVLinear backward, the type-attribute backward (everything a step of the four task models runs) and the four
+    standalone small layers (mvsilu / mvnorm / mvlayernorm / wgp _apply: the csmpn_*_det entry points, which serve every
+    shape the default forms serve - no fallback, hard and soft requests alike). Nothing the modules launch ignores it."""
     global _DETERMINISTIC
     _DETERMINISTIC = None if flag is None else bool(flag)
 
@@ -385,16 +386,26 @@ _DET_LAUNCHES = 0
 
 
 def det_launches() -> int:
-    """Calls of csmpn_mvlinear_backward_det / csmpn_type_attr_backward_det so far (tests assert that the deterministic
-    forms ran)."""
+    """Calls of the _det entry points so far: csmpn_mvlinear_backward_det, csmpn_type_attr_backward_det and the small
+    layers' csmpn_mvsilu_backward_det, csmpn_mvnorm_backward_det, csmpn_mvlayernorm_forward_det / _backward_det and
+    csmpn_wgp_backward_det (tests assert that the deterministic forms ran)."""
     return _DET_LAUNCHES
+
+
+def _count_det():
+    global _DET_LAUNCHES
+    _DET_LAUNCHES += 1
 
 
 def _det_scratch(nbytes, device):
     """Scratch for ONE call of a _det entry point (sized by its _bytes query; needs no initialisation); counts the call."""
-    global _DET_LAUNCHES
-    _DET_LAUNCHES += 1
+    _count_det()
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def _small_det_scratch(op, metric, x):
+    """_det_scratch for the backward of a standalone small layer on x [rows, C, D]."""
+    return _det_scratch(native.lib().csmpn_small_layer_det_bytes(op, len(metric), x.shape[0], x.shape[1]), x.device)
 
 
 def _warn_soft_slice():
@@ -933,9 +944,13 @@ class _MVSiLUFn(torch.autograd.Function):
         x, a, b = ctx.saved_tensors
         gy = gy.contiguous()
         gx, ga, gb = torch.empty_like(x), torch.zeros_like(a), torch.zeros_like(b)
-        check(native.lib().csmpn_mvsilu_backward(native.metric_array(ctx.metric), len(ctx.metric), x.data_ptr(),
-                                                 a.data_ptr(), b.data_ptr(), gy.data_ptr(), x.shape[0], x.shape[1],
-                                                 gx.data_ptr(), ga.data_ptr(), gb.data_ptr(), _stream(x.device)))
+        args = (native.metric_array(ctx.metric), len(ctx.metric), x.data_ptr(), a.data_ptr(), b.data_ptr(), gy.data_ptr(),
+                x.shape[0], x.shape[1], gx.data_ptr(), ga.data_ptr(), gb.data_ptr())
+        if deterministic_request():   # the atomic-free form: parked contributions, per-workgroup partial rows in scratch
+            ws = _small_det_scratch(native.LAYER_MVSILU, ctx.metric, x)
+            check(native.lib().csmpn_mvsilu_backward_det(*args, ws.data_ptr(), ws.numel(), _stream(x.device)))
+        else:
+            check(native.lib().csmpn_mvsilu_backward(*args, _stream(x.device)))
         _count()
         return gx, ga, gb, None
 
@@ -950,9 +965,13 @@ class _RowParamFn(torch.autograd.Function):
         x = _small_args(x, which, (a,))
         a2 = a.contiguous()
         y = torch.empty_like(x)
-        fwd = getattr(native.lib(), f"csmpn_{which}_forward")
+        # MVLayerNorm sums a row's channel norms across lanes: its forward has a _det form too (no scratch)
+        det = which == "mvlayernorm" and deterministic_request()
+        fwd = getattr(native.lib(), f"csmpn_{which}_forward" + ("_det" if det else ""))
         check(fwd(native.metric_array(metric), len(metric), x.data_ptr(), a2.data_ptr(), x.shape[0], x.shape[1],
                   y.data_ptr(), _stream(x.device)))
+        if det:
+            _count_det()
         _count()
         ctx.save_for_backward(x, a2)
         ctx.metric, ctx.which = metric, which
@@ -964,9 +983,14 @@ class _RowParamFn(torch.autograd.Function):
         x, a = ctx.saved_tensors
         gy = gy.contiguous()
         gx, ga = torch.empty_like(x), torch.zeros_like(a)
-        bwd = getattr(native.lib(), f"csmpn_{ctx.which}_backward")
-        check(bwd(native.metric_array(ctx.metric), len(ctx.metric), x.data_ptr(), a.data_ptr(), gy.data_ptr(),
-                  x.shape[0], x.shape[1], gx.data_ptr(), ga.data_ptr(), _stream(x.device)))
+        args = (native.metric_array(ctx.metric), len(ctx.metric), x.data_ptr(), a.data_ptr(), gy.data_ptr(),
+                x.shape[0], x.shape[1], gx.data_ptr(), ga.data_ptr())
+        if deterministic_request():
+            op = native.LAYER_MVNORM if ctx.which == "mvnorm" else native.LAYER_MVLAYERNORM
+            ws = _small_det_scratch(op, ctx.metric, x)
+            check(getattr(native.lib(), f"csmpn_{ctx.which}_backward_det")(*args, ws.data_ptr(), ws.numel(), _stream(x.device)))
+        else:
+            check(getattr(native.lib(), f"csmpn_{ctx.which}_backward")(*args, _stream(x.device)))
         _count()
         return gx, ga, None, None
 
@@ -996,9 +1020,13 @@ class _WgpFn(torch.autograd.Function):
         z, r, w = ctx.saved_tensors
         gy = gy.contiguous()
         gz, gr, gw = torch.empty_like(z), torch.empty_like(r), torch.zeros_like(w)
-        check(native.lib().csmpn_wgp_backward(native.metric_array(ctx.metric), len(ctx.metric), z.data_ptr(), r.data_ptr(),
-                                              w.data_ptr(), gy.data_ptr(), z.shape[0], z.shape[1], gz.data_ptr(),
-                                              gr.data_ptr(), gw.data_ptr(), _stream(z.device)))
+        args = (native.metric_array(ctx.metric), len(ctx.metric), z.data_ptr(), r.data_ptr(), w.data_ptr(), gy.data_ptr(),
+                z.shape[0], z.shape[1], gz.data_ptr(), gr.data_ptr(), gw.data_ptr())
+        if deterministic_request():
+            ws = _small_det_scratch(native.LAYER_WGP, ctx.metric, z)
+            check(native.lib().csmpn_wgp_backward_det(*args, ws.data_ptr(), ws.numel(), _stream(z.device)))
+        else:
+            check(native.lib().csmpn_wgp_backward(*args, _stream(z.device)))
         _count()
         return gz, gr, gw, None
 

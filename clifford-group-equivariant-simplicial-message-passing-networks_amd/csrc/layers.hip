@@ -9,7 +9,9 @@
 // the layers on their own, so these kernels are the plain HBM-bound form: one thread per (row,
 // channel) with the channel's D blades in registers (compile-time sign tables, algebra.hpp), rows of a
 // workgroup contiguous in memory. Parameter gradients: per-workgroup sums in LDS, then one float
-// atomic per parameter and workgroup.
+// atomic per parameter and workgroup. The csmpn_*_det forms of the four small layers use no float
+// atomic: contributions parked in LDS and added in a fixed order, one partial row per workgroup in
+// the caller's scratch, a second launch that adds the partial rows (see "_det forms" below).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -313,7 +315,7 @@ __global__ void __launch_bounds__(kThreads) wgp_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------- dispatch
-enum Op { OP_SILU, OP_NORM, OP_LNORM, OP_WGP };
+enum Op { OP_SILU = CSMPN_LAYER_MVSILU, OP_NORM = CSMPN_LAYER_MVNORM, OP_LNORM = CSMPN_LAYER_MVLAYERNORM, OP_WGP = CSMPN_LAYER_WGP };
 
 struct Args {
     const float *x, *r, *p0, *p1, *gy;
@@ -321,6 +323,312 @@ struct Args {
     int C;
     float *out, *out2, *g0, *g1;
 };
+
+// ---------------------------------------------------------------------------------- _det forms (no float atomics)
+// A tile is what one workgroup of the default form covers: kThreads consecutive (row, channel) elements, for MVLayerNorm
+// floor(kThreads / C) whole rows. At most kDetMaxParts workgroups: workgroup w walks the tiles [w * tiles_per_wg,
+// (w + 1) * tiles_per_wg) in ascending order and leaves ONE partial row of `entries` parameter-gradient sums in
+// part[w][entry]; small_det_reduce_kernel adds the partial rows in ascending order into the gradients. Everything below
+// follows from (op, n, rows, channels): det_shape().
+constexpr long kDetMaxParts = 512;
+
+// Where a lane's parameter-gradient contributions go: `add(k, v)` = contribution v of this lane to entry k of its channel,
+// called exactly once per k, parks v in the lane's own LDS slot park[k][lane]. Row stride kThreads + 1, so that the threads
+// that later walk different k at the same lane position hit different banks.
+constexpr int kParkStride = kThreads + 1;
+struct ParkSums {
+    float* park;
+    __device__ void add(int k, float v) { park[k * kParkStride + threadIdx.x] = v; }
+};
+
+// The backward of element t = (row, channel) of the three one-lane-per-element layers: the arithmetic of mvsilu_kernel /
+// mvnorm_kernel / wgp_kernel<ALG, true>, statement for statement. Copies, not shared helpers: with one body behind both
+// forms the default kernels compiled to other code (operand order, register allocation), and those stay as they are.
+template <class ALG>
+__device__ __forceinline__ void mvsilu_bwd_lane(const float* __restrict__ x, const float* __restrict__ a, const float* __restrict__ b,
+                                                const float* __restrict__ gy, long t, int C, float* __restrict__ out, ParkSums& ps) {
+    constexpr int D = ALG::D, G = ALG::G;
+    const int c = (int)(t % C);
+    float xv[D], u[G], gate[G];
+    load_row<ALG>(xv, x + t * D);
+    grade_q<ALG>(xv, u);
+    u[0] = xv[0];
+#pragma unroll
+    for (int g = 0; g < G; ++g) gate[g] = sigmoid_sat(a[c * G + g] * u[g] + b[c * G + g]);
+    float gv[D], gx[D];
+    load_row<ALG>(gv, gy + t * D);
+    static_for<0, G>([&](auto g) {
+        float gg = 0.f;
+        static_for<ALG::gstart(g), ALG::gstart(g) + ALG::gsize(g)>([&](auto d) { gg += gv[d] * xv[d]; });
+        const float gpre = gg * gate[g] * (1.0f - gate[g]);
+        ps.add(g, gpre * u[g]);
+        ps.add(G + g, gpre);
+        const float gu = gpre * a[c * G + g];
+        static_for<ALG::gstart(g), ALG::gstart(g) + ALG::gsize(g)>([&](auto d) {
+            gx[d] = gv[d] * gate[g] + (g == 0 ? gu : gu * (2.0f * qsf<ALG, d>) * xv[d]);
+        });
+    });
+    store_row<ALG>(gx, out + t * D);
+}
+
+template <class ALG>
+__device__ __forceinline__ void mvnorm_bwd_lane(const float* __restrict__ x, const float* __restrict__ a, const float* __restrict__ gy,
+                                                long t, int C, float* __restrict__ out, ParkSums& ps) {
+    constexpr int D = ALG::D, G = ALG::G;
+    const int c = (int)(t % C);
+    float xv[D], q[G], inv[G], sg[G], nu[G];
+    load_row<ALG>(xv, x + t * D);
+    grade_q<ALG>(xv, q);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        sg[g] = sigmoid_sat(a[c * G + g]);
+        nu[g] = smooth_abs_sqrt(q[g]);
+        inv[g] = 1.0f / (sg[g] * (nu[g] - 1.0f) + 1.0f + kEps);
+    }
+    float gv[D], gx[D];
+    load_row<ALG>(gv, gy + t * D);
+    static_for<0, G>([&](auto g) {
+        float dot = 0.f;
+        static_for<ALG::gstart(g), ALG::gstart(g) + ALG::gsize(g)>([&](auto d) { dot += gv[d] * xv[d]; });
+        const float gden = -dot * inv[g] * inv[g];
+        ps.add(g, gden * (nu[g] - 1.0f) * sg[g] * (1.0f - sg[g]));
+        const float inu = 1.0f / nu[g];
+        const float gq = gden * sg[g] * (0.5f * q[g]) * (inu * inu * inu);   // d nu / d q = q / (2 nu^3)
+        static_for<ALG::gstart(g), ALG::gstart(g) + ALG::gsize(g)>([&](auto d) {
+            gx[d] = gv[d] * inv[g] + gq * (2.0f * qsf<ALG, d>) * xv[d];
+        });
+    });
+    store_row<ALG>(gx, out + t * D);
+}
+
+template <class ALG>
+__device__ __forceinline__ void wgp_bwd_lane(const float* __restrict__ z, const float* __restrict__ r, const float* __restrict__ w,
+                                             const float* __restrict__ gy, long t, int C, float* __restrict__ gz,
+                                             float* __restrict__ gr, ParkSums& ps) {
+    constexpr int D = ALG::D, P = ALG::P;
+    const int c = (int)(t % C);
+    float zv[D], rv[D], gv[D], gzv[D], grv[D];
+    load_row<ALG>(zv, z + t * D);
+    load_row<ALG>(rv, r + t * D);
+    load_row<ALG>(gv, gy + t * D);
+#pragma unroll
+    for (int d = 0; d < D; ++d) { gzv[d] = 0.f; grv[d] = 0.f; }
+    static_for<0, P>([&](auto p) {
+        constexpr int gi = ALG::t.path_g[p][0], gj = ALG::t.path_g[p][1], gk = ALG::t.path_g[p][2];
+        constexpr int i0 = ALG::gstart(gi), ni = ALG::gsize(gi);
+        constexpr int j0 = ALG::gstart(gj), nj = ALG::gsize(gj);
+        constexpr int k0 = ALG::gstart(gk), nk = ALG::gsize(gk);
+        float U[ni], V[nk];   // unweighted d/dz, d/dr of this path
+#pragma unroll
+        for (int u = 0; u < ni; ++u) U[u] = 0.f;
+#pragma unroll
+        for (int u = 0; u < nk; ++u) V[u] = 0.f;
+        static_for<0, ni>([&](auto ii) {
+            static_for<0, nk>([&](auto kk) {
+                constexpr int i = i0 + ii, k = k0 + kk;
+                constexpr int j = ALG::t.out[i][k];
+                if constexpr (j >= j0 && j < j0 + nj) {
+                    const float sg = float(ALG::t.sign[i][k]) * gv[j];
+                    U[ii] += sg * rv[k];
+                    V[kk] += sg * zv[i];
+                }
+            });
+        });
+        const float wp = w[c * P + p];
+        float gwp = 0.f;
+#pragma unroll
+        for (int u = 0; u < ni; ++u) { gzv[i0 + u] += wp * U[u]; gwp += zv[i0 + u] * U[u]; }
+#pragma unroll
+        for (int u = 0; u < nk; ++u) grv[k0 + u] += wp * V[u];
+        ps.add(p, gwp);
+    });
+    store_row<ALG>(gzv, gz + t * D);
+    store_row<ALG>(grv, gr + t * D);
+}
+
+struct DetShape {
+    long tiles, tiles_per_wg, parts;   // parts = ceil(tiles / tiles_per_wg) <= min(tiles, kDetMaxParts)
+    int entries;                       // parameter-gradient entries = floats of one partial row
+};
+
+constexpr int paths_of(int n) { return n == 2 ? Alg<2, 0u>::P : n == 3 ? Alg<3, 0u>::P : n == 4 ? Alg<4, 0u>::P : Alg<5, 0u>::P; }
+static_assert(Alg<4, 0x8u>::P == Alg<4, 0u>::P && Alg<5, 0x10u>::P == Alg<5, 0u>::P, "the grade paths depend on n alone");
+static_assert(sizeof(float) * Alg<5, 0u>::P * kParkStride <= 64 * 1024, "parked path-weight contributions exceed 64 KB of LDS");
+
+inline bool det_shape(int op, int n, long rows, int C, DetShape& S) {
+    if (n < 2 || n > 5 || rows <= 0 || C < 1 || C > kMaxChannels || rows > (1L << 40)) return false;
+    const int G = n + 1;
+    switch (op) {
+        case OP_SILU: S.entries = 2 * G * C; break;
+        case OP_NORM: S.entries = G * C; break;
+        case OP_LNORM: S.entries = C; break;
+        case OP_WGP: S.entries = paths_of(n) * C; break;
+        default: return false;
+    }
+    const long per_tile = op == OP_LNORM ? kThreads / C : kThreads;   // rows, or elements
+    const long units = op == OP_LNORM ? rows : rows * C;
+    S.tiles = (units + per_tile - 1) / per_tile;
+    S.tiles_per_wg = (S.tiles + kDetMaxParts - 1) / kDetMaxParts;
+    S.parts = (S.tiles + S.tiles_per_wg - 1) / S.tiles_per_wg;
+    return true;
+}
+
+// The three one-lane-per-element layers. After a tile's lanes have parked their contributions, thread i (i + kThreads, ...)
+// owns entry i = c * NP + k and adds the slots of the lanes of channel c in ascending lane order; only lanes inside
+// rows * C are visited, so a ragged tile's idle lanes park nothing and nothing of theirs is read. The sum of a tile is
+// added to the workgroup's partial row in tile order (the row is written before it is read: the first tile stores).
+template <class ALG, Op OP>
+__global__ void __launch_bounds__(kThreads) elem_bwd_det_kernel(const Args A, long tiles, long tiles_per_wg, float* part) {
+    constexpr int NP = OP == OP_SILU ? 2 * ALG::G : OP == OP_NORM ? ALG::G : ALG::P;
+    __shared__ float park[NP * kParkStride];
+    ParkSums ps{park};
+    const int C = A.C, entries = NP * C;
+    const long total = A.rows * C;
+    float* const prow = part + (size_t)blockIdx.x * entries;
+    const long tile0 = (long)blockIdx.x * tiles_per_wg;
+    const long tile1 = tile0 + tiles_per_wg < tiles ? tile0 + tiles_per_wg : tiles;
+    for (long tile = tile0; tile < tile1; ++tile) {
+        const long base = tile * kThreads, t = base + threadIdx.x;
+        if (t < total) {
+            if constexpr (OP == OP_SILU) mvsilu_bwd_lane<ALG>(A.x, A.p0, A.p1, A.gy, t, C, A.out, ps);
+            else if constexpr (OP == OP_NORM) mvnorm_bwd_lane<ALG>(A.x, A.p0, A.gy, t, C, A.out, ps);
+            else wgp_bwd_lane<ALG>(A.x, A.r, A.p0, A.gy, t, C, A.out, A.out2, ps);
+        }
+        __syncthreads();
+        const int nvalid = total - base < kThreads ? (int)(total - base) : kThreads;
+        const int c0 = (int)(base % C);   // channel of the tile's lane 0
+        for (int i = threadIdx.x; i < entries; i += kThreads) {
+            const int c = i / NP, k = i % NP;
+            float s = 0.f;
+            for (int l = c >= c0 ? c - c0 : c - c0 + C; l < nvalid; l += C) s += park[k * kParkStride + l];
+            prow[i] = tile == tile0 ? s : prow[i] + s;
+        }
+        __syncthreads();
+    }
+}
+
+// MVLayerNorm, forward and backward: as mvlayernorm_kernel, but the lanes park their channel norm (and a_c <gy_c, x_c>) in
+// LDS and the row's first lane adds them in ascending channel order; the backward's d/da contributions are parked the same
+// way and thread c adds the tile's rows in ascending order, keeping the workgroup's sum over its tiles in a register.
+// Forward: one tile per workgroup, part unused.
+template <class ALG, bool BWD>
+__global__ void __launch_bounds__(kThreads) mvlayernorm_det_kernel(const float* __restrict__ x, const float* __restrict__ a,
+                                                                   const float* __restrict__ gy, long rows, int C,
+                                                                   float* __restrict__ out, long tiles, long tiles_per_wg,
+                                                                   float* __restrict__ part) {
+    constexpr int D = ALG::D;
+    __shared__ float pnorm[kThreads], pdot[kThreads], rsum[kThreads], rdot[kThreads];
+    const int rpb = kThreads / C;                 // rows per tile
+    const int lr = threadIdx.x / C, c = threadIdx.x % C;
+    const long tile0 = (long)blockIdx.x * tiles_per_wg;
+    const long tile1 = tile0 + tiles_per_wg < tiles ? tile0 + tiles_per_wg : tiles;
+    float acc = 0.f;                              // thread c < C: d/da[c] over this workgroup's tiles
+    for (long tile = tile0; tile < tile1; ++tile) {
+        const long row = tile * rpb + lr;
+        const bool act = lr < rpb && row < rows;
+        float xv[D], gv[D];
+        float q = 0.f, nl = 0.f, dot = 0.f, ac = 0.f;
+        if (act) {
+            ac = a[c];
+            load_row<ALG>(xv, x + (row * C + c) * D);
+            static_for<0, D>([&](auto d) { q += qsf<ALG, d> * xv[d] * xv[d]; });
+            nl = smooth_abs_sqrt(q);
+            pnorm[threadIdx.x] = nl;
+            if constexpr (BWD) {
+                load_row<ALG>(gv, gy + (row * C + c) * D);
+                static_for<0, D>([&](auto d) { dot += gv[d] * xv[d]; });
+                pdot[threadIdx.x] = ac * dot;
+            }
+        }
+        __syncthreads();
+        if (act && c == 0) {
+            float s = 0.f, sd = 0.f;
+            for (int j = 0; j < C; ++j) s += pnorm[threadIdx.x + j];
+            rsum[lr] = s;
+            if constexpr (BWD) {
+                for (int j = 0; j < C; ++j) sd += pdot[threadIdx.x + j];
+                rdot[lr] = sd;
+            }
+        }
+        __syncthreads();
+        if (act) {
+            const float invM = 1.0f / (rsum[lr] / float(C) + kEps);
+            if constexpr (!BWD) {
+                float y[D];
+                static_for<0, D>([&](auto d) { y[d] = ac * xv[d] * invM; });
+                store_row<ALG>(y, out + (row * C + c) * D);
+            } else {
+                pnorm[threadIdx.x] = dot * invM;                          // every read of the norms lies before the barrier above
+                const float gM = -rdot[lr] * invM * invM / float(C);      // d/d(norm of one channel)
+                const float inl = 1.0f / nl;
+                const float gq = gM * (0.5f * q) * (inl * inl * inl);
+                float gx[D];
+                static_for<0, D>([&](auto d) { gx[d] = ac * gv[d] * invM + gq * (2.0f * qsf<ALG, d>) * xv[d]; });
+                store_row<ALG>(gx, out + (row * C + c) * D);
+            }
+        }
+        if constexpr (BWD) {
+            __syncthreads();
+            if (threadIdx.x < C) {
+                const long left = rows - tile * rpb;
+                const int nr = left < rpb ? (int)left : rpb;              // rows of this tile: only their slots were written
+                float s = 0.f;
+                for (int j = 0; j < nr; ++j) s += pnorm[j * C + threadIdx.x];
+                acc += s;
+            }
+            __syncthreads();
+        }
+    }
+    if constexpr (BWD)
+        if (threadIdx.x < C) part[(size_t)blockIdx.x * C + threadIdx.x] = acc;
+}
+
+// g += the partial rows in ascending order: one thread per entry, eight rows in flight. silu_G != 0: MVSiLU's entries
+// c * 2G + k go to g0 (a) for k < G and to g1 (b) behind; every other layer's entry i is g0[i].
+__global__ void __launch_bounds__(kThreads) small_det_reduce_kernel(const float* __restrict__ part, int parts, int entries, int silu_G,
+                                                                    float* g0, float* g1) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= entries) return;
+    float s = 0.f;
+    int w = 0;
+    for (; w + 8 <= parts; w += 8) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = part[(size_t)(w + j) * entries + i];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += v[j];
+    }
+    for (; w < parts; ++w) s += part[(size_t)w * entries + i];
+    float* dst = g0 + i;
+    if (silu_G) {
+        const int c = i / (2 * silu_G), k = i % (2 * silu_G);
+        dst = (k < silu_G ? g0 : g1) + c * silu_G + k % silu_G;
+    }
+    *dst += s;
+}
+
+template <class ALG, bool BWD>
+hipError_t launch_det(Op op, const Args& A, const DetShape& S, float* part, hipStream_t st) {
+    const dim3 grid((unsigned)S.parts), block(kThreads);
+    if constexpr (!BWD) {   // MVLayerNorm forward, the only forward with a sum across lanes
+        hipLaunchKernelGGL((mvlayernorm_det_kernel<ALG, false>), dim3((unsigned)S.tiles), block, 0, st, A.x, A.p0, A.gy, A.rows, A.C,
+                           A.out, S.tiles, 1L, (float*)nullptr);
+        return hipGetLastError();
+    } else {
+        switch (op) {
+            case OP_SILU: hipLaunchKernelGGL((elem_bwd_det_kernel<ALG, OP_SILU>), grid, block, 0, st, A, S.tiles, S.tiles_per_wg, part); break;
+            case OP_NORM: hipLaunchKernelGGL((elem_bwd_det_kernel<ALG, OP_NORM>), grid, block, 0, st, A, S.tiles, S.tiles_per_wg, part); break;
+            case OP_WGP: hipLaunchKernelGGL((elem_bwd_det_kernel<ALG, OP_WGP>), grid, block, 0, st, A, S.tiles, S.tiles_per_wg, part); break;
+            case OP_LNORM:
+                hipLaunchKernelGGL((mvlayernorm_det_kernel<ALG, true>), grid, block, 0, st, A.x, A.p0, A.gy, A.rows, A.C, A.out,
+                                   S.tiles, S.tiles_per_wg, part);
+                break;
+        }
+        hipLaunchKernelGGL(small_det_reduce_kernel, dim3((unsigned)((S.entries + kThreads - 1) / kThreads)), block, 0, st,
+                           (const float*)part, (int)S.parts, S.entries, op == OP_SILU ? ALG::G : 0, A.g0, A.g1);
+        return hipGetLastError();
+    }
+}
 
 template <class ALG, bool BWD>
 hipError_t launch(Op op, const Args& A, hipStream_t st) {
@@ -350,7 +658,9 @@ hipError_t launch(Op op, const Args& A, hipStream_t st) {
     return hipGetLastError();
 }
 
-int run(const float* metric, int n, Op op, bool bwd, const Args& A, void* stream) {
+// det: the _det form of (op, bwd); `workspace` holds its partial rows (backward only).
+int run(const float* metric, int n, Op op, bool bwd, const Args& A, void* stream, bool det = false, void* workspace = nullptr,
+        size_t workspace_bytes = 0) {
     if (!metric || n < 2 || n > 5) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "standalone layers: n=%d not in 2..5", n);
     unsigned neg = 0;
     for (int i = 0; i < n; ++i) {
@@ -359,10 +669,22 @@ int run(const float* metric, int n, Op op, bool bwd, const Args& A, void* stream
     }
     if (A.rows < 0 || A.C < 1 || A.C > kMaxChannels) return csmpn_fail(CSMPN_ERR_INVALID, "standalone layers: bad rows / channels (1..%d)", kMaxChannels);
     if (A.rows == 0) return CSMPN_OK;
+    DetShape S{};
+    if (det) {
+        if (!det_shape(op, n, A.rows, A.C, S)) return csmpn_fail(CSMPN_ERR_INVALID, "standalone layers (_det): rows=%ld out of range", A.rows);
+        const size_t need = csmpn_small_layer_det_bytes(op, n, A.rows, A.C);
+        if (bwd && (!workspace || workspace_bytes < need))
+            return csmpn_fail(CSMPN_ERR_INVALID, "standalone layers (_det): workspace %zu bytes < %zu (csmpn_small_layer_det_bytes)",
+                              workspace ? workspace_bytes : (size_t)0, need);
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e = hipErrorInvalidValue;
-#define CSMPN_LAYER_ALG(N_, NEG_)                                                              \
-    if (n == N_ && neg == NEG_) e = bwd ? launch<Alg<N_, NEG_>, true>(op, A, st) : launch<Alg<N_, NEG_>, false>(op, A, st); else
+#define CSMPN_LAYER_ALG(N_, NEG_)                                                                                       \
+    if (n == N_ && neg == NEG_) {                                                                                       \
+        using A_ = Alg<N_, NEG_>;                                                                                       \
+        if (det) e = bwd ? launch_det<A_, true>(op, A, S, (float*)workspace, st) : launch_det<A_, false>(op, A, S, nullptr, st); \
+        else e = bwd ? launch<A_, true>(op, A, st) : launch<A_, false>(op, A, st);                                      \
+    } else
     CSMPN_LAYER_ALG(2, 0u) CSMPN_LAYER_ALG(3, 0u) CSMPN_LAYER_ALG(4, 0u) CSMPN_LAYER_ALG(4, 0x8u) CSMPN_LAYER_ALG(5, 0u)
     CSMPN_LAYER_ALG(5, 0x10u)
         return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "standalone layers: no kernels for this signature (n=%d, negative mask 0x%x)", n, neg);
@@ -565,6 +887,45 @@ int csmpn_wgp_backward(const float* metric_host, int n, const float* z, const fl
     if (!z || !r || !weight || !gy || !gz || !gr || !g_weight) return csmpn_fail(CSMPN_ERR_INVALID, "csmpn_wgp_backward: null pointer");
     Args A{z, r, weight, nullptr, gy, (long)rows, channels, gz, gr, g_weight, nullptr};
     return run(metric_host, n, OP_WGP, true, A, stream);
+}
+
+size_t csmpn_small_layer_det_bytes(int op, int n, int64_t rows, int32_t channels) {
+    DetShape S;
+    if (!det_shape(op, n, (long)rows, channels, S)) return 0;
+    return (size_t)(S.tiles < kDetMaxParts ? S.tiles : kDetMaxParts) * S.entries * sizeof(float);
+}
+int csmpn_mvsilu_backward_det(const float* metric_host, int n, const float* x, const float* a, const float* b, const float* gy,
+                              int64_t rows, int32_t channels, float* gx, float* g_a, float* g_b, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (!x || !a || !b || !gy || !gx || !g_a || !g_b) return csmpn_fail(CSMPN_ERR_INVALID, "csmpn_mvsilu_backward_det: null pointer");
+    Args A{x, nullptr, a, b, gy, (long)rows, channels, gx, nullptr, g_a, g_b};
+    return run(metric_host, n, OP_SILU, true, A, stream, true, workspace, workspace_bytes);
+}
+int csmpn_mvnorm_backward_det(const float* metric_host, int n, const float* x, const float* a, const float* gy, int64_t rows,
+                              int32_t channels, float* gx, float* g_a, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !a || !gy || !gx || !g_a) return csmpn_fail(CSMPN_ERR_INVALID, "csmpn_mvnorm_backward_det: null pointer");
+    Args A{x, nullptr, a, nullptr, gy, (long)rows, channels, gx, nullptr, g_a, nullptr};
+    return run(metric_host, n, OP_NORM, true, A, stream, true, workspace, workspace_bytes);
+}
+int csmpn_mvlayernorm_forward_det(const float* metric_host, int n, const float* x, const float* a, int64_t rows,
+                                  int32_t channels, float* y, void* stream) {
+    if (!x || !a || !y) return csmpn_fail(CSMPN_ERR_INVALID, "csmpn_mvlayernorm_forward_det: null pointer");
+    Args A{x, nullptr, a, nullptr, nullptr, (long)rows, channels, y, nullptr, nullptr, nullptr};
+    return run(metric_host, n, OP_LNORM, false, A, stream, true);
+}
+int csmpn_mvlayernorm_backward_det(const float* metric_host, int n, const float* x, const float* a, const float* gy,
+                                   int64_t rows, int32_t channels, float* gx, float* g_a, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    if (!x || !a || !gy || !gx || !g_a) return csmpn_fail(CSMPN_ERR_INVALID, "csmpn_mvlayernorm_backward_det: null pointer");
+    Args A{x, nullptr, a, nullptr, gy, (long)rows, channels, gx, nullptr, g_a, nullptr};
+    return run(metric_host, n, OP_LNORM, true, A, stream, true, workspace, workspace_bytes);
+}
+int csmpn_wgp_backward_det(const float* metric_host, int n, const float* z, const float* r, const float* weight, const float* gy,
+                           int64_t rows, int32_t channels, float* gz, float* gr, float* g_weight, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    if (!z || !r || !weight || !gy || !gz || !gr || !g_weight) return csmpn_fail(CSMPN_ERR_INVALID, "csmpn_wgp_backward_det: null pointer");
+    Args A{z, r, weight, nullptr, gy, (long)rows, channels, gz, gr, g_weight, nullptr};
+    return run(metric_host, n, OP_WGP, true, A, stream, true, workspace, workspace_bytes);
 }
 
 int csmpn_mvlinear_forward(int n, const float* x, const float* weight, const float* bias, int64_t rows,

@@ -81,12 +81,13 @@ extern "C" {
                                          - csmpn_mvlinear_backward_det and csmpn_type_attr_backward_det (entry points of
                                            their own: they need scratch the plain forms do not take); every forward,
                                            csmpn_mvlinear_backward's d/dx, csmpn_simplex_rows, csmpn_segment_reduce and the
-                                           readout entry points have fixed-order sums as they are.
-                                       NOT covered: the four standalone small layers (csmpn_mvsilu_*, csmpn_mvnorm_*,
-                                       csmpn_mvlayernorm_*, csmpn_wgp_*): their parameter gradients - and the row sums in the
-                                       forward of csmpn_mvlayernorm_forward - use float atomics in LDS and in memory. No task
-                                       model calls them alone. csmpn_mvlinear_backward and csmpn_type_attr_backward (the
-                                       plain forms) add d/dW, d/dbias and the table gradient with float atomics. */
+                                           readout entry points have fixed-order sums as they are;
+                                         - the four standalone small layers through csmpn_mvsilu_backward_det,
+                                           csmpn_mvnorm_backward_det, csmpn_mvlayernorm_forward_det / _backward_det and
+                                           csmpn_wgp_backward_det (the other forwards of these layers work lane by lane).
+                                       The plain forms csmpn_mvsilu_backward, csmpn_mvnorm_backward, csmpn_mvlayernorm_forward /
+                                       _backward, csmpn_wgp_backward, csmpn_mvlinear_backward and csmpn_type_attr_backward add
+                                       their parameter gradients (MVLayerNorm: also the row sums) with float atomics. */
 #define CSMPN_FLAG_SAVE_STATE 8u     /* csmpn_egcl_{edge,node}_{forward,backward}, csmpn_embed_cemlp_{forward,backward} (two-block
                                       * modules), round 4; csmpn_cemlp_{forward,backward}, round 5, for the standalone Cl(3,0) CEMLPs
                                       * of 32 channels the 16-row-tile family serves (1 or 2 blocks; 32, 60 or 90 input channels:
@@ -254,6 +255,51 @@ int csmpn_wgp_forward(const float* metric_host, int n, const float* z, const flo
                       int32_t channels, float* y, void* stream);
 int csmpn_wgp_backward(const float* metric_host, int n, const float* z, const float* r, const float* weight,
                        const float* gy, int64_t rows, int32_t channels, float* gz, float* gr, float* g_weight, void* stream);
+
+/* The same four layers without float atomics, neither in LDS nor in memory (entry points of their own: the backward
+ * forms need scratch the plain forms do not take). Arguments, results and limits as the plain forms; the forwards of
+ * MVSiLU, NormalizationLayer and the weighted product have no sum across lanes and no _det twin.
+ *   Within a workgroup: every lane parks its contributions to the parameter gradients in LDS slots of its own, and one
+ *     lane per parameter entry adds the slots of its channel's lanes in ascending lane order - an order fixed by (rows,
+ *     channels) alone. MVLayerNorm's sum of a row's channel norms (forward and backward) and of a_c <gy_c, x_c>
+ *     (backward) is taken the same way: parked, then added by the row's first lane in ascending channel order.
+ *   Across workgroups: every workgroup stores one partial row to workspace[workgroup][entry]; a second launch adds the
+ *     partial rows in ascending workgroup order INTO g_* (+=, as the plain forms). Entries per row: MVSiLU 2 (n+1) C,
+ *     NormalizationLayer (n+1) C, MVLayerNorm C, weighted product P C.
+ *   At most 512 partial rows. A tile is what one workgroup of the plain form covers: 256 consecutive (row, channel)
+ *     elements, for MVLayerNorm floor(256 / C) whole rows; tiles = ceil(rows * C / 256), for MVLayerNorm
+ *     ceil(rows / floor(256 / C)). Up to 512 tiles every workgroup takes one; beyond, a workgroup walks a contiguous
+ *     range of ceil(tiles / 512) tiles and accumulates in tile order, so the scratch stops growing with the rows:
+ *     csmpn_small_layer_det_bytes() = min(tiles, 512) * entries * 4 bytes - non-decreasing in rows, constant from the
+ *     first row count with 512 tiles on (29.4 MB at most: the weighted product on n = 5, 256 channels; 1.3 MB for it on
+ *     Cl(3,0) with 32 channels).
+ *   Launch shape, tile ranges and the cap depend on (op, n, rows, channels) only: the same bits in every run and process.
+ *   Every shape the plain forms serve is served (the six compiled signatures, 1..256 channels; rows up to 2^40): there
+ *     is no fallback. 257 channels: CSMPN_ERR_INVALID, as the plain forms. rows == 0: CSMPN_OK, nothing touched.
+ *   The workspace needs no initialisation (every word read was written by the same call); NULL or smaller than
+ *     csmpn_small_layer_det_bytes(): CSMPN_ERR_INVALID before anything is launched. Nothing is allocated.
+ *     csmpn_small_layer_det_bytes is host-only; 0 for sizes the entry points reject, an unknown op and rows <= 0.
+ *   LDS: static, at most 56 * 257 * 4 = 57 568 bytes per workgroup (the weighted product on n = 5: P = 56 path weights
+ *     per lane, 256 lanes) - below the 64 KB a launch gets without further ado.
+ *   Lanes past rows * channels of a ragged tile park nothing, and their slots are not among those added. */
+#define CSMPN_LAYER_MVSILU 0
+#define CSMPN_LAYER_MVNORM 1
+#define CSMPN_LAYER_MVLAYERNORM 2
+#define CSMPN_LAYER_WGP 3
+size_t csmpn_small_layer_det_bytes(int op, int n, int64_t rows, int32_t channels);
+int csmpn_mvsilu_backward_det(const float* metric_host, int n, const float* x, const float* a, const float* b, const float* gy,
+                              int64_t rows, int32_t channels, float* gx, float* g_a, float* g_b, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int csmpn_mvnorm_backward_det(const float* metric_host, int n, const float* x, const float* a, const float* gy, int64_t rows,
+                              int32_t channels, float* gx, float* g_a, void* workspace, size_t workspace_bytes, void* stream);
+int csmpn_mvlayernorm_forward_det(const float* metric_host, int n, const float* x, const float* a, int64_t rows,
+                                  int32_t channels, float* y, void* stream);
+int csmpn_mvlayernorm_backward_det(const float* metric_host, int n, const float* x, const float* a, const float* gy,
+                                   int64_t rows, int32_t channels, float* gx, float* g_a, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+int csmpn_wgp_backward_det(const float* metric_host, int n, const float* z, const float* r, const float* weight, const float* gy,
+                           int64_t rows, int32_t channels, float* gz, float* gr, float* g_weight, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* One-time per complex: sort the E directed adjacencies by target (stable radix sort).
  * edge_index is the reference's [2,E] int64 (row 0 = source j, row 1 = target i).
