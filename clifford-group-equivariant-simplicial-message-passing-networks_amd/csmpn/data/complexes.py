@@ -27,8 +27,9 @@ A batch caches the target-sorted CSR of its `edge_index` (complexes are static: 
 from __future__ import annotations
 
 import itertools
+import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -162,6 +163,9 @@ class SimplicialBatch:
 
     def to(self, device):
         out = SimplicialBatch(**{k: getattr(self, k).to(device) for k in self._names})
+        for k in ("n_real_rows", "n_real_edges"):      # set by pad_batch
+            if hasattr(self, k):
+                setattr(out, k, getattr(self, k))
         return out
 
     @property
@@ -200,6 +204,53 @@ class SimplicialBatch:
         plan["vertices_per_graph"] = torch.bincount(plan["graph_of_vertex"], minlength=self.num_graphs)
         self._plan = plan
         return plan
+
+    def lazy_table(self, plan, key, build):
+        """plan[key], built on first use by build(None). The builder is kept: refresh_() calls build(plan[key]) to refill
+        the table IN PLACE for a batch of new topology - fixed-shape device ops only; the host-side checks of a table run
+        on its first build."""
+        if key not in plan:
+            plan[key] = build(None)
+            plan.setdefault("builders", {})[key] = build
+        return plan[key]
+
+    def refresh_(self, raw: "SimplicialBatch") -> "SimplicialBatch":
+        """Make this DEVICE batch hold `raw` - a batch of exactly the same shapes, i.e. padded to the same capacity
+        (pad_batch), on the CPU or the device - without changing the address of anything: the tensors are copied into this
+        batch's, and every table derived from the topology is rebuilt in place on the current stream with no allocation
+        (after the first call) and no host round trip: the tables of plan() (csmpn_simplex_tables), the target-sorted CSR
+        (ops.Csr.rebuild_) and whatever the models have added to the plan (lazy_table). A training step captured over this
+        batch (csmpn_hip.graphed.GraphedTrainStep) can then be replayed on the new batch. plan() and csr() must have been
+        called. Nothing is validated here: pad_batch has checked the indices on the host; a batch whose row counts per
+        dimension differ from this one's sets bits in plan()["status"] (ops.simplex_tables) instead of writing out of
+        bounds."""
+        from csmpn_hip import ops
+        plan = getattr(self, "_plan", None)
+        if plan is None or self._csr is None:
+            raise RuntimeError("refresh_: call plan() and csr() on the batch first")
+        if sorted(raw._names) != sorted(self._names):
+            raise ValueError(f"refresh_: the batches hold different tensors ({sorted(set(raw._names) ^ set(self._names))})")
+        for k in self._names:
+            if tuple(getattr(raw, k).shape) != tuple(getattr(self, k).shape):
+                raise ValueError(f"refresh_: {k} has shape {tuple(getattr(raw, k).shape)}, this batch "
+                                 f"{tuple(getattr(self, k).shape)} (pad both to one BatchCapacity)")
+        for k in self._names:
+            getattr(self, k).copy_(getattr(raw, k), non_blocking=True)
+        for k in ("n_real_rows", "n_real_edges"):
+            if hasattr(raw, k):
+                setattr(self, k, getattr(raw, k))
+        dev = self.x_ind.device
+        if "tables_ws" not in plan:
+            plan["tables_ws"] = ops.simplex_tables_workspace(self.node_types.shape[0], plan["max_dim"], dev)
+            plan["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        ops.simplex_tables(self.x_ind, self.node_types, self.x_ind_batch, self.x_ind_ptr, plan["max_dim"], plan["rows"],
+                           plan["verts"], plan.get("verts_i32"), plan["graph_of_vertex"], plan["vertices_per_graph"],
+                           plan.get("types_i32"), plan["status"], plan["tables_ws"])
+        self._csr.rebuild_(self.edge_index)
+        for key, build in plan.get("builders", {}).items():
+            if key not in ("verts_i32", "types_i32"):      # those two are outputs of csmpn_simplex_tables
+                build(plan[key])
+        return self
 
     def csr(self):
         """Target-sorted adjacency of the batch, built once (device batches only)."""
@@ -243,3 +294,160 @@ def hulls_example(points: np.ndarray, target: Optional[float] = None, max_dim: i
         target = float(ConvexHull(np.asarray(points, dtype=np.float64)).volume)
     c.labels["target"] = torch.tensor(target, dtype=torch.float32)
     return c
+
+
+# ------------------------------------------------------------------------------- fixed-capacity batches
+#
+# A training step captured in a HIP graph (csmpn_hip.graphed.GraphedTrainStep) addresses every tensor of its batch, so it
+# can be replayed only on batches of the same SHAPES. The batches of one dataset share their vertex count (the task
+# models reshape the vertex rows per graph); what changes with the complex is the number of 1-simplices, 2-simplices and
+# adjacencies. pad_batch() fills those up to a capacity with simplices and adjacencies that no real row ever hears of.
+
+
+@dataclass(frozen=True)
+class BatchCapacity:
+    simplices: Tuple[int, ...]   # rows per dimension (n_0, ..., n_maxdim); n_0 is the exact vertex count, never padded
+    edges: int                   # adjacencies
+
+    @property
+    def max_dim(self) -> int:
+        return len(self.simplices) - 1
+
+    @property
+    def rows(self) -> int:
+        return int(sum(self.simplices))
+
+
+def _real_counts(batch, max_dim: int):
+    """(rows per dimension, adjacencies) of the real part of a (possibly padded) batch."""
+    n_rows = int(getattr(batch, "n_real_rows", batch.node_types.shape[0]))
+    n_edges = int(getattr(batch, "n_real_edges", batch.edge_index.shape[1]))
+    nt = batch.node_types[:n_rows].cpu()
+    if nt.numel() and (int(nt.min()) < 0 or int(nt.max()) > max_dim):
+        raise ValueError(f"node_types outside [0, {max_dim}]")
+    return torch.bincount(nt, minlength=max_dim + 1).tolist(), n_edges
+
+
+def capacity_of(batches: Sequence["SimplicialBatch"], slack: float = 0.0) -> BatchCapacity:
+    """The element-wise maximum of the row counts per dimension and of the adjacency counts of `batches`, the d >= 1 counts
+    and the adjacencies enlarged by the fraction `slack` (for batches yet to come) - and always at least one spare
+    1-simplex: filler adjacencies are self-loops on filler rows, so there must be one."""
+    if not batches:
+        raise ValueError("capacity_of: no batches")
+    if slack < 0:
+        raise ValueError("capacity_of: slack must be >= 0")
+    max_dim = int(batches[0].x_ind.shape[1]) - 1
+    if max_dim < 1:
+        raise ValueError("capacity_of: batches without 1-simplices cannot be padded")
+    rows, edges = [0] * (max_dim + 1), 0
+    for b in batches:
+        if int(b.x_ind.shape[1]) - 1 != max_dim:
+            raise ValueError("capacity_of: the batches differ in max_dim")
+        r, e = _real_counts(b, max_dim)
+        rows = [max(a, c) for a, c in zip(rows, r)]
+        edges = max(edges, e)
+    grow = lambda n: int(math.ceil(n * (1.0 + slack)))
+    return BatchCapacity((rows[0], max(grow(rows[1]), rows[1] + 1)) + tuple(grow(n) for n in rows[2:]), grow(edges))
+
+
+_STRUCTURE = ("x_ind", "node_types", "edge_index", "edge_types", "batch", "ptr", "x_ind_batch", "x_ind_ptr")
+
+
+def pad_batch(batch: "SimplicialBatch", capacity: BatchCapacity, simplex_features: Sequence[str] = ()) -> "SimplicialBatch":
+    """A CPU batch of exactly the capacity's shapes: `batch` (collated; an already padded one is cut back to its real part
+    first) with filler simplices and filler adjacencies behind the real ones.
+
+    Real rows keep their indices and real adjacencies their positions; ptr / x_ind_ptr are unchanged and still end at the
+    real row count, so per-graph pooling over them never sees a filler. Filler d-simplices (d >= 1, dimension by dimension
+    behind the last graph): node_types = d, x_ind = the local vertex ids 0..d, batch = x_ind_batch = B - 1 (their vertex
+    rows are real vertices of the last graph: every gather stays in range), zero rows in the per-simplex tensors named in
+    `simplex_features` (every other tensor - per-graph labels, per-vertex targets - is passed on as it is). Filler
+    adjacencies: self-loops on the filler rows, round-robin, edge_types (d, d). No adjacency joins a filler and a real
+    row: messages never cross, a loss that reads real rows sends no gradient into a filler row, and real results do not
+    depend on what the fillers hold.
+
+    Everything the device code will index with is validated HERE, on the host (the in-place rebuild on the device,
+    SimplicialBatch.refresh_, checks nothing): ValueError for node_types outside [0, max_dim], x_ind outside its graph,
+    x_ind_batch / edge_index out of range, a vertex count other than the capacity's, a count above its capacity, filler
+    adjacencies without a filler row, a last graph with fewer than d + 1 vertices. The result records n_real_rows and
+    n_real_edges."""
+    max_dim = capacity.max_dim
+    cpu = {k: getattr(batch, k).cpu() for k in batch._names}
+    S = int(getattr(batch, "n_real_rows", cpu["node_types"].shape[0]))
+    E = int(getattr(batch, "n_real_edges", cpu["edge_index"].shape[1]))
+    S_all = int(cpu["node_types"].shape[0])
+    for name in simplex_features:
+        if name not in cpu:
+            raise ValueError(f"pad_batch: the batch has no tensor {name!r}")
+        if name in _STRUCTURE or int(cpu[name].shape[0]) != S_all:
+            raise ValueError(f"pad_batch: {name!r} is not a per-simplex feature tensor [{S_all}, ...]")
+    if S != S_all or E != int(cpu["edge_index"].shape[1]):        # padded before: back to the real part
+        for k in ("x_ind", "node_types", "batch", "x_ind_batch") + tuple(simplex_features):
+            cpu[k] = cpu[k][:S]
+        cpu["edge_index"] = cpu["edge_index"][:, :E]
+        if "edge_types" in cpu:
+            cpu["edge_types"] = cpu["edge_types"][:E]
+    # numpy from here on (views of the CPU tensors): this runs once per training step on the host, in front of every replay,
+    # and a few dozen small single-threaded array operations cost a fraction of the same tensor operations
+    x_ind, nt, ei = cpu["x_ind"].numpy(), cpu["node_types"].numpy(), cpu["edge_index"].numpy()
+    ptr, xb = cpu["x_ind_ptr"].numpy().astype(np.int64), cpu["x_ind_batch"].numpy()
+    B = int(ptr.shape[0]) - 1
+    if x_ind.ndim != 2 or int(x_ind.shape[1]) < max_dim + 1:
+        raise ValueError(f"pad_batch: x_ind has {tuple(x_ind.shape)[1:]} columns, max_dim = {max_dim} needs {max_dim + 1}")
+    if int(x_ind.shape[0]) != S or int(xb.shape[0]) != S or int(cpu["batch"].shape[0]) != S:
+        raise ValueError("pad_batch: x_ind, node_types, batch and x_ind_batch must have one row per simplex")
+    if B < 1 or int(ptr[0]) != 0 or int(ptr[-1]) != S or bool((ptr[1:] < ptr[:-1]).any()) or not np.array_equal(cpu["ptr"].numpy(), ptr):
+        raise ValueError("pad_batch: ptr / x_ind_ptr must ascend from 0 to the row count")
+    if S and (int(nt.min()) < 0 or int(nt.max()) > max_dim):
+        raise ValueError(f"pad_batch: node_types outside [0, {max_dim}]")
+    for name, g in (("x_ind_batch", xb), ("batch", cpu["batch"].numpy())):
+        if S and (int(g.min()) < 0 or int(g.max()) >= B):
+            raise ValueError(f"pad_batch: {name} outside [0, {B})")
+    size = (ptr[1:] - ptr[:-1])[xb]                      # rows of the graph of every simplex
+    if S and (int(x_ind.min()) < 0 or bool((x_ind >= size[:, None]).any())):
+        raise ValueError("pad_batch: x_ind points outside the graph of its simplex")
+    if ei.ndim != 2 or int(ei.shape[0]) != 2:
+        raise ValueError("pad_batch: edge_index must be [2, E]")
+    if E and (int(ei.min()) < 0 or int(ei.max()) >= S):
+        raise ValueError(f"pad_batch: edge_index outside [0, {S})")
+    counts = np.bincount(nt, minlength=max_dim + 1).tolist()
+    if counts[0] != capacity.simplices[0]:
+        raise ValueError(f"pad_batch: {counts[0]} vertex rows, the capacity has {capacity.simplices[0]} (vertex rows are never padded)")
+    for d in range(1, max_dim + 1):
+        if counts[d] > capacity.simplices[d]:
+            raise ValueError(f"pad_batch: {counts[d]} {d}-simplices exceed the capacity of {capacity.simplices[d]}")
+    if E > capacity.edges:
+        raise ValueError(f"pad_batch: {E} adjacencies exceed the capacity of {capacity.edges}")
+    fill = [0] + [capacity.simplices[d] - counts[d] for d in range(1, max_dim + 1)]
+    n_fill, e_fill = sum(fill), capacity.edges - E
+    if e_fill and not n_fill:
+        raise ValueError(f"pad_batch: {e_fill} filler adjacencies, but the capacity leaves no filler row to carry them")
+    last_vertices = int((nt[int(ptr[B - 1]):] == 0).sum())
+    for d in range(1, max_dim + 1):
+        if fill[d] and last_vertices < d + 1:
+            raise ValueError(f"pad_batch: the last graph has {last_vertices} vertices, a filler {d}-simplex needs {d + 1}")
+    f_types = np.repeat(np.arange(max_dim + 1, dtype=np.int64), fill)
+    cols = np.arange(int(x_ind.shape[1]), dtype=np.int64)[None, :]
+    f_x = np.where(cols <= f_types[:, None], cols, 0)
+    f_graph = np.full((n_fill,), B - 1, dtype=np.int64)
+    f_rows = S + (np.arange(e_fill, dtype=np.int64) % max(n_fill, 1))
+
+    def extend(name, tail, axis=0):
+        a = cpu[name].numpy()
+        return torch.from_numpy(np.ascontiguousarray(np.concatenate([a, tail.astype(a.dtype)], axis=axis)))
+
+    out = dict(cpu)
+    out["x_ind"] = extend("x_ind", f_x)
+    out["node_types"] = extend("node_types", f_types)
+    out["batch"] = extend("batch", f_graph)
+    out["x_ind_batch"] = extend("x_ind_batch", f_graph)
+    out["edge_index"] = extend("edge_index", np.stack([f_rows, f_rows]), axis=1)
+    if "edge_types" in cpu:
+        f_et = f_types[f_rows - S] if e_fill else np.zeros(0, dtype=np.int64)
+        out["edge_types"] = extend("edge_types", np.stack([f_et, f_et], axis=1))
+    for name in simplex_features:
+        t = cpu[name]
+        out[name] = extend(name, np.zeros((n_fill,) + tuple(t.shape[1:]), dtype=t.numpy().dtype))
+    padded = SimplicialBatch(**{k: out[k] for k in batch._names})
+    padded.n_real_rows, padded.n_real_edges = S, E
+    return padded

@@ -59,6 +59,75 @@ def segment_mean(x: torch.Tensor, index: torch.Tensor, n: int) -> torch.Tensor:
     return out / cnt.clamp(min=1).reshape((-1,) + (1,) * (x.dim() - 1))
 
 
+def segment_mean_ptr(x: torch.Tensor, index: torch.Tensor, ptr: torch.Tensor, n: int) -> torch.Tensor:
+    """segment_mean over the rows below ptr[-1] only: the filler rows of a padded batch (csmpn.data.complexes.pad_batch)
+    lie behind the last graph and carry its id, and must not be counted. The same bits as segment_mean where there are
+    none (the same sums in the same order); no host round trip."""
+    real = torch.arange(x.shape[0], device=x.device) < ptr[-1]
+    out = x.new_zeros((n,) + tuple(x.shape[1:]))
+    out.index_add_(0, index, torch.where(real.reshape((-1,) + (1,) * (x.dim() - 1)), x, torch.zeros_like(x)))
+    cnt = x.new_zeros(n)
+    cnt.index_add_(0, index, real.to(x.dtype))
+    return out / cnt.clamp(min=1).reshape((-1,) + (1,) * (x.dim() - 1))
+
+
+# Builders of the index tables the models add to batch.plan() (SimplicialBatch.lazy_table): build(None) makes the table
+# - with its host-side checks, once per batch -, build(table) refills it in place for a batch of new topology and the
+# same shapes (SimplicialBatch.refresh_: fixed-shape device ops, no host round trip).
+
+def _verts_i32_builder(plan, n_rows):
+    def build(out):
+        if out is None:
+            # range check once per batch (the C-ABI would repeat it on every forward, with a host round trip)
+            for v in plan["verts"]:
+                if v.numel() and not (0 <= int(v.min()) and int(v.max()) < n_rows):
+                    raise IndexError(f"simplex vertex rows outside [0, {n_rows}) (x_ind / x_ind_ptr of the batch)")
+            plan["verts_rows_checked"] = n_rows
+            return [v.to(torch.int32).contiguous() for v in plan["verts"]]
+        for o, v in zip(out, plan["verts"]):
+            o.copy_(v)
+        return out
+    return build
+
+
+def _types_i32_builder(batch, n_types):
+    def build(out):
+        nt = batch.node_types
+        if out is None:
+            if nt.numel() and not (0 <= int(nt.min()) and int(nt.max()) < n_types):   # once per batch
+                raise IndexError(f"node_types outside [0, {n_types}) (nn.Embedding would raise too)")
+            return nt.to(torch.int32).contiguous()
+        return out.copy_(nt)
+    return build
+
+
+def _ei_i32_builder(batch):
+    def build(out):
+        ei = batch.edge_index
+        if out is None:
+            return (ei[0].to(torch.int32).contiguous(), ei[1].to(torch.int32).contiguous())
+        out[0].copy_(ei[0])
+        out[1].copy_(ei[1])
+        return out
+    return build
+
+
+def _ptr_i32_builder(batch):
+    def build(out):
+        return batch.x_ind_ptr.to(torch.int32) if out is None else out.copy_(batch.x_ind_ptr)
+    return build
+
+
+def _traj_builder(plan, n_graphs, **kw):
+    def build(out):
+        from csmpn_hip import ops
+        if out is None:
+            return ops.readout_traj_tables(plan["graph_of_vertex"], n_graphs, **kw)
+        return ops.readout_traj_tables(plan["graph_of_vertex"], n_graphs, out=out,
+                                       vertices_per_graph=plan["vertices_per_graph"], **kw)
+    return build
+
+
 def simplex_vertex_rows(batch) -> torch.Tensor:
     """Row (in the batch) of every vertex of every simplex: x_ind is local to its graph."""
     start = batch.x_ind_ptr[:-1][batch.x_ind_batch]
@@ -101,14 +170,7 @@ class SimplexEmbedding(nn.Module):
             if all(ops.embed_cemlp_supported(self.cl_feature_embedding[d].binding(), d + 1, t0.shape[1])
                    for d in range(1, self.max_dim + 1)):
                 emb_feat = self.algebra.embed_grade(t0, g0).contiguous()      # [S, K, D]: no vertex-order blow-up
-                if "verts_i32" not in plan:
-                    plan["verts_i32"] = [v.to(torch.int32).contiguous() for v in plan["verts"]]
-                    # range check once per batch (the C-ABI would repeat it on every forward, with a host round trip)
-                    S = int(emb_feat.shape[0])
-                    for v in plan["verts"]:
-                        if v.numel() and not (0 <= int(v.min()) and int(v.max()) < S):
-                            raise IndexError(f"simplex vertex rows outside [0, {S}) (x_ind / x_ind_ptr of the batch)")
-                    plan["verts_rows_checked"] = S
+                batch.lazy_table(plan, "verts_i32", _verts_i32_builder(plan, int(emb_feat.shape[0])))
         # (Tried in round 4 and dropped: the modules of the dimensions as parallel branches on side streams - forward and,
         # through autograd's stream rule, backward. Two long independent chains overlap in a replayed HIP graph (1 618 ->
         # 851 us in a probe), these short forks do not pay for their joins: md17 step 3.13 -> 3.27 ms, hulls 4.80 -> 4.91.)
@@ -164,13 +226,9 @@ def embedded_type_attributes(algebra: CliffordAlgebra, table: nn.Embedding, batc
     if table.weight.is_cuda and table.weight.dtype == torch.float32 and table.weight.numel() <= 64:
         from csmpn_hip import ops
         plan = batch.plan(max_dim)
-        if "types_i32" not in plan:
-            nt = batch.node_types
-            if nt.numel() and not (0 <= int(nt.min()) and int(nt.max()) < table.num_embeddings):   # once per batch
-                raise IndexError(f"node_types outside [0, {table.num_embeddings}) (nn.Embedding would raise too)")
-            plan["types_i32"] = nt.to(torch.int32).contiguous()
-            plan["ei_i32"] = (ei[0].to(torch.int32).contiguous(), ei[1].to(torch.int32).contiguous())
-        return ops.type_attr_apply(table.weight, plan["types_i32"], plan["ei_i32"][0], plan["ei_i32"][1], algebra.dim)
+        types_i32 = batch.lazy_table(plan, "types_i32", _types_i32_builder(batch, table.num_embeddings))
+        ei_i32 = batch.lazy_table(plan, "ei_i32", _ei_i32_builder(batch))
+        return ops.type_attr_apply(table.weight, types_i32, ei_i32[0], ei_i32[1], algebra.dim)
     return type_attributes(algebra, type_embedding(table, batch.node_types), ei)
 
 
@@ -212,12 +270,11 @@ class HullsSimplicialMPNN(nn.Module):
         if x.is_cuda and len(self.projection) == 1 and head.out_features == 1 and head.weight.dim() == 3:
             # fused readout + loss (csmpn_readout_mse_*): blade 0 of the projection, mean per graph, squared error
             from csmpn_hip import ops
-            if "ptr_i32" not in plan:
-                plan["ptr_i32"] = batch.x_ind_ptr.to(torch.int32)
-            loss, _pred = ops.readout_mse(x, head.weight, getattr(head, "bias", None), plan["ptr_i32"], batch.target, n)
+            ptr_i32 = batch.lazy_table(plan, "ptr_i32", _ptr_i32_builder(batch))
+            loss, _pred = ops.readout_mse(x, head.weight, getattr(head, "bias", None), ptr_i32, batch.target, n)
         else:
             pred = self.projection(x)[:, :, 0]
-            pred = segment_mean(pred, batch.x_ind_batch, B)
+            pred = segment_mean_ptr(pred, batch.x_ind_batch, batch.x_ind_ptr, B)
             loss = (pred.squeeze(-1) - batch.target) ** 2
         return loss.mean(0), {"loss": loss}
 
@@ -271,10 +328,9 @@ class MD17SimplicialMPNN(nn.Module):
             # fused head + loss (csmpn_readout_traj_*): the CEMLP of the head on the vertex rows, then MVLinear -> vector blades
             # -> + loc -> per-graph MSE / ADE / FDE in one launch each way
             from csmpn_hip import ops
-            if "traj" not in plan:
-                plan["traj"] = ops.readout_traj_tables(plan["graph_of_vertex"], B)
+            traj = batch.lazy_table(plan, "traj", _traj_builder(plan, B))
             z = self.projection[0](x.index_select(0, vr))
-            per_graph, _pv, _pred = ops.readout_traj(z, head.weight, loc_node, batch.y, plan["traj"], 3)
+            per_graph, _pv, _pred = ops.readout_traj(z, head.weight, loc_node, batch.y, traj, 3)
             loss = per_graph[:, 0]
             return loss.mean() + _zero_grad_of(head), {"loss": loss, "ade_loss": per_graph[:, 1], "fde_loss": per_graph[:, 2]}
         pred = self.projection(x.index_select(0, vr))[..., 1:4]
@@ -333,9 +389,8 @@ class MotionSimplicialMPNN(nn.Module):
         head = self.projection[0]
         if head.out_features == 1 and _fused_traj_readout(head, x):
             from csmpn_hip import ops      # fused head + loss: vertex rows gathered inside the kernel
-            if "traj" not in plan:
-                plan["traj"] = ops.readout_traj_tables(plan["graph_of_vertex"], B, vertex_rows=vr, n_rows=x.shape[0])
-            _pg, loss, _pred = ops.readout_traj(x, head.weight, node_pos, batch.y, plan["traj"], 3)
+            traj = batch.lazy_table(plan, "traj", _traj_builder(plan, B, vertex_rows=vr, n_rows=x.shape[0]))
+            _pg, loss, _pred = ops.readout_traj(x, head.weight, node_pos, batch.y, traj, 3)
             return loss.mean() + _zero_grad_of(head), {"loss": loss}
         pred = node_pos + self.projection(x.index_select(0, vr))[..., 0, 1:4]
         loss = ((pred - batch.y.reshape(-1, 3)) ** 2).mean(dim=1)
@@ -404,9 +459,8 @@ class NBASimplicialMPNN(nn.Module):
         vr = plan["vertex_rows"]
         if _fused_traj_readout(self.projection, x):
             from csmpn_hip import ops      # fused head + loss: the last agent of every graph (the ball) is not scored
-            if "traj" not in plan:
-                plan["traj"] = ops.readout_traj_tables(plan["graph_of_vertex"], B, vertex_rows=vr, n_rows=x.shape[0], unscored_last=1)
-            per_graph, _pv, _pred = ops.readout_traj(x, self.projection.weight, None, batch.y, plan["traj"], 2)
+            traj = batch.lazy_table(plan, "traj", _traj_builder(plan, B, vertex_rows=vr, n_rows=x.shape[0], unscored_last=1))
+            per_graph, _pv, _pred = ops.readout_traj(x, self.projection.weight, None, batch.y, traj, 2)
             ade = per_graph[:, 1]
             return ade.mean() + _zero_grad_of(self.projection), {"loss": ade, "ade_loss": ade, "fde_loss": per_graph[:, 2]}
         pred = self.projection(x.index_select(0, vr))[..., 1:3]                      # [V, num_out, 2]

@@ -10,6 +10,12 @@ trajectories of one molecule, repeated epochs over cached batches) this module c
 embedding, every EGCL layer forward and backward, readout, loss and the optimizer update - once and replays
 it; per step the host copies the new features into the captured buffers and launches one graph.
 
+Batches of CHANGING topology (a shuffled training loop: another complex in every batch) replay the same graph when the
+step is built with a `capacity` (csmpn.data.complexes.BatchCapacity): every batch is padded to the capacity's shapes on the
+host (pad_batch: filler simplices and self-loop adjacencies that no real row hears of), copied into the captured buffers,
+and the tables derived from the topology - the target-sorted CSR, the index tables of the embedding and of the readout -
+are rebuilt in place on the device (SimplicialBatch.refresh_: csmpn_simplex_tables, csmpn_csr_build) in front of the replay.
+
 The kernels launched inside are the same C-ABI calls as in eager mode (they take the current stream); the
 CSR and the embedding index tables are built before capture (their only host round trips).
 """
@@ -80,9 +86,32 @@ class GraphedTrainStep:
     model(batch) must return (loss, aux) like the reference's task models; `optimizer` must be
     graph-capturable (torch.optim.Adam(..., capturable=True)); `batch` is a device SimplicialBatch
     whose tensors become the captured input buffers. `feature_names`: the batch attributes that change
-    from step to step (everything else - topology, types - is part of the captured graph)."""
+    from step to step (everything else - topology, types - is part of the captured graph).
 
-    def __init__(self, model, optimizer, batch, feature_names: Iterable[str], warmup: int = 2, max_dim: Optional[int] = None):
+    capacity (a csmpn.data.complexes.BatchCapacity, e.g. capacity_of(batches, slack)): the step serves batches of any
+    topology that fits. `batch` (CPU or device, padded or not) is padded to the capacity and moved to `device` (default: the
+    batch's own if it is a GPU, else the current one); `simplex_features` names its per-simplex tensors, which get zero
+    filler rows (default: those of `feature_names` with one row per simplex). step(batch=collated_cpu_batch) then pads that
+    batch (ValueError BEFORE anything is launched if it does not fit or its indices are out of range - run it eagerly),
+    refreshes the captured batch in place and replays. The refresh runs eagerly on the current stream in front of the
+    replay; it is not part of the captured graph. status(): the device status word of the table rebuild (0 = every batch
+    so far had the row counts of the capacity; one small copy with a synchronisation - read it where the loop syncs
+    anyway)."""
+
+    def __init__(self, model, optimizer, batch, feature_names: Iterable[str], warmup: int = 2, max_dim: Optional[int] = None,
+                 capacity=None, simplex_features: Optional[Iterable[str]] = None, device=None):
+        self.capacity = capacity
+        self.simplex_features = None
+        if capacity is not None:
+            from csmpn.data.complexes import pad_batch
+            if device is None:
+                device = batch.edge_index.device if batch.edge_index.is_cuda else torch.device("cuda", torch.cuda.current_device())
+            if simplex_features is None:
+                rows = int(batch.node_types.shape[0])
+                simplex_features = [k for k in feature_names if hasattr(batch, k) and getattr(batch, k).dim() >= 1
+                                    and int(getattr(batch, k).shape[0]) == rows]
+            self.simplex_features = tuple(simplex_features)
+            batch = pad_batch(batch, capacity, self.simplex_features).to(device)
         dev = batch.edge_index.device
         if dev.type != "cuda":
             raise RuntimeError("GraphedTrainStep needs a device batch (no CPU fallback)")
@@ -121,6 +150,11 @@ class GraphedTrainStep:
                 for v in st.values():
                     if torch.is_tensor(v):
                         v.zero_()
+        if capacity is not None:
+            # every table the models have added to the plan exists now: one refresh onto itself allocates the workspaces of
+            # the in-place rebuild and leaves the tables as the rebuild writes them - the state every later step starts from
+            batch.refresh_(batch)
+            torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss, self.aux = self._eager_step()
@@ -140,7 +174,22 @@ class GraphedTrainStep:
                 raise KeyError(f"{name!r} was not declared as a changing feature")
             getattr(self.batch, name).copy_(value, non_blocking=True)
 
-    def step(self, features: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+    def load_batch(self, batch):
+        """Pad `batch` (collated, CPU or device) to the capacity and make the captured batch hold it. ValueError - before
+        anything is launched - if it does not fit or its indices are out of range."""
+        if self.capacity is None:
+            raise RuntimeError("GraphedTrainStep was built without a capacity: it replays ONE topology (load(features))")
+        from csmpn.data.complexes import pad_batch
+        self.batch.refresh_(pad_batch(batch, self.capacity, self.simplex_features))
+
+    def status(self) -> int:
+        """The status word of the table rebuilds so far (ops.simplex_tables; 0 = fine). Synchronises."""
+        word = self.batch._plan.get("status")
+        return 0 if word is None else int(word.item())
+
+    def step(self, features: Optional[Dict[str, torch.Tensor]] = None, batch=None) -> torch.Tensor:
+        if batch is not None:
+            self.load_batch(batch)
         if features:
             self.load(features)
         self.graph.replay()

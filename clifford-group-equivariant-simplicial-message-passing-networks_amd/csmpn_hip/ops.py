@@ -431,7 +431,7 @@ def segment_reduce(rows, out, add=None, sub=None, accumulate=True):
 class Csr:
     """Target-sorted adjacency of one complex (built once, reused by every layer and step)."""
 
-    __slots__ = ("perm", "src", "dst", "deg", "row_ptr", "n_edges", "n_nodes", "build_ms", "_src_order")
+    __slots__ = ("perm", "src", "dst", "deg", "row_ptr", "n_edges", "n_nodes", "build_ms", "_src_order", "_ws")
 
     def source_order(self):
         """(row_ptr_src, order): the sorted edge positions grouped by source (deterministic mode)."""
@@ -459,6 +459,7 @@ class Csr:
         i32 = dict(dtype=torch.int32, device=dev)
         self.n_edges, self.n_nodes = E, n_nodes
         self._src_order = None
+        self._ws = None
         self.perm = torch.empty(max(E, 1), **i32)
         self.src = torch.empty(max(E, 1), **i32)
         self.dst = torch.empty(max(E, 1), **i32)
@@ -475,6 +476,36 @@ class Csr:
             t1.record()
             t1.synchronize()
             self.build_ms = t0.elapsed_time(t1)
+
+
+    def rebuild_(self, edge_index: torch.Tensor) -> "Csr":
+        """The same five tensors - and the source order, if it exists - rebuilt IN PLACE for another adjacency of the same
+        size (a batch of new topology under a captured step, csmpn_hip.graphed): same data_ptrs, no allocation after the
+        first call (the workspace is kept from then on), no host synchronisation - the indices are NOT range-checked here
+        (CSMPN_FLAG_NO_VALIDATE: the caller has validated them, csmpn.data.complexes.pad_batch; an entry outside
+        [0, n_nodes) is mapped to node 0). Re-stamps the cache entry on `edge_index` (ops.get_csr) with its version."""
+        if not edge_index.is_cuda or edge_index.device != self.src.device:
+            raise RuntimeError("edge_index must live on the device of the CSR (no CPU fallback)")
+        if edge_index.dtype != torch.int64 or tuple(edge_index.shape) != (2, self.n_edges) or not edge_index.is_contiguous():
+            raise RuntimeError(f"Csr.rebuild_: edge_index must be contiguous int64 [2, {self.n_edges}] (the size it was built for)")
+        dev = self.src.device
+        lib = native.lib()
+        if self._ws is None:
+            self._ws = torch.empty(int(lib.csmpn_csr_workspace_bytes(self.n_edges, self.n_nodes)), dtype=torch.uint8, device=dev)
+        ws = self._ws
+        with torch.cuda.device(dev):
+            check(lib.csmpn_csr_build(edge_index.data_ptr(), self.n_edges, self.n_nodes, self.perm.data_ptr(),
+                                      self.src.data_ptr(), self.dst.data_ptr(), self.deg.data_ptr(), self.row_ptr.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), native.FLAG_NO_VALIDATE, _stream(dev)))
+            if self._src_order is not None:
+                rp, order = self._src_order
+                check(lib.csmpn_csr_source_order(self.src.data_ptr(), self.n_edges, self.n_nodes, order.data_ptr(),
+                                                 rp.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+        try:
+            edge_index._csmpn_csr = (edge_index._version, self)
+        except Exception:
+            pass
+        return self
 
 
 class CsrSlice:
@@ -1265,32 +1296,48 @@ class _ReadoutTrajFn(torch.autograd.Function):
         return gx, gw, None, None, None, None
 
 
-def readout_traj_tables(graph_of_vertex, n_graphs, vertex_rows=None, n_rows=None, unscored_last=0):
+def readout_traj_tables(graph_of_vertex, n_graphs, vertex_rows=None, n_rows=None, unscored_last=0, out=None,
+                        vertices_per_graph=None):
     """Index tables of csmpn_readout_traj_* (int32, on the device of graph_of_vertex), built once per batch:
     vptr [B + 1] (the vertices of a graph are contiguous in the vertex list), graph_of_vertex [V]; with `vertex_rows` (rows of
     the layer output that are vertices) also its inverse vertex_of_row [n_rows]; unscored_last = k: the last k vertices of
-    every graph are not scored (NBA: the ball) and the target rows number the scored ones consecutively."""
+    every graph are not scored (NBA: the ball) and the target rows number the scored ones consecutively.
+    out = the dict of an earlier call with the same shapes and options: its tensors are refilled IN PLACE for another batch
+    (same data_ptrs) with fixed-shape device ops only - no host round trip, so the contiguity check of the first build is
+    not repeated, and `vertices_per_graph` [B] (the histogram of graph_of_vertex) must then be given: bincount would
+    synchronise."""
     gov = graph_of_vertex.to(torch.int64)
     dev = gov.device
     V = int(gov.shape[0])
-    if V > 1 and bool((gov[1:] < gov[:-1]).any()):
-        raise RuntimeError("trajectory readout: the vertices of a graph must be contiguous in the vertex list")
-    cnt = torch.bincount(gov, minlength=n_graphs)
+    if out is None:
+        if V > 1 and bool((gov[1:] < gov[:-1]).any()):
+            raise RuntimeError("trajectory readout: the vertices of a graph must be contiguous in the vertex list")
+        cnt = torch.bincount(gov, minlength=n_graphs)
+    else:
+        cnt = vertices_per_graph.to(torch.int64)
     vptr = torch.zeros(n_graphs + 1, dtype=torch.int64, device=dev)
     vptr[1:] = torch.cumsum(cnt, 0)
     trow = None
     if unscored_last:
-        pos = torch.arange(V, device=dev) - vptr[:-1][gov]                 # position inside the graph
-        scored = pos < (cnt[gov] - unscored_last)
+        pos = torch.arange(V, device=dev) - vptr[:-1].index_select(0, gov)   # position inside the graph
+        scored = pos < (cnt.index_select(0, gov) - unscored_last)
         first = torch.cumsum(torch.cat([cnt.new_zeros(1), (cnt - unscored_last).clamp(min=0)[:-1]]), 0)
-        trow = torch.where(scored, first[gov] + pos, torch.full_like(pos, -1)).to(torch.int32).contiguous()
+        trow = torch.where(scored, first.index_select(0, gov) + pos, torch.full_like(pos, -1)).to(torch.int32).contiguous()
     vrows = vof = None
     if vertex_rows is not None:
         vrows = vertex_rows.to(torch.int32).contiguous()
         vof = torch.full((int(n_rows),), -1, dtype=torch.int32, device=dev)
-        vof[vertex_rows.long()] = torch.arange(V, dtype=torch.int32, device=dev)
-    return {"vrows": vrows, "vertex_of_row": vof, "trow": trow, "graph_of_vertex": gov.to(torch.int32).contiguous(),
-            "vptr": vptr.to(torch.int32).contiguous()}
+        vof.index_copy_(0, vertex_rows.long(), torch.arange(V, dtype=torch.int32, device=dev))
+    new = {"vrows": vrows, "vertex_of_row": vof, "trow": trow, "graph_of_vertex": gov.to(torch.int32).contiguous(),
+           "vptr": vptr.to(torch.int32).contiguous()}
+    if out is None:
+        return new
+    for k, v in new.items():
+        if (v is None) != (out[k] is None):
+            raise RuntimeError(f"readout_traj_tables: table {k!r} exists on one side only (other options than the first build?)")
+        if v is not None:
+            out[k].copy_(v)
+    return out
 
 
 def readout_traj(x, weight, loc, target, tables, n):
@@ -1308,3 +1355,61 @@ def readout_traj_supported(head, x) -> bool:
 def readout_mse(x, weight, bias, graph_ptr_i32, target, n):
     """(loss per graph, prediction per graph); graph_ptr_i32 [B+1] int32 device tensor (rows of a graph are contiguous)."""
     return _ReadoutMseFn.apply(x, weight, bias, graph_ptr_i32, target, int(n))
+
+
+# --------------------------------------------------------------------------------- per-batch index tables on the device
+
+STATUS_TYPE_OUTSIDE, STATUS_CLAMPED = 16, 32   # bits of the status word of simplex_tables; bit d = the count of dimension d
+
+
+def simplex_tables_workspace(n_rows: int, max_dim: int, device) -> torch.Tensor:
+    """Workspace of simplex_tables for batches of n_rows rows (uninitialised device bytes)."""
+    return torch.empty(max(int(native.lib().csmpn_simplex_tables_workspace_bytes(int(n_rows), int(max_dim))), 16),
+                       dtype=torch.uint8, device=device)
+
+
+def simplex_tables(x_ind, node_types, x_ind_batch, x_ind_ptr, max_dim, rows, verts, verts_i32, graph_of_vertex,
+                   vertices_per_graph, types_i32, status, workspace):
+    """csmpn_simplex_tables: the tables of SimplicialBatch.plan() written into the given buffers (rows[d] int64 [n_d],
+    verts[d] int64 [n_d (d+1)!, d+1], verts_i32 = None or a list with None / int32 tensors of verts' shapes, graph_of_vertex
+    int64 [n_0], vertices_per_graph int64 [B], types_i32 = None or int32 [S], status = None or a uint32 / int32 device word)
+    on the current stream: no allocation, no host round trip. The expected counts n_d are the lengths of rows[d]."""
+    if not x_ind.is_cuda:
+        raise RuntimeError("simplex_tables needs device tensors (no CPU fallback)")
+    for name, t in (("x_ind", x_ind), ("node_types", node_types), ("x_ind_batch", x_ind_batch), ("x_ind_ptr", x_ind_ptr),
+                    ("graph_of_vertex", graph_of_vertex), ("vertices_per_graph", vertices_per_graph)):
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.device != x_ind.device:
+            raise RuntimeError(f"simplex_tables: {name} must be a contiguous int64 tensor on the device of x_ind")
+    nd = int(max_dim) + 1
+    if len(rows) != nd or len(verts) != nd or (verts_i32 is not None and len(verts_i32) != nd):
+        raise RuntimeError(f"simplex_tables: max_dim = {max_dim} needs {nd} tables of each kind")
+    S, B = int(node_types.shape[0]), int(x_ind_ptr.shape[0]) - 1
+    if x_ind.dim() != 2 or x_ind.shape[0] != S or x_ind_batch.shape[0] != S or vertices_per_graph.shape[0] != B:
+        raise RuntimeError("simplex_tables: x_ind [S, M], node_types [S], x_ind_batch [S], x_ind_ptr [B + 1], vertices_per_graph [B]")
+    fact = 1
+    for d in range(nd):
+        fact *= d + 1
+        n_d = int(rows[d].shape[0])
+        ok = rows[d].dtype == torch.int64 and verts[d].dtype == torch.int64 and tuple(verts[d].shape) == (n_d * fact, d + 1) \
+            and rows[d].is_contiguous() and verts[d].is_contiguous()
+        vi = None if verts_i32 is None else verts_i32[d]
+        if vi is not None:
+            ok = ok and vi.dtype == torch.int32 and vi.shape == verts[d].shape and vi.is_contiguous()
+        if not ok and nd <= 4:   # (max_dim > 3: the entry point refuses before it reads a table)
+            raise RuntimeError(f"simplex_tables: tables of dimension {d} must be rows int64 [n], verts int64 [n * {fact}, {d + 1}] (+ int32 copy)")
+    if graph_of_vertex.shape[0] != rows[0].shape[0]:
+        raise RuntimeError("simplex_tables: graph_of_vertex must have the length of rows[0]")
+    if types_i32 is not None and (types_i32.dtype != torch.int32 or types_i32.shape[0] != S or not types_i32.is_contiguous()):
+        raise RuntimeError("simplex_tables: types_i32 must be contiguous int32 [S]")
+    if status is not None and (status.element_size() != 4 or status.numel() < 1 or not status.is_cuda):
+        raise RuntimeError("simplex_tables: status must be a 4-byte device word")
+    dev = x_ind.device
+    arr = lambda ts: (C.c_void_p * nd)(*[None if t is None or t.numel() == 0 else t.data_ptr() for t in ts])
+    expected = (C.c_int64 * nd)(*[int(r.shape[0]) for r in rows])
+    r_arr, v_arr, i_arr = arr(rows), arr(verts), None if verts_i32 is None else arr(verts_i32)   # host arrays: alive over the call
+    with torch.cuda.device(dev):
+        check(native.lib().csmpn_simplex_tables(
+            x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), x_ind_batch.data_ptr(), x_ind_ptr.data_ptr(), S, B,
+            int(max_dim), C.addressof(expected), C.addressof(r_arr), C.addressof(v_arr),
+            None if i_arr is None else C.addressof(i_arr), graph_of_vertex.data_ptr(),
+            vertices_per_graph.data_ptr(), _ptr(types_i32), _ptr(status), workspace.data_ptr(), workspace.numel(), _stream(dev)))

@@ -107,7 +107,7 @@ __global__ void readout_bwd_kernel(const float* w, int wstride, int C, int D, co
     const int e = (int)(t - s * per);
     const int c = e / D, d = e - c * D;
     float v = 0.f;
-    if (d == 0) {
+    if (d == 0 && s < ptr[B]) {   // rows behind the last graph (the fillers of a padded batch) are in no mean: zero gradient
         int lo = 0, hi = B;   // graph of row s: last g with ptr[g] <= s
         while (hi - lo > 1) {
             const int mid = (lo + hi) >> 1;

@@ -408,6 +408,35 @@ typedef struct csmpn_vertex_block {
 int csmpn_simplex_rows(int n, const csmpn_vertex_block* blocks, int n_blocks, const int64_t* verts, int64_t n_rows,
                        int32_t verts_per_row, int64_t n_feature_rows, float* out, void* stream);
 
+/* Index tables of the embedding stage, rebuilt on the device for a batch of new topology and unchanged row counts (what
+ * SimplicialBatch.plan() builds on the host with nonzero / indexing / bincount), so that a captured training step can be
+ * replayed on it: no allocation, no host round trip, every launch on `stream`.
+ *   inputs (device, int64): x_ind [n_rows, x_ind_cols] (vertex ids local to the row's graph; x_ind_cols > max_dim),
+ *     node_types [n_rows], x_ind_batch [n_rows] (graph of every row), x_ind_ptr [n_graphs + 1] (first row of every graph);
+ *   n_expected (HOST, int64 [max_dim + 1]): the row count n_d of every dimension = the lengths of the output buffers;
+ *   rows / verts / verts_i32 (HOST arrays of max_dim + 1 DEVICE pointers; verts_i32 or single entries of it may be NULL,
+ *     rows[d] / verts[d] may be NULL where n_d = 0):
+ *     rows[d]  int64 [n_d]: the rows of type d, ascending (a stable compaction by type, implemented as a scan);
+ *     verts[d] int64 [n_d * (d+1)!, d+1]: for every such row r in that order and every vertex order pi in lexicographic
+ *              order (itertools.permutations(range(d+1))), x_ind[r, pi[j]] + x_ind_ptr[x_ind_batch[r]]; verts_i32[d]: the
+ *              same values as int32;
+ *   graph_of_vertex int64 [n_0] = x_ind_batch[rows[0]]; vertices_per_graph int64 [n_graphs] = its histogram;
+ *   types_i32 int32 [n_rows] (may be NULL) = node_types.
+ * Safety: vertex rows are clamped to [0, n_rows) and graph ids to [0, n_graphs); a row whose rank among the rows of its
+ * type is not below n_d writes nothing, so a wrong n_expected never writes outside a buffer. Such findings are OR-ed into
+ * *status (device, may be NULL; never read by the call, never cleared by it): bit d (d = 0..3) = the batch holds another
+ * number of rows of type d than n_expected[d] (fewer: the tail of the tables keeps its old contents), bit 4 = a type
+ * outside [0, max_dim] (the row is in no table), bit 5 = a vertex row or graph id was clamped.
+ * max_dim <= 3 (24 vertex orders); larger: CSMPN_ERR_UNSUPPORTED. n_rows, n_graphs in [1, 2^31).
+ * workspace: csmpn_simplex_tables_workspace_bytes(n_rows, max_dim) bytes of device memory (host-only query; 0 for sizes
+ * the entry point rejects); needs no initialisation. */
+size_t csmpn_simplex_tables_workspace_bytes(int64_t n_rows, int32_t max_dim);
+int csmpn_simplex_tables(const int64_t* x_ind, int32_t x_ind_cols, const int64_t* node_types, const int64_t* x_ind_batch,
+                         const int64_t* x_ind_ptr, int64_t n_rows, int64_t n_graphs, int32_t max_dim,
+                         const int64_t* n_expected, int64_t* const* rows, int64_t* const* verts, int32_t* const* verts_i32,
+                         int64_t* graph_of_vertex, int64_t* vertices_per_graph, int32_t* types_i32, uint32_t* status,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fused simplex feature embedding (round 3; hulls_cssmpnn.py:96-125: vertex features of every d-simplex in all (d+1)!
  * vertex orders -> CEMLP -> sum over the orders), for the shapes the wide parity-lane kernels serve as standalone CEMLPs
  * (Cl(5,0) / Cl(4,1), 16 / 24 / 28 / 32 output channels, at most 8 input channels = verts_per_row * channels_per_vertex);
@@ -489,7 +518,9 @@ int csmpn_type_attr_backward_det(int n, int32_t n_types, int32_t k, const int32_
  * bias at MVLinear.bias or NULL. The simplices of graph g are rows [graph_ptr[g], graph_ptr[g+1]).
  * channel_sums [n_graphs, channels] receives sum_s x[s][c][0] (the weight gradient is coef^T channel_sums).
  * backward: gx[s][c][d] = (d == 0) ? coef[graph(s)] * weight[c * weight_stride] : 0 (overwritten), with
- * coef_g = dL/dloss_g * 2 (pred_g - target_g) / max(count_g, 1) computed by the caller. */
+ * coef_g = dL/dloss_g * 2 (pred_g - target_g) / max(count_g, 1) computed by the caller. Rows at or behind
+ * graph_ptr[n_graphs] (n_rows may exceed it: the filler rows of a padded batch) belong to no graph: they are not read by
+ * the forward and get gx = 0. */
 int csmpn_readout_mse_forward(int n, const float* x, const float* weight, int32_t weight_stride, const float* bias,
                               int64_t n_rows, int32_t channels, const int32_t* graph_ptr, int64_t n_graphs,
                               const float* target, float* pred, float* loss, float* channel_sums, void* stream);

@@ -1,10 +1,21 @@
 """Whole-model training step, eager vs one HIP graph (csmpn_hip.graphed.GraphedTrainStep).
 
     python tools/model_step_bench.py [--batch 16] [--steps 30]
+    python tools/model_step_bench.py --model md17 --varying 8 [--slack 0.0] [--pkg-root OTHER_TREE]
 
 The convex-hulls task model at the reference's configuration (csmpn/configs/hulls.yaml: Cl(5,0), 28
 hidden channels, 3 layers, batch size 16, 8 points per hull, Adam lr 1e-3) on synthetic hulls. Prints one
 JSON line with the step times and the simplices / adjacencies of the batch.
+
+--varying K: K different batches of the model (another complex in every graph), as a shuffled training loop sees them:
+  eager_varying_ms_per_step    the eager step on a FRESH device batch per step - host-to-device copy, plan() and csr()
+                               included: what such a loop costs without a capacity
+  graphed_varying_ms_per_step  GraphedTrainStep(capacity=capacity_of(batches, slack)).step(batch=...) cycling through the K
+                               batches: pad on the host, copy, rebuild the tables on the device, replay
+  graphed_fixed_ms_per_step    the same captured step replayed on one topology (no refresh): the floor at this capacity
+  fill_rows / fill_adjacencies real / padded, mean over the K batches
+--pkg-root: import the package from another tree (a build of another commit) with this same tool file; a tree without
+  the capacity interface reports the eager figure only.
 """
 import argparse
 import importlib
@@ -77,30 +88,11 @@ def op_sites(eager, steps=2):
         print(f"{us / steps:8.1f} us {n / steps:5.1f}x  {k[0]:70s} {k[1]:40s} {k[2]}")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=16)
-    ap.add_argument("--steps", type=int, default=30)
-    ap.add_argument("--points", type=int, default=8)
-    ap.add_argument("--model", default="hulls", choices=["hulls", "md17", "motion", "nba"])
-    ap.add_argument("--no-fused-adam", action="store_true", help="torch.optim.Adam(foreach) instead of fused=True")
-    ap.add_argument("--no-fused-grads", action="store_true", help="hand parameter gradients to autograd (one add kernel per tensor)")
-    ap.add_argument("--profile-ops", action="store_true", help="torch.profiler over 3 eager steps: the small GPU kernels by Python call site")
-    ap.add_argument("--no-flat-params", action="store_true", help="optimizer over the module's ~1 000 parameter tensors instead of ONE flat buffer (csmpn_hip.graphed.flatten_parameters)")
-    ap.add_argument("--op-sites", action="store_true", help="GPU kernels of one eager step by the package line that launched them")
-    args = ap.parse_args()
-    importlib.import_module(PKG)
-    from csmpn.data import complexes as cx
-    from csmpn.models import simplicial_mpnn as M
-    from csmpn_hip.graphed import GraphedTrainStep
-    from csmpn_hip import ops
-    ops.set_fused_grad_accumulation(not args.no_fused_grads)
-
-    dev = torch.device("cuda:0")
-    rng = np.random.default_rng(0)
+def make_batch(args, rng, cx):
+    """One collated CPU batch of the chosen model and the names of its changing tensors."""
     if args.model == "hulls":
         batch = cx.collate([cx.hulls_example(rng.standard_normal((args.points, 5)).astype(np.float32))
-                            for _ in range(args.batch)]).to(dev)
+                            for _ in range(args.batch)])
         features = ["input", "target"]
     elif args.model == "motion":
         # motion-capture-shaped batch (motion_cssmpnn.py: Cl(3,0), 16 channels, 4 layers, aggr = mean): 31 joints per
@@ -118,7 +110,6 @@ def main():
         batch = cx.collate(graphs)
         batch.y = torch.cat([g.features["pos"][: g.n_vertices] + 0.1 * torch.randn(g.n_vertices, 3) for g in graphs], dim=0)
         batch._names.append("y")
-        batch = batch.to(dev)
         features = ["pos", "vel", "y"]
     elif args.model == "nba":
         # NBA-shaped batch (nba_cssmpnn.py:12-190: Cl(2,0), 40 channels, 4 layers, aggr = sum): 6 agents in the plane (5 players +
@@ -137,7 +128,6 @@ def main():
         batch = cx.collate(graphs)
         batch.y = torch.cat(ys, dim=0)
         batch._names.append("y")
-        batch = batch.to(dev)
         features = ["pos", "vel", "y"]
     else:
         # MD17-shaped batch (md17_cssmpnn.py; csmpn/configs/md17.yaml: Cl(3,0), 32 channels, 5 layers): 21 atoms
@@ -156,8 +146,90 @@ def main():
         batch = cx.collate(graphs)
         batch.y = torch.cat([g.features["loc"][: g.n_vertices] + 0.1 * torch.randn(g.n_vertices, F, 3) for g in graphs], dim=0)
         batch._names.append("y")
-        batch = batch.to(dev)
         features = ["loc", "vel", "charges", "y"]
+    return batch, features
+
+
+LABELS = {"hulls": "hulls (Cl(5,0), 28 channels, 3 layers)", "md17": "md17 (Cl(3,0), 32 channels, 5 layers)",
+          "motion": "motion (Cl(3,0), 16 channels, 4 layers)", "nba": "nba (Cl(2,0), 40 channels, 4 layers)"}
+
+
+def timed(fn, steps, warm=5):
+    """ms per call of fn(i), the device drained before and behind the window."""
+    for i in range(warm):
+        fn(i)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(steps):
+        fn(warm + i)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def varying(args, rng, cx, M, GraphedTrainStep, dev):
+    from csmpn_hip.graphed import flatten_parameters
+    K = args.varying
+    made = [make_batch(args, rng, cx) for _ in range(K)]
+    batches, features = [m[0] for m in made], made[0][1]
+    torch.manual_seed(0)
+    model = {"hulls": M.HullsSimplicialMPNN, "md17": M.MD17SimplicialMPNN, "motion": M.MotionSimplicialMPNN,
+             "nba": M.NBASimplicialMPNN}[args.model]().to(dev)
+    opt_params = model.parameters() if args.no_flat_params else [flatten_parameters(model)]
+    opt = torch.optim.Adam(opt_params, lr=1e-3, capturable=True, **({"foreach": True} if args.no_fused_adam else {"fused": True}))
+
+    def eager(i):
+        batch = batches[i % K].to(dev)          # a fresh device batch: its plan() and csr() are built inside the step
+        opt.zero_grad(set_to_none=False)
+        loss, _ = model(batch)
+        loss.backward()
+        opt.step()
+        return loss
+
+    out = {"model": LABELS[args.model], "graphs_per_batch": args.batch, "varying": K, "steps": args.steps,
+           "simplices": [int(b.x_ind.shape[0]) for b in batches], "adjacencies": [int(b.edge_index.shape[1]) for b in batches],
+           "eager_varying_ms_per_step": round(timed(eager, args.steps), 3)}
+    if hasattr(cx, "capacity_of"):
+        cap = cx.capacity_of(batches, args.slack)
+        gs = GraphedTrainStep(model, opt, batches[0], features, capacity=cap)
+        out["graphed_varying_ms_per_step"] = round(timed(lambda i: gs.step(batch=batches[i % K]), args.steps), 3)
+        out["graphed_fixed_ms_per_step"] = round(timed(lambda i: gs.step(), args.steps), 3)
+        out.update(capacity={"simplices": list(cap.simplices), "adjacencies": cap.edges}, slack=args.slack, status=gs.status(),
+                   fill_rows=round(float(np.mean([b.x_ind.shape[0] for b in batches])) / cap.rows, 4),
+                   fill_adjacencies=round(float(np.mean([b.edge_index.shape[1] for b in batches])) / cap.edges, 4),
+                   loss=float(gs.loss.detach()))
+    print(json.dumps(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--points", type=int, default=8)
+    ap.add_argument("--model", default="hulls", choices=["hulls", "md17", "motion", "nba"])
+    ap.add_argument("--no-fused-adam", action="store_true", help="torch.optim.Adam(foreach) instead of fused=True")
+    ap.add_argument("--no-fused-grads", action="store_true", help="hand parameter gradients to autograd (one add kernel per tensor)")
+    ap.add_argument("--profile-ops", action="store_true", help="torch.profiler over 3 eager steps: the small GPU kernels by Python call site")
+    ap.add_argument("--no-flat-params", action="store_true", help="optimizer over the module's ~1 000 parameter tensors instead of ONE flat buffer (csmpn_hip.graphed.flatten_parameters)")
+    ap.add_argument("--op-sites", action="store_true", help="GPU kernels of one eager step by the package line that launched them")
+    ap.add_argument("--varying", type=int, default=0, metavar="K", help="K batches of different topology: the eager loop on fresh device batches against ONE captured step with a capacity")
+    ap.add_argument("--slack", type=float, default=0.0, help="--varying: capacity_of(batches, slack)")
+    ap.add_argument("--pkg-root", default=None, help="import the package from this tree instead of the tool's own")
+    args = ap.parse_args()
+    if args.pkg_root:
+        sys.path.insert(0, os.path.abspath(args.pkg_root))
+    importlib.import_module(PKG)
+    from csmpn.data import complexes as cx
+    from csmpn.models import simplicial_mpnn as M
+    from csmpn_hip.graphed import GraphedTrainStep
+    from csmpn_hip import ops
+    ops.set_fused_grad_accumulation(not args.no_fused_grads)
+
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(0)
+    if args.varying:
+        return varying(args, rng, cx, M, GraphedTrainStep, dev)
+    batch, features = make_batch(args, rng, cx)
+    batch = batch.to(dev)
     torch.manual_seed(0)
     model = {"hulls": M.HullsSimplicialMPNN, "md17": M.MD17SimplicialMPNN, "motion": M.MotionSimplicialMPNN,
              "nba": M.NBASimplicialMPNN}[args.model]().to(dev)
@@ -205,8 +277,7 @@ def main():
         gs.step()
     torch.cuda.synchronize()
     graph_ms = (time.perf_counter() - t0) * 1e3 / args.steps
-    label = {"hulls": "hulls (Cl(5,0), 28 channels, 3 layers)", "md17": "md17 (Cl(3,0), 32 channels, 5 layers)",
-             "motion": "motion (Cl(3,0), 16 channels, 4 layers)", "nba": "nba (Cl(2,0), 40 channels, 4 layers)"}[args.model]
+    label = LABELS[args.model]
     print(json.dumps({"model": label, "graphs_per_batch": args.batch,
                       "simplices": int(batch.x_ind.shape[0]), "adjacencies": int(batch.edge_index.shape[1]),
                       "fused_grad_accumulation": not args.no_fused_grads, "fused_adam": not args.no_fused_adam, "flat_parameters": not args.no_flat_params, "eager_ms_per_step": round(eager_ms, 3), "graphed_ms_per_step": round(graph_ms, 3),
