@@ -91,9 +91,12 @@ def _run_layer(pkg, C, seed, N=2000, E=20000, metric=(1.0, 1.0, 1.0)):
 
 
 @pytest.mark.parametrize("C,metric,N,E", [(8, (1.0, 1.0, 1.0), 2000, 20000), (16, (1.0, 1.0, 1.0), 2000, 20000),
-                                          # the wide parity-lane kernels: the convex-hulls width, and Cl(4,1)
+                                          # the convex-hulls width: the 16-row-tile kernels (cemlp_pg.hpp) both ways, on the
+                                          # state their forward saved; Cl(4,1) at 16 channels: the wide parity-lane kernels
+                                          # (cemlp_plw.hpp) - the dispatch log of tests/test_lane_d32_gpu.py, group det
                                           (28, (1.0,) * 5, 400, 4000), (16, (1.0, 1.0, 1.0, 1.0, -1.0), 300, 3000),
-                                          # 8 channels of D = 32: routed to the one-group wide kernels in this mode
+                                          # 8 channels of D = 32: the parity-lane kernels (cemlp_pl.hpp) in this mode too; the
+                                          # one-group wide kernels take them only under CSMPN_PLW8=1
                                           (8, (1.0, 1.0, 1.0, 1.0, -1.0), 500, 5000),
                                           # round 3: the general row-tile kernels in their deterministic form (one row tile per
                                           # workgroup, mirror slices + fixed-order reduction): the md17 width (Cl(3,0), 32 channels),
