@@ -46,9 +46,9 @@ struct SliceSet {
 // What one instantiation unit (family x algebra) exports. Both size queries return 0 for a shape the unit does not serve.
 struct LaneUnit {
     size_t (*table_floats)(const LaneShape&);   // weight tables the launch packs into the workspace (0: the family has none)
-    // one gradient slice of a backward (per workgroup; pl: per wave), all blocks that coexist. dispatch.hip sizes the cl, cm and
-    // pq regions by it; the pl, plw and pg regions are sized by the bounds below, which those units assert against their
-    // slices: there it marks the shape as served and states the exact figure, nothing reads it for sizing
+    // one gradient slice of a backward (per workgroup; pl: per wave), all blocks that coexist. The cl, cm and pq entries of
+    // dispatch.hip size their regions by it; the pl, plw and pg entries take the bounds below, which those units assert against
+    // their slices: there it marks the shape as served and states the exact figure, nothing reads it for sizing
     size_t (*slice_floats)(const LaneShape&);
     // pack: write the weight tables first (pg, pq; plw always does). *handled = false: shape not served, nothing launched.
     hipError_t (*launch)(const LaneShape&, bool bwd, bool pack, unsigned grid, hipStream_t st, const DevCemlp& C, const RowIO& io,
@@ -105,12 +105,13 @@ constexpr unsigned kPqGridCap = 768;
 CSMPN_DECLARE_LANE_UNIT(pq, n3)
 
 // ----------------------------------------------------------------------------- the D = 32 families' region at the end of the workspace
-// Upper bounds by channel count, not the kernels' exact sizes: pl_inst.inc, plw_inst.inc and pg_inst.inc assert for every
-// shape they serve that its backward and reduce kernels stay inside them at the grid cap.
+// Upper bounds by channel count, not the kernels' exact sizes. Each has two kinds of reader: the family's entry in dispatch.hip
+// (its tail need and reservation) and the family's unit (pl_inst.inc, plw_inst.inc, pg_inst.inc), which asserts for every
+// shape it serves that its tables and its backward and reduce kernels at the grid cap stay inside.
 // the 8-channel parity-lane backward (cemlp_pl.hpp): one slice per wave, 4 waves x kPlMaxBwdGroups workgroups
 constexpr size_t pl_part_bytes() { return (size_t)(8 * 768 + 2 * 640) * sizeof(float) * 4 * kPlMaxBwdGroups + 256; }
-// gradient slices of the wide parity-lane backward (one slice of weight-gradient MFMA tiles per workgroup), of the pg backward
-// (positioned and sized by the same bound) and, at 8 channels, of the parity-lane backward
+// gradient slices of the wide parity-lane backward (one slice of weight-gradient MFMA tiles per workgroup); at 8 channels no
+// less than the parity-lane backward's, whose shapes the wide family's reservation covers
 constexpr size_t plw_part_bytes(int ch) {
     const size_t NG = (ch + 7) / 8, nch0 = 2 * NG + 1;
     const size_t image = 8 * NG * (3 + 3 * 6 + 64) + 16;   // per-channel sums (CP x (3 + 3 G + P)), generous
@@ -123,7 +124,11 @@ constexpr size_t plw_tables_bytes(int ch) {
     const size_t NG = (ch + 7) / 8, nch0 = 2 * NG + 1;
     return ((2 * NG * nch0 + 4 * NG * NG) + (2 * NG * NG + 4 * NG * NG)) * 384 * sizeof(float);
 }
-// ... from 17 channels on 64 KB more: the weight-fragment tables of cemlp_pg.hpp, carved from the same region, are up to
-// 368 KB at 28 / 32 channels
-constexpr size_t kPgTablesExtraBytes = 65536;
+// The 16-row-tile family (cemlp_pg.hpp) carves the same region: its gradient slices by the wide kernels' bound, its
+// weight-fragment tables (up to 368 KB at 28 / 32 channels) by the wide kernels' tables and 64 KB more.
+constexpr size_t pg_part_bytes(int ch) { return plw_part_bytes(ch); }
+constexpr size_t pg_tables_bytes(int ch) { return plw_tables_bytes(ch) + 65536; }
+// ... which the 24-channel tables (312 KB edge, 360 KB node) exceed by up to this much: DESIGN.md section 6, gap 9. Zero
+// once pg_tables_bytes is raised, which changes csmpn_cemlp_workspace_bytes.
+constexpr size_t pg_tables_overshoot(int ch) { return ch == 24 ? 100352 : 0; }
 }  // namespace csmpn

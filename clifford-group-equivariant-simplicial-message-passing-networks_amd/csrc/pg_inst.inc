@@ -18,14 +18,13 @@ hipError_t pg_launch_bwd(unsigned grid, hipStream_t st, const DevCemlp& Cd, cons
 
 template <class CF>
 hipError_t pg_launch(bool bwd, bool pack, unsigned grid, hipStream_t st, const DevCemlp& Cd, const RowIO& io_in, float* tabs) {
-    static_assert((size_t)CF::slice_max * kPgMaxGroups * sizeof(float) <= plw_part_bytes(CF::C),
+    static_assert((size_t)CF::slice_max * kPgMaxGroups * sizeof(float) <= pg_part_bytes(CF::C),
                   "one slice per workgroup at the grid cap: inside the region the host reserves in front of the tables");
-    // At 24 channels the tables, 312 KB edge / 360 KB node, exceed the 262 KB the tail reserves for them by up to 100352 B and
-    // reach into the general kernels' front part of the workspace, which pg_eligible's fits() counts in (DESIGN.md section 6):
-    // a known gap, held at today's overshoot so that it cannot widen unnoticed.
-    constexpr size_t known_overshoot = CF::C == 24 ? 100352 : 0;
-    static_assert(CF::tab_floats * sizeof(float) <= plw_tables_bytes(CF::C) + kPgTablesExtraBytes + known_overshoot,
-                  "weight-fragment tables: inside the region the host reserves");
+    // pg_tables_overshoot (launch.hpp) is nonzero at 24 channels only: there the tables reach into the general kernels' front
+    // part of the workspace, which the family's admission counts in (DESIGN.md section 6, gap 9). Held at today's figure so
+    // that the gap cannot widen unnoticed.
+    static_assert(CF::tab_floats * sizeof(float) <= pg_tables_bytes(CF::C) + pg_tables_overshoot(CF::C),
+                  "weight-fragment tables: inside the region the host reserves, but for the known overshoot");
     RowIO io = io_in;
     io.tabs = tabs;
     hipError_t e = hipSuccess;

@@ -97,12 +97,20 @@ int run_pack(const Plan& plan, hipStream_t st);
 // entry points and both directions (no metric: upper bound)
 size_t plan_front_bytes(int n, const csmpn_block_params* blocks, int nblk);
 
-// A region carved from the END of the workspace: `bytes` long, start rounded down to `align` (a power of two). The sizing
-// side (csmpn_cemlp_workspace_bytes) reserves bytes + kTailSlack behind the front part for whichever region a launch takes.
-constexpr size_t kTailSlack = 16 + 256;
+// A region carved from the END of the workspace: `bytes` long, start rounded down to `align` (a power of two).
 inline char* tail_region(const Plan& plan, size_t bytes, size_t align) {
     return static_cast<char*>(plan.workspace) + ((plan.workspace_bytes - bytes) & ~(align - 1));
 }
+// A lane family's tables and slices (TailNeed of dispatch.hip) end kTailPad bytes, one float4 of margin, before the end of
+// the workspace and start on a multiple of kTailAlign, the tables' alignment for the kernels' vector loads: with the start
+// rounded down, the region reaches less than kTailSlack further from the end than its own bytes. The sizing side
+// (csmpn_cemlp_workspace_bytes) reserves bytes + kTailSlack behind the front part for whichever region a launch takes.
+constexpr size_t kTailPad = 16, kTailAlign = 256;
+constexpr size_t kTailSlack = kTailPad + kTailAlign;
+// What a launch asks of the workspace beyond its tables and slices before it carves them: kTailSlack rounded up to 1 KB.
+constexpr size_t kAdmitSlack = 1024;
+// What a reservation stated by launch.hpp's channel-count bounds adds to them: one more alignment step.
+constexpr size_t kBoundSlack = kTailAlign;
 
 // The ten parameter-gradient tensors of block B in reference order: f(pointer slot, floats, present). G grades, P paths.
 template <class Block, class F>

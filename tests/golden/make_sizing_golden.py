@@ -6,7 +6,8 @@ every environment is measured in a child process of its own.
     python tests/golden/make_sizing_golden.py            # rewrites tests/golden/sizing_contract.npz
 
 tests/test_sizing_contract.py compares the built library with the stored figures, entry by entry. The fixture in the
-tree was recorded from the library of commit f7329ee (the parent of the change that split csrc/capi.hip).
+tree was recorded from the library of commit f7329ee (the parent of the change that split csrc/capi.hip), its "no_cm" table
+from the library of commit 5645b40 (the parent of the change that gave every kernel family one statement of its regions).
 """
 import os
 import subprocess
@@ -25,6 +26,7 @@ PLAIN_EXTRA_INPUTS = (40, 60, 90)      # standalone CEMLPs of the task models, a
 ENVS = {
     "default": {},
     "no_cm_bwd": {"CSMPN_NO_CM_BWD": "1"},
+    "no_cm": {"CSMPN_NO_CM": "1"},
     "no_pq": {"CSMPN_NO_PQ": "1"},
     "phased_min_rows_1000": {"CSMPN_PHASED_MIN_ROWS": "1000"},
 }
