@@ -224,7 +224,6 @@ class SimplicialBatch:
         called. Nothing is validated here: pad_batch has checked the indices on the host; a batch whose row counts per
         dimension differ from this one's sets bits in plan()["status"] (ops.simplex_tables) instead of writing out of
         bounds."""
-        from csmpn_hip import ops
         plan = getattr(self, "_plan", None)
         if plan is None or self._csr is None:
             raise RuntimeError("refresh_: call plan() and csr() on the batch first")
@@ -239,6 +238,12 @@ class SimplicialBatch:
         for k in ("n_real_rows", "n_real_edges"):
             if hasattr(raw, k):
                 setattr(self, k, getattr(raw, k))
+        return self._rebuild_in_place()
+
+    def _rebuild_in_place(self) -> "SimplicialBatch":
+        """Everything derived from the structure tensors, rebuilt in place on the current stream (refresh_, relift_)."""
+        from csmpn_hip import ops
+        plan = self._plan
         dev = self.x_ind.device
         if "tables_ws" not in plan:
             plan["tables_ws"] = ops.simplex_tables_workspace(self.node_types.shape[0], plan["max_dim"], dev)
@@ -250,6 +255,51 @@ class SimplicialBatch:
         for key, build in plan.get("builders", {}).items():
             if key not in ("verts_i32", "types_i32"):      # those two are outputs of csmpn_simplex_tables
                 build(plan[key])
+        return self
+
+    def relift_(self, points: torch.Tensor, dis: float, vertex_features: Optional[Dict[str, torch.Tensor]] = None) -> "SimplicialBatch":
+        """Make this DEVICE batch hold the Vietoris-Rips complexes of `points` (device float32 [B * V, n], the V vertices of
+        graph g contiguous; B and V are this batch's) at threshold `dis`, at the capacity the batch was built with: the
+        structure tensors are written by ops.rips_lift (csmpn_rips_lift) as pad_batch(collate([rips_complex(...)]), capacity)
+        would lay them out, then everything derived from them is rebuilt in place as in refresh_. vertex_features
+        {name: per-vertex tensor [B * V, ...]}: the per-simplex tensor `name` is zeroed and gets these rows at the vertex
+        rows of the new batch. plan() and csr() must have been called. After the first call: no allocation, no host
+        synchronisation. A complex that does not fit the capacity leaves the batch as it was (the features excepted, which
+        land on the old vertex rows) and sets bits in plan()["lift_status"] (ops.rips_lift). The host-side n_real_rows /
+        n_real_edges are dropped: the real counts live on the device, in plan()["lift_counts"] (rows per dimension,
+        adjacencies)."""
+        from csmpn_hip import ops
+        plan = getattr(self, "_plan", None)
+        if plan is None or self._csr is None:
+            raise RuntimeError("relift_: call plan() and csr() on the batch first")
+        dev = self.x_ind.device
+        if dev.type != "cuda" or points.device != dev:
+            raise RuntimeError("relift_: the batch and the points must live on one GPU (no CPU fallback)")
+        max_dim, B = plan["max_dim"], self.num_graphs
+        rows = [int(r.shape[0]) for r in plan["rows"]]
+        if points.dim() != 2 or int(points.shape[0]) != rows[0]:
+            raise ValueError(f"relift_: points must be [{rows[0]}, n] (one row per vertex of the batch), got {tuple(points.shape)}")
+        for name, value in (vertex_features or {}).items():
+            t = getattr(self, name, None)
+            if name not in self._names or name in _STRUCTURE or int(t.shape[0]) != int(self.node_types.shape[0]):
+                raise ValueError(f"relift_: {name!r} is not a per-simplex feature tensor of the batch")
+            if tuple(value.shape) != (rows[0],) + tuple(t.shape[1:]):
+                raise ValueError(f"relift_: vertex feature {name!r} has shape {tuple(value.shape)}, expected {(rows[0],) + tuple(t.shape[1:])}")
+        if "lift_ws" not in plan:
+            plan["lift_ws"] = ops.rips_lift_workspace(B, rows[0] // B, max_dim, dev)
+            plan["lift_status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+            plan["lift_counts"] = torch.zeros(max_dim + 2, dtype=torch.int64, device=dev)
+        ops.rips_lift(points, B, dis, max_dim, rows, int(self.edge_index.shape[1]), self.x_ind, self.node_types, self.batch,
+                      self.x_ind_batch, self.ptr, self.x_ind_ptr, self.edge_index, getattr(self, "edge_types", None),
+                      plan["lift_counts"], plan["lift_status"], plan["lift_ws"])
+        for k in ("n_real_rows", "n_real_edges"):
+            if hasattr(self, k):
+                delattr(self, k)
+        self._rebuild_in_place()
+        for name, value in (vertex_features or {}).items():
+            t = getattr(self, name)
+            t.zero_()
+            t.index_copy_(0, plan["vertex_rows"], value.to(t.dtype))
         return self
 
     def csr(self):
@@ -451,3 +501,72 @@ def pad_batch(batch: "SimplicialBatch", capacity: BatchCapacity, simplex_feature
     padded = SimplicialBatch(**{k: out[k] for k in batch._names})
     padded.n_real_rows, padded.n_real_edges = S, E
     return padded
+
+
+# ------------------------------------------------------------------------------- Rips complexes built on the device
+#
+# A complex that depends on the current positions (a loader that does not pre-lift, jittered positions, a rollout that
+# re-lifts from predicted positions) is lifted on the device at a fixed capacity (csmpn_rips_lift, csrc/lift.hip): the
+# structure tensors come out exactly as pad_batch(collate([rips_complex(...)])) lays them out, and relift_ rebuilds the
+# rest in place in front of a replayed step.
+
+
+def rips_adjacencies(n_graphs: int, verts_per_graph: int, n_edges: int, n_triangles: int) -> int:
+    """Adjacencies of a batch of Rips complexes with n_edges 1-simplices and n_triangles 2-simplices in all: per graph the
+    V (V - 1) + n1 entries of the 0_0 block (2 n1 through a shared edge + the V (V - 1) - n1 ordered non-edges), 2 n1 each
+    of 0_1 and 1_0, 6 n2 of 1_1 and 3 n2 each of 1_2 and 2_1 (lift())."""
+    return int(n_graphs) * int(verts_per_graph) * (int(verts_per_graph) - 1) + 5 * int(n_edges) + 12 * int(n_triangles)
+
+
+def rips_capacity(n_graphs: int, verts_per_graph: int, max_edges: int, max_triangles: int, max_dim: int = 2) -> BatchCapacity:
+    """The capacity that serves every batch of n_graphs Rips complexes on verts_per_graph vertices each with at most
+    max_edges 1-simplices and max_triangles 2-simplices in all - with one spare 1-simplex, the filler row that carries the
+    filler adjacencies of every smaller batch."""
+    if max_dim not in (1, 2):
+        raise ValueError("rips_capacity: max_dim must be 1 or 2")
+    if n_graphs < 1 or verts_per_graph < max_dim + 1 or max_edges < 0 or max_triangles < 0:
+        raise ValueError("rips_capacity: need n_graphs >= 1, verts_per_graph >= max_dim + 1 and counts >= 0")
+    if max_dim == 1:
+        max_triangles = 0
+    rows = (n_graphs * verts_per_graph, max_edges + 1) + ((max_triangles,) if max_dim == 2 else ())
+    return BatchCapacity(rows, rips_adjacencies(n_graphs, verts_per_graph, max_edges, max_triangles))
+
+
+def rips_batch_device(points: torch.Tensor, n_graphs: int, dis: float, capacity: BatchCapacity,
+                      features: Optional[Dict[str, torch.Tensor]] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
+                      x_ind_cols: Optional[int] = None) -> SimplicialBatch:
+    """The device batch of the Rips complexes of `points` (device float32 [n_graphs * V, n]) at `capacity`, lifted on the
+    device - the batch relift_ is then called on. features {name: tensor}: further tensors of the batch as they are
+    (per-graph labels, per-vertex targets); vertex_features {name: per-vertex tensor [n_graphs * V, ...]}: per-simplex
+    tensors [capacity.rows, ...] that hold these rows at the vertex rows and zeros elsewhere. Synchronises once;
+    ValueError if the complex does not fit the capacity."""
+    from csmpn_hip import ops
+    if not points.is_cuda:
+        raise RuntimeError("rips_batch_device needs device points (no CPU fallback)")
+    dev, max_dim, S, E, B = points.device, capacity.max_dim, capacity.rows, capacity.edges, int(n_graphs)
+    i64 = lambda *shape: torch.zeros(*shape, dtype=torch.int64, device=dev)
+    tensors = dict(x_ind=i64(S, max_dim + 1 if x_ind_cols is None else int(x_ind_cols)), node_types=i64(S), edge_index=i64(2, E),
+                   edge_types=i64(E, 2), batch=i64(S), ptr=i64(B + 1), x_ind_batch=i64(S), x_ind_ptr=i64(B + 1))
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    counts = i64(max_dim + 2)
+    ws = ops.rips_lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev)
+    ops.rips_lift(points, B, dis, max_dim, capacity.simplices, E, tensors["x_ind"], tensors["node_types"], tensors["batch"],
+                  tensors["x_ind_batch"], tensors["ptr"], tensors["x_ind_ptr"], tensors["edge_index"], tensors["edge_types"], counts,
+                  status, ws)
+    word = int(status.item())
+    if word:
+        raise ValueError(f"rips_batch_device: the complex does not fit the capacity {capacity} (status {word:#x}: bit 1 / 2 = too "
+                         "many 1- / 2-simplices, bit 3 = too many adjacencies, bit 4 = filler adjacencies without a filler row)")
+    vertex_rows = torch.nonzero(tensors["node_types"] == 0, as_tuple=False).flatten()
+    for name, value in (vertex_features or {}).items():
+        t = torch.zeros((S,) + tuple(value.shape[1:]), dtype=value.dtype, device=dev)
+        t.index_copy_(0, vertex_rows, value.to(dev))
+        tensors[name] = t
+    for name, value in (features or {}).items():
+        tensors[name] = value.to(dev)
+    out = SimplicialBatch(**tensors)
+    out.plan(max_dim)
+    out.csr()
+    plan = out._plan
+    plan["lift_ws"], plan["lift_status"], plan["lift_counts"] = ws, status, counts
+    return out

@@ -15,6 +15,8 @@ step is built with a `capacity` (csmpn.data.complexes.BatchCapacity): every batc
 host (pad_batch: filler simplices and self-loop adjacencies that no real row hears of), copied into the captured buffers,
 and the tables derived from the topology - the target-sorted CSR, the index tables of the embedding and of the readout -
 are rebuilt in place on the device (SimplicialBatch.refresh_: csmpn_simplex_tables, csmpn_csr_build) in front of the replay.
+Where the complex is the Vietoris-Rips complex of the current positions, step(points=...) builds it on the device as well
+(SimplicialBatch.relift_: csmpn_rips_lift writes the structure tensors at the capacity), so a step takes no host lift at all.
 
 The kernels launched inside are the same C-ABI calls as in eager mode (they take the current stream); the
 CSR and the embedding index tables are built before capture (their only host round trips).
@@ -24,6 +26,9 @@ from __future__ import annotations
 from typing import Dict, Iterable, Optional
 
 import torch
+
+
+LIFT_STATUS_SHIFT = 8     # status(): the word of the device lift sits above the bits of the table rebuild
 
 
 def flatten_parameters(module: torch.nn.Module) -> torch.nn.Parameter:
@@ -96,12 +101,19 @@ class GraphedTrainStep:
     refreshes the captured batch in place and replays. The refresh runs eagerly on the current stream in front of the
     replay; it is not part of the captured graph. status(): the device status word of the table rebuild (0 = every batch
     so far had the row counts of the capacity; one small copy with a synchronisation - read it where the loop syncs
-    anyway)."""
+    anyway).
+
+    step(points=device points [B * V, n], vertex_features={name: per-vertex tensor}) lifts the Vietoris-Rips complexes of the
+    points at threshold `rips_dis` (or dis=...) ON THE DEVICE into the captured batch (SimplicialBatch.relift_:
+    csmpn_rips_lift + the same in-place rebuild), eagerly in front of the replay like the refresh; the per-simplex tensors
+    named in vertex_features get the given rows at the new vertex rows and zeros elsewhere. Nothing is checked on the host:
+    a complex over the capacity leaves the previous structure in place and sets bits in status()."""
 
     def __init__(self, model, optimizer, batch, feature_names: Iterable[str], warmup: int = 2, max_dim: Optional[int] = None,
-                 capacity=None, simplex_features: Optional[Iterable[str]] = None, device=None):
+                 capacity=None, simplex_features: Optional[Iterable[str]] = None, device=None, rips_dis: Optional[float] = None):
         self.capacity = capacity
         self.simplex_features = None
+        self.rips_dis = rips_dis
         if capacity is not None:
             from csmpn.data.complexes import pad_batch
             if device is None:
@@ -182,14 +194,32 @@ class GraphedTrainStep:
         from csmpn.data.complexes import pad_batch
         self.batch.refresh_(pad_batch(batch, self.capacity, self.simplex_features))
 
-    def status(self) -> int:
-        """The status word of the table rebuilds so far (ops.simplex_tables; 0 = fine). Synchronises."""
-        word = self.batch._plan.get("status")
-        return 0 if word is None else int(word.item())
+    def load_points(self, points: torch.Tensor, dis: Optional[float] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None):
+        """Make the captured batch hold the Vietoris-Rips complexes of the device points [B * V, n] at threshold `dis`
+        (default: the step's `rips_dis`), lifted on the device (SimplicialBatch.relift_): no host work per batch. A complex
+        over the capacity leaves the structure of the captured batch as it was and shows in status()."""
+        if self.capacity is None:
+            raise RuntimeError("GraphedTrainStep was built without a capacity: it replays ONE topology (load(features))")
+        dis = self.rips_dis if dis is None else dis
+        if dis is None:
+            raise ValueError("step(points=...): pass dis=... or set the step's rips_dis")
+        self.batch.relift_(points, dis, vertex_features)
 
-    def step(self, features: Optional[Dict[str, torch.Tensor]] = None, batch=None) -> torch.Tensor:
+    def status(self) -> int:
+        """The status words of the table rebuilds (ops.simplex_tables) and of the device lifts (ops.rips_lift: its bits
+        1..4 are reported as bits 9..12) so far; 0 = fine. Synchronises."""
+        plan = self.batch._plan
+        word, lift = plan.get("status"), plan.get("lift_status")
+        return (0 if word is None else int(word.item())) | (0 if lift is None else int(lift.item()) << LIFT_STATUS_SHIFT)
+
+    def step(self, features: Optional[Dict[str, torch.Tensor]] = None, batch=None, points: Optional[torch.Tensor] = None,
+             vertex_features: Optional[Dict[str, torch.Tensor]] = None, dis: Optional[float] = None) -> torch.Tensor:
+        if batch is not None and points is not None:
+            raise ValueError("step: pass batch=... (lifted on the host) or points=... (lifted on the device), not both")
         if batch is not None:
             self.load_batch(batch)
+        if points is not None:
+            self.load_points(points, dis, vertex_features)
         if features:
             self.load(features)
         self.graph.replay()

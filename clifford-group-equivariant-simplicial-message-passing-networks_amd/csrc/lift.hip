@@ -1,0 +1,392 @@
+// Vietoris-Rips lift of a batch on the device at a fixed capacity (C-ABI: csmpn_rips_lift, include/csmpn_hip.h): the
+// structure tensors that the host builds with rips_complex -> lift -> to_complex -> collate -> pad_batch
+// (csmpn/data/complexes.py) - x_ind, node_types, batch / x_ind_batch, ptr / x_ind_ptr, edge_index, edge_types, the fillers
+// behind the real part included - from the vertex positions, without an allocation, a host round trip or an atomic on an
+// output: every position of every entry is computed, never claimed.
+//
+// A graph has at most 64 vertices, so ONE 64-bit neighbour mask per vertex (a wave ballot over the other vertices) carries
+// it, and every index is a popcount of masks plus a scan: with upper[a] = mask[a] restricted to b > a,
+//   index of the edge (a, b), a < b      = sum_{a' < a} popc(upper[a']) + popc(upper[a] & below(b))
+//   triangles in front of the edge (a,b) = the scan over the edges of popc(upper[a] & upper[b])   (triangles (a, b, c), c ascending)
+//   cofaces in front of the edge (a, b)  = the scan over the edges of popc(mask[a] & mask[b])     (the 1_1 block)
+// Both scans are kept per vertex a (64 entries in LDS); the part inside a's row of edges is a wave scan over the lanes b.
+//
+//   count    one workgroup per graph: the masks -> workspace, the graph's numbers of 1- and 2-simplices
+//   offsets  ONE workgroup: the totals against the capacity -> fit flag, status word; where the batch fits, the scan of the
+//            graphs' row and adjacency counts (256 graphs per pass) -> ptr / x_ind_ptr, counts, the offsets of every graph
+//   scatter  one workgroup per graph + workgroups for the fillers; all of them return at once when the fit flag is clear,
+//            so a batch that does not fit leaves every output as it was
+//
+// Order of a graph's real part (= lift + to_complex): rows = the V vertices, the close pairs (a < b) and the triples
+// (a < b < c) with all pairs close, both lexicographic; adjacencies = seven blocks, see scatter_graph below.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "../../include/csmpn_hip.h"
+#include "capi_common.hpp"
+
+namespace {
+
+using u64 = unsigned long long;
+
+constexpr int kBlock = 256;      // 4 waves of 64
+constexpr int kWaves = kBlock / 64;
+constexpr int kMaxVerts = 64;    // one mask bit per vertex
+constexpr int kMaxFillBlocks = 1024;
+
+struct Capacity {
+    long long rows[3];           // rows per dimension (rows[2] = 0 for max_dim = 1)
+    long long edges;
+};
+
+struct Header {                  // first 256 bytes of the workspace, written by the offsets kernel
+    int fit;                     // 1: the batch fits its capacity, the scatter kernel writes
+    long long n[3];              // real rows per dimension
+    long long adj;               // real adjacencies
+};
+
+struct Outputs {
+    int64_t* x_ind;
+    int64_t* node_types;
+    int64_t* batch;
+    int64_t* x_ind_batch;
+    int64_t* edge_index;         // [2, cap_edges]
+    int64_t* edge_types;         // [cap_edges, 2] or nullptr
+    int cols;                    // columns of x_ind
+    long long cap_edges;
+};
+
+__device__ __forceinline__ u64 below(int b) { return (1ull << b) - 1ull; }                       // bits < b, b in 0..63
+__device__ __forceinline__ u64 above(int a) { return a >= 63 ? 0ull : ~0ull << (a + 1); }         // bits > a
+__device__ __forceinline__ int first_bit(u64 m) { return __ffsll((long long)m) - 1; }
+
+// exclusive prefix sum of v over the 64 lanes of a wave (every lane calls it)
+__device__ __forceinline__ int wave_scan(int v, int lane, int* total) {
+    int x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    if (total) *total = __shfl(x, 63, 64);
+    return x - v;
+}
+
+__device__ __forceinline__ void put_row(const Outputs& o, long long row, int type, long long graph, int v0, int v1, int v2) {
+    for (int j = 0; j < o.cols; ++j) o.x_ind[row * o.cols + j] = j == 0 ? v0 : j == 1 ? v1 : j == 2 ? v2 : 0;
+    o.node_types[row] = type;
+    o.batch[row] = graph;
+    o.x_ind_batch[row] = graph;
+}
+
+__device__ __forceinline__ void put_adj(const Outputs& o, long long pos, long long src, long long dst, int ts, int tt) {
+    o.edge_index[pos] = src;
+    o.edge_index[o.cap_edges + pos] = dst;
+    if (o.edge_types) {
+        o.edge_types[2 * pos] = ts;
+        o.edge_types[2 * pos + 1] = tt;
+    }
+}
+
+// one workgroup per graph: mask[a] bit b = (a != b and |p_a - p_b|^2 <= dis^2, summed in double over k ascending)
+__global__ __launch_bounds__(kBlock) void lift_count_kernel(const float* points, int P, int V, double dis2, int max_dim,
+                                                             u64* masks, int* n1, int* n2) {
+    __shared__ u64 m[kMaxVerts];
+    const long g = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* pg = points + g * V * (long)P;
+    for (int a = wave; a < V; a += kWaves) {
+        bool close = false;
+        if (lane < V && lane != a) {
+            double s = 0.0;
+            for (int k = 0; k < P; ++k) {
+                const double d = (double)pg[a * P + k] - (double)pg[lane * P + k];
+                s = __dadd_rn(s, __dmul_rn(d, d));            // no contraction: the sum the host takes
+            }
+            close = s <= dis2;                                // false for a NaN
+        }
+        const u64 mk = __ballot(close);
+        if (lane == 0) m[a] = mk;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    int c1 = 0, c2 = 0;
+    if (lane < V) {
+        const u64 ma = m[lane], up = ma & above(lane);
+        masks[g * V + lane] = ma;
+        c1 = __popcll(up);
+        if (max_dim >= 2)
+            for (u64 r = up; r; r &= r - 1) {
+                const int b = first_bit(r);
+                c2 += __popcll(up & m[b] & above(b));
+            }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        c1 += __shfl_down(c1, d, 64);
+        c2 += __shfl_down(c2, d, 64);
+    }
+    if (lane == 0) {
+        n1[g] = c1;
+        n2[g] = c2;
+    }
+}
+
+// one workgroup: totals against the capacity; if the batch fits, the offsets of every graph and ptr / x_ind_ptr / counts
+__global__ __launch_bounds__(kBlock) void lift_offsets_kernel(const int* n1, const int* n2, long B, int V, int max_dim, Capacity cap,
+                                                               Header* hdr, long long* row_off, long long* adj_off, int64_t* ptr,
+                                                               int64_t* x_ind_ptr, int64_t* counts, unsigned* status) {
+    using Scan = hipcub::BlockScan<long long, kBlock>;
+    __shared__ typename Scan::TempStorage temp;
+    const long long VV = (long long)V * (V - 1);
+    long long N1 = 0, N2 = 0;
+    for (long base = 0; base < B; base += kBlock) {
+        const long g = base + threadIdx.x;
+        long long excl, sum;
+        Scan(temp).ExclusiveSum(g < B ? (long long)n1[g] : 0ll, excl, sum);
+        __syncthreads();
+        N1 += sum;
+        Scan(temp).ExclusiveSum(g < B ? (long long)n2[g] : 0ll, excl, sum);
+        __syncthreads();
+        N2 += sum;
+    }
+    const long long E = B * VV + 5 * N1 + 12 * N2;
+    unsigned bad = 0;
+    if (N1 > cap.rows[1]) bad |= 1u << 1;
+    if (max_dim >= 2 && N2 > cap.rows[2]) bad |= 1u << 2;
+    if (E > cap.edges) bad |= 1u << 3;
+    if (!bad && E < cap.edges && cap.rows[1] - N1 + (max_dim >= 2 ? cap.rows[2] - N2 : 0) == 0) bad |= 1u << 4;
+    if (bad) {                                               // uniform: every thread holds the same totals
+        if (threadIdx.x == 0) {
+            hdr->fit = 0;
+            if (status) atomicOr(status, bad);
+        }
+        return;
+    }
+    long long rows = 0, adjs = 0;
+    for (long base = 0; base < B; base += kBlock) {
+        const long g = base + threadIdx.x;
+        const long long a1 = g < B ? n1[g] : 0, a2 = g < B ? n2[g] : 0;
+        long long excl, sum;
+        Scan(temp).ExclusiveSum(g < B ? V + a1 + a2 : 0ll, excl, sum);
+        __syncthreads();
+        if (g < B) {
+            row_off[g] = rows + excl;
+            ptr[g] = rows + excl;
+            x_ind_ptr[g] = rows + excl;
+        }
+        rows += sum;
+        Scan(temp).ExclusiveSum(g < B ? VV + 5 * a1 + 12 * a2 : 0ll, excl, sum);
+        __syncthreads();
+        if (g < B) adj_off[g] = adjs + excl;
+        adjs += sum;
+    }
+    if (threadIdx.x == 0) {
+        ptr[B] = rows;
+        x_ind_ptr[B] = rows;
+        hdr->n[0] = B * V;
+        hdr->n[1] = N1;
+        hdr->n[2] = N2;
+        hdr->adj = E;
+        hdr->fit = 1;
+        if (counts) {
+            counts[0] = B * V;
+            counts[1] = N1;
+            if (max_dim >= 2) counts[2] = N2;
+            counts[max_dim + 1] = E;
+        }
+    }
+}
+
+// The real part of graph g. Adjacency blocks, each at its closed-form offset behind adj_off[g] (rows offset by row_off[g]):
+//   1  0_0  for s, for the neighbours u of s ascending: (u, s)                                              2 n1
+//   2  0_0  for i, for j: (i, j) for every ordered pair i != j except the pairs i < j that are an edge      V (V - 1) - n1
+//   3  0_1  for every edge e = (a, b): (a, e), (b, e)                                                       2 n1
+//   4  1_0  the flips of block 3                                                                            2 n1
+//   5  1_1  for every edge s = (a, b), for the common neighbours w ascending: ({a, w}, s), ({b, w}, s)       6 n2
+//   6  1_2  for every triangle t = (a, b, c): ((a, b), t), ((a, c), t), ((b, c), t)                         3 n2
+//   7  2_1  the flips of block 6                                                                            3 n2
+// A wave takes the vertices a = wave, wave + 4, ...; its lane b holds the pair (a, b).
+__device__ void scatter_graph(long g, int V, int max_dim, const u64* masks, const int* n1s, const int* n2s,
+                              const long long* row_off, const long long* adj_off, const Outputs& o) {
+    __shared__ u64 m[kMaxVerts];
+    __shared__ int deg_s[kMaxVerts], up_s[kMaxVerts], tri_s[kMaxVerts], cof_s[kMaxVerts];   // sums over the vertices in front
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < kMaxVerts) m[tid] = tid < V ? masks[g * V + tid] : 0ull;
+    __syncthreads();
+    if (wave == 0) {
+        const u64 ma = m[lane], up = ma & above(lane);
+        int t = 0, c = 0;
+        if (max_dim >= 2)
+            for (u64 r = up; r; r &= r - 1) {
+                const int b = first_bit(r);
+                const u64 mb = m[b];
+                t += __popcll(up & mb & above(b));
+                c += __popcll(ma & mb);
+            }
+        deg_s[lane] = wave_scan(__popcll(ma), lane, nullptr);
+        up_s[lane] = wave_scan(__popcll(up), lane, nullptr);
+        tri_s[lane] = wave_scan(t, lane, nullptr);
+        cof_s[lane] = wave_scan(c, lane, nullptr);
+    }
+    __syncthreads();
+    const long long n1 = n1s[g], n2 = n2s[g], row0 = row_off[g], adj0 = adj_off[g];
+    const long long VV = (long long)V * (V - 1);
+    const long long o1 = adj0, o2 = o1 + 2 * n1, o3 = adj0 + VV + n1, o4 = o3 + 2 * n1, o5 = o4 + 2 * n1, o6 = o5 + 6 * n2,
+                    o7 = o6 + 3 * n2;
+    const long long e0 = row0 + V, t0 = e0 + n1;              // first edge row, first triangle row
+    if (tid < V) put_row(o, row0 + tid, 0, g, tid, 0, 0);
+    for (int a = wave; a < V; a += kWaves) {
+        const u64 ma = m[a], up = ma & above(a), mb = m[lane];
+        if ((ma >> lane) & 1ull) put_adj(o, o1 + deg_s[a] + __popcll(ma & below(lane)), row0 + lane, row0 + a, 0, 0);
+        if (lane < V && lane != a && !(lane > a && ((ma >> lane) & 1ull)))
+            put_adj(o, o2 + (long long)a * (V - 1) - up_s[a] + lane - (lane > a ? 1 : 0) - __popcll(up & below(lane)), row0 + a,
+                    row0 + lane, 0, 0);
+        const bool edge = (up >> lane) & 1ull;                // the pair (a, lane), a < lane, is an edge
+        const u64 tri = edge && max_dim >= 2 ? up & mb & above(lane) : 0ull;     // its triangles (a, lane, c)
+        const u64 cof = edge && max_dim >= 2 ? ma & mb : 0ull;                   // its cofaces {a, lane, w}
+        const long long tb = tri_s[a] + wave_scan(__popcll(tri), lane, nullptr);
+        const long long cb = cof_s[a] + wave_scan(__popcll(cof), lane, nullptr);
+        if (!edge) continue;
+        const long long e = up_s[a] + __popcll(up & below(lane)), erow = e0 + e;
+        put_row(o, erow, 1, g, a, lane, 0);
+        put_adj(o, o3 + 2 * e, row0 + a, erow, 0, 1);
+        put_adj(o, o3 + 2 * e + 1, row0 + lane, erow, 0, 1);
+        put_adj(o, o4 + 2 * e, erow, row0 + a, 1, 0);
+        put_adj(o, o4 + 2 * e + 1, erow, row0 + lane, 1, 0);
+        const u64 upb = mb & above(lane);
+        int k = 0;
+        for (u64 r = tri; r; r &= r - 1, ++k) {
+            const int c = first_bit(r);
+            const long long t = tb + k, trow = t0 + t;
+            const long long eac = e0 + up_s[a] + __popcll(up & below(c)), ebc = e0 + up_s[lane] + __popcll(upb & below(c));
+            put_row(o, trow, 2, g, a, lane, c);
+            put_adj(o, o6 + 3 * t, erow, trow, 1, 2);
+            put_adj(o, o6 + 3 * t + 1, eac, trow, 1, 2);
+            put_adj(o, o6 + 3 * t + 2, ebc, trow, 1, 2);
+            put_adj(o, o7 + 3 * t, trow, erow, 2, 1);
+            put_adj(o, o7 + 3 * t + 1, trow, eac, 2, 1);
+            put_adj(o, o7 + 3 * t + 2, trow, ebc, 2, 1);
+        }
+        k = 0;
+        for (u64 r = cof; r; r &= r - 1, ++k) {
+            const int w = first_bit(r);
+            // in the sorted triple of {a, lane, w} the edge {a, w} always comes before {lane, w}
+            const int la = a < w ? a : w, ha = a < w ? w : a, lb = lane < w ? lane : w, hb = lane < w ? w : lane;
+            const long long eaw = e0 + up_s[la] + __popcll(m[la] & above(la) & below(ha));
+            const long long ebw = e0 + up_s[lb] + __popcll(m[lb] & above(lb) & below(hb));
+            put_adj(o, o5 + 2 * (cb + k), eaw, erow, 1, 1);
+            put_adj(o, o5 + 2 * (cb + k) + 1, ebw, erow, 1, 1);
+        }
+    }
+}
+
+// The fillers behind the real part (pad_batch): filler d-simplices, dimension by dimension, x_ind = 0..d, graph B - 1;
+// filler adjacencies = self-loops on the filler rows, round-robin, edge_types (d, d).
+__device__ void scatter_fillers(long block, long n_blocks, long B, int max_dim, Capacity cap, const Header* hdr, const Outputs& o) {
+    const long long S = hdr->n[0] + hdr->n[1] + hdr->n[2], E = hdr->adj;
+    const long long fill1 = cap.rows[1] - hdr->n[1], fill2 = max_dim >= 2 ? cap.rows[2] - hdr->n[2] : 0;
+    const long long n_fill = fill1 + fill2, e_fill = cap.edges - E;
+    const long long first = block * kBlock + threadIdx.x, stride = n_blocks * kBlock;
+    for (long long i = first; i < n_fill; i += stride) {
+        const int d = i < fill1 ? 1 : 2;
+        put_row(o, S + i, d, B - 1, 0, 1, d == 2 ? 2 : 0);
+    }
+    if (n_fill <= 0) return;                                  // (the offsets kernel has refused e_fill > 0 without a filler row)
+    for (long long j = first; j < e_fill; j += stride) {
+        const long long i = j % n_fill;
+        const int d = i < fill1 ? 1 : 2;
+        put_adj(o, E + j, S + i, S + i, d, d);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void lift_scatter_kernel(long B, int V, int max_dim, Capacity cap, const Header* hdr,
+                                                               const u64* masks, const int* n1, const int* n2, const long long* row_off,
+                                                               const long long* adj_off, Outputs o) {
+    if (!hdr->fit) return;
+    if ((long)blockIdx.x < B)
+        scatter_graph((long)blockIdx.x, V, max_dim, masks, n1, n2, row_off, adj_off, o);
+    else
+        scatter_fillers((long)blockIdx.x - B, (long)gridDim.x - B, B, max_dim, cap, hdr, o);
+}
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+inline bool sizes_ok(int64_t n_graphs, int32_t V, int32_t max_dim) {
+    return (max_dim == 1 || max_dim == 2) && V > max_dim && V <= kMaxVerts && n_graphs > 0 && n_graphs < (1ll << 31) / V;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t csmpn_rips_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim) {
+    if (!sizes_ok(n_graphs, verts_per_graph, max_dim)) return 0;
+    const size_t B = (size_t)n_graphs;
+    // alignment slack + header | masks | n1 | n2 | row offsets | adjacency offsets
+    return 256 + 256 + align256(sizeof(u64) * B * (size_t)verts_per_graph) + 2 * align256(sizeof(int) * B) +
+           2 * align256(sizeof(long long) * B);
+}
+
+int csmpn_rips_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, double dis, int32_t max_dim,
+                    const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                    int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                    int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int V = verts_per_graph;
+    if (max_dim < 0) return csmpn_fail(CSMPN_ERR_INVALID, "max_dim %d is negative", (int)max_dim);
+    if (max_dim != 1 && max_dim != 2) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "rips lift: max_dim %d (1 or 2)", (int)max_dim);
+    if (V > kMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "rips lift: %d vertices per graph > %d (one 64-bit mask per vertex)", V, kMaxVerts);
+    if (V <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "rips lift: %d vertices per graph, max_dim %d needs %d", V, (int)max_dim, (int)max_dim + 1);
+    if (n_graphs <= 0 || n_graphs >= (1ll << 31) / V) return csmpn_fail(CSMPN_ERR_INVALID, "bad sizes n_graphs=%lld verts_per_graph=%d", (long long)n_graphs, V);
+    if (point_dim <= 0) return csmpn_fail(CSMPN_ERR_INVALID, "point_dim %d", (int)point_dim);
+    if (!(dis >= 0.0)) return csmpn_fail(CSMPN_ERR_INVALID, "dis %g is negative or not a number", dis);
+    if (x_ind_cols <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "x_ind has %d columns, max_dim %d needs %d", (int)x_ind_cols, (int)max_dim, (int)max_dim + 1);
+    if (!points || !capacity_rows || !x_ind || !node_types || !batch || !x_ind_batch || !ptr || !x_ind_ptr || !edge_index)
+        return csmpn_fail(CSMPN_ERR_INVALID, "null pointer");
+    Capacity cap{};
+    long long total = 0;
+    for (int d = 0; d <= max_dim; ++d) {
+        cap.rows[d] = capacity_rows[d];
+        if (cap.rows[d] < 0 || cap.rows[d] >= (1ll << 31)) return csmpn_fail(CSMPN_ERR_INVALID, "capacity %lld of dimension %d", cap.rows[d], d);
+        total += cap.rows[d];
+    }
+    cap.edges = capacity_edges;
+    if (cap.rows[0] != n_graphs * V)
+        return csmpn_fail(CSMPN_ERR_INVALID, "capacity_rows[0] = %lld, the batch has %lld vertices (vertex rows are never padded)", cap.rows[0], (long long)(n_graphs * V));
+    if (total >= (1ll << 31) || cap.edges < 0 || cap.edges >= (1ll << 31))
+        return csmpn_fail(CSMPN_ERR_INVALID, "bad capacity: %lld rows, %lld adjacencies", total, cap.edges);
+    const size_t need = csmpn_rips_lift_workspace_bytes(n_graphs, V, max_dim);
+    if (!workspace || workspace_bytes < need) return csmpn_fail(CSMPN_ERR_INVALID, "rips lift workspace too small: %zu < %zu", workspace_bytes, need);
+    const size_t B = (size_t)n_graphs;
+    char* ws = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(workspace)));   // may cost up to 255 of the spare bytes
+    Header* hdr = reinterpret_cast<Header*>(ws);
+    ws += 256;
+    u64* masks = reinterpret_cast<u64*>(ws);
+    ws += align256(sizeof(u64) * B * (size_t)V);
+    int* n1 = reinterpret_cast<int*>(ws);
+    ws += align256(sizeof(int) * B);
+    int* n2 = reinterpret_cast<int*>(ws);
+    ws += align256(sizeof(int) * B);
+    long long* row_off = reinterpret_cast<long long*>(ws);
+    ws += align256(sizeof(long long) * B);
+    long long* adj_off = reinterpret_cast<long long*>(ws);
+    Outputs out{x_ind, node_types, batch, x_ind_batch, edge_index, edge_types, (int)x_ind_cols, cap.edges};
+    const long long fill_items = std::max(cap.rows[1] + cap.rows[2], cap.edges);
+    const long fill_blocks = (long)std::min<long long>(std::max<long long>((fill_items + kBlock - 1) / kBlock, 1), kMaxFillBlocks);
+    hipLaunchKernelGGL(lift_count_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, points, (int)point_dim, V, dis * dis, (int)max_dim,
+                       masks, n1, n2);
+    hipLaunchKernelGGL(lift_offsets_kernel, dim3(1), dim3(kBlock), 0, st, (const int*)n1, (const int*)n2, (long)B, V, (int)max_dim, cap,
+                       hdr, row_off, adj_off, ptr, x_ind_ptr, counts, (unsigned*)status);
+    hipLaunchKernelGGL(lift_scatter_kernel, dim3((unsigned)(B + fill_blocks)), dim3(kBlock), 0, st, (long)B, V, (int)max_dim, cap,
+                       (const Header*)hdr, (const u64*)masks, (const int*)n1, (const int*)n2, (const long long*)row_off,
+                       (const long long*)adj_off, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "rips lift kernels: %s", hipGetErrorString(e));
+    return CSMPN_OK;
+}
+
+}  // extern "C"

@@ -437,6 +437,35 @@ int csmpn_simplex_tables(const int64_t* x_ind, int32_t x_ind_cols, const int64_t
                          int64_t* graph_of_vertex, int64_t* vertices_per_graph, int32_t* types_i32, uint32_t* status,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Vietoris-Rips lift of a batch on the device at a fixed capacity: the structure tensors of exactly the batch that
+ *   pad_batch(collate([rips_complex(points_g, dis, max_dim) for g]), BatchCapacity(capacity_rows, capacity_edges))
+ * builds on the host (csmpn/data/complexes.py; the filler simplices and filler self-loop adjacencies behind the real part
+ * included), written into buffers of the capacity's shapes: no allocation, no host round trip, every launch on `stream`, no
+ * atomics on the outputs - every position is computed from popcounts of 64-bit neighbour masks and scans.
+ *   points (device, float [n_graphs * verts_per_graph, point_dim], the vertices of graph g contiguous); vertices a and b are
+ *     close iff sum_k ((double)p_a[k] - (double)p_b[k])^2 <= dis^2, summed in double over k ascending (a NaN is close to
+ *     nothing); dis >= 0;
+ *   capacity_rows (HOST, int64 [max_dim + 1]): rows per dimension; capacity_rows[0] == n_graphs * verts_per_graph;
+ *   outputs (device, int64): x_ind [rows, x_ind_cols] (x_ind_cols > max_dim; the columns behind a simplex's vertices are 0),
+ *     node_types / batch / x_ind_batch [rows] with rows = sum of capacity_rows, ptr / x_ind_ptr [n_graphs + 1],
+ *     edge_index [2, capacity_edges], edge_types [capacity_edges, 2] (may be NULL),
+ *     counts [max_dim + 2] (may be NULL): the real rows of every dimension, then the real adjacencies.
+ * A graph's real rows: its vertices, the close pairs (a < b) and, for max_dim = 2, the triples (a < b < c) with all pairs
+ * close, both in lexicographic order; its adjacencies in the order of lift() + to_complex().
+ * A batch that does not fit leaves EVERY output as it was and ORs into *status (device, may be NULL; never read, never
+ * cleared by the call): bit d (d = 1, 2) = more d-simplices than capacity_rows[d], bit 3 = more adjacencies than
+ * capacity_edges, bit 4 = filler adjacencies are needed but the batch leaves no filler row to carry them.
+ * Limits: max_dim in {1, 2} and verts_per_graph <= 64, else CSMPN_ERR_UNSUPPORTED; verts_per_graph > max_dim,
+ * n_graphs * verts_per_graph, the sum of capacity_rows and capacity_edges in [1, 2^31) ([0, 2^31) for the last), else
+ * CSMPN_ERR_INVALID. Arguments are checked before the first HIP call.
+ * workspace: csmpn_rips_lift_workspace_bytes(...) bytes of device memory (host-only query; 0 for sizes the entry point
+ * rejects); needs no initialisation. */
+size_t csmpn_rips_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim);
+int csmpn_rips_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, double dis, int32_t max_dim,
+                    const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                    int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                    int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fused simplex feature embedding (round 3; hulls_cssmpnn.py:96-125: vertex features of every d-simplex in all (d+1)!
  * vertex orders -> CEMLP -> sum over the orders), for the shapes the wide parity-lane kernels serve as standalone CEMLPs
  * (Cl(5,0) / Cl(4,1), 16 / 24 / 28 / 32 output channels, at most 8 input channels = verts_per_row * channels_per_vertex);

@@ -14,6 +14,10 @@ JSON line with the step times and the simplices / adjacencies of the batch.
                                batches: pad on the host, copy, rebuild the tables on the device, replay
   graphed_fixed_ms_per_step    the same captured step replayed on one topology (no refresh): the floor at this capacity
   fill_rows / fill_adjacencies real / padded, mean over the K batches
+--device-lift (with --varying, Rips models): the same K point sets in the same run through step(points=...)
+  graphed_device_lift_ms_per_step   csmpn_rips_lift + the in-place rebuild + the feature scatter + replay
+  graphed_host_lifted_ms_per_step   step(batch=pre-lifted host batch) again, measured right behind it
+  host_lift_ms_per_batch            rips_complex + collate + pad_batch of one batch on the host (what step(batch=...) leaves out)
 --pkg-root: import the package from another tree (a build of another commit) with this same tool file; a tree without
   the capacity interface reports the eager figure only.
 """
@@ -89,7 +93,9 @@ def op_sites(eager, steps=2):
 
 
 def make_batch(args, rng, cx):
-    """One collated CPU batch of the chosen model and the names of its changing tensors."""
+    """One collated CPU batch of the chosen model and the names of its changing tensors. The Rips models' batches carry the
+    points they were lifted from and the threshold (lift_points float32 [B * V, n], lift_dis) for --device-lift."""
+    points, dis = [], None
     if args.model == "hulls":
         batch = cx.collate([cx.hulls_example(rng.standard_normal((args.points, 5)).astype(np.float32))
                             for _ in range(args.batch)])
@@ -97,10 +103,11 @@ def make_batch(args, rng, cx):
     elif args.model == "motion":
         # motion-capture-shaped batch (motion_cssmpnn.py: Cl(3,0), 16 channels, 4 layers, aggr = mean): 31 joints per
         # skeleton, Vietoris-Rips complex of the joint positions, one frame of positions / velocities
-        V, graphs = 31, []
+        V, graphs, dis = 31, [], 1.6
         for _ in range(args.batch):
             base = (1.6 * rng.standard_normal((V, 3))).astype(np.float32)
-            c = cx.rips_complex(base, dis=1.6, max_dim=2)
+            points.append(base)
+            c = cx.rips_complex(base, dis=dis, max_dim=2)
             S = c.n_simplices
             pos, vel = torch.zeros(S, 3), torch.zeros(S, 3)
             pos[:V] = torch.from_numpy(base)
@@ -114,10 +121,11 @@ def make_batch(args, rng, cx):
     elif args.model == "nba":
         # NBA-shaped batch (nba_cssmpnn.py:12-190: Cl(2,0), 40 channels, 4 layers, aggr = sum): 6 agents in the plane (5 players +
         # the ball), 10 frames, Vietoris-Rips complex of the first frame; the target: 40 future frames of the 5 players
-        V, F, graphs, ys = 6, 10, [], []
+        V, F, graphs, ys, dis = 6, 10, [], [], 1.6
         for _ in range(args.batch):
             base = rng.standard_normal((V, 2)).astype(np.float32)
-            c = cx.rips_complex(base, dis=1.6, max_dim=2)
+            points.append(base)
+            c = cx.rips_complex(base, dis=dis, max_dim=2)
             S = c.n_simplices
             pos, vel = torch.zeros(S, F, 2), torch.zeros(S, F, 2)
             pos[:V] = torch.from_numpy(base)[:, None, :] + 0.05 * torch.from_numpy(rng.standard_normal((V, F, 2)).astype(np.float32))
@@ -132,10 +140,11 @@ def make_batch(args, rng, cx):
     else:
         # MD17-shaped batch (md17_cssmpnn.py; csmpn/configs/md17.yaml: Cl(3,0), 32 channels, 5 layers): 21 atoms
         # (aspirin), 10 frames, Vietoris-Rips complex of the first frame, random positions / velocities / charges
-        V, F, graphs = 21, 10, []
+        V, F, graphs, dis = 21, 10, [], 1.8
         for _ in range(args.batch):
             base = (1.6 * rng.standard_normal((V, 3))).astype(np.float32)
-            c = cx.rips_complex(base, dis=1.8, max_dim=2)
+            points.append(base)
+            c = cx.rips_complex(base, dis=dis, max_dim=2)
             S = c.n_simplices
             loc = torch.zeros(S, F, 3); vel = torch.zeros(S, F, 3); ch = torch.zeros(S, F, 1)
             loc[:V] = torch.from_numpy(base)[:, None, :] + 0.05 * torch.from_numpy(rng.standard_normal((V, F, 3)).astype(np.float32))
@@ -147,6 +156,8 @@ def make_batch(args, rng, cx):
         batch.y = torch.cat([g.features["loc"][: g.n_vertices] + 0.1 * torch.randn(g.n_vertices, F, 3) for g in graphs], dim=0)
         batch._names.append("y")
         features = ["loc", "vel", "charges", "y"]
+    if points:
+        batch.lift_points, batch.lift_dis = np.concatenate(points, axis=0), dis
     return batch, features
 
 
@@ -197,7 +208,35 @@ def varying(args, rng, cx, M, GraphedTrainStep, dev):
                    fill_rows=round(float(np.mean([b.x_ind.shape[0] for b in batches])) / cap.rows, 4),
                    fill_adjacencies=round(float(np.mean([b.edge_index.shape[1] for b in batches])) / cap.edges, 4),
                    loss=float(gs.loss.detach()))
+        if args.device_lift:
+            device_lift(args, out, cx, gs, batches, features, cap, dev)
     print(json.dumps(out))
+
+
+def device_lift(args, out, cx, gs, batches, features, cap, dev):
+    """--device-lift: the same K point sets through step(points=...) - the complexes lifted on the device in front of the
+    replay - beside step(batch=pre-lifted host batch) of the same run, and what the host lift of such a batch costs."""
+    if not hasattr(gs, "load_points") or not hasattr(batches[0], "lift_points"):
+        raise SystemExit("--device-lift needs a Rips model (md17, motion, nba) and a tree with the device lift")
+    K, dis = len(batches), batches[0].lift_dis
+    names = [k for k in features if k != "y"]
+    on_dev = []
+    for b in batches:
+        vertex = b.node_types == 0
+        on_dev.append((torch.from_numpy(b.lift_points).to(dev), {k: getattr(b, k)[vertex].to(dev) for k in names}, b.y.to(dev)))
+
+    def lifted(i):
+        pts, vf, y = on_dev[i % K]
+        return gs.step(features={"y": y}, points=pts, vertex_features=vf, dis=dis)
+
+    out["graphed_device_lift_ms_per_step"] = round(timed(lifted, args.steps), 3)
+    out["graphed_host_lifted_ms_per_step"] = round(timed(lambda i: gs.step(batch=batches[i % K]), args.steps), 3)
+    out["status_after_device_lift"] = gs.status()
+    t0 = time.perf_counter()
+    for b in batches:
+        p = b.lift_points.reshape(b.num_graphs, -1, b.lift_points.shape[-1])
+        cx.pad_batch(cx.collate([cx.rips_complex(g, dis=dis, max_dim=2) for g in p]), cap)
+    out["host_lift_ms_per_batch"] = round((time.perf_counter() - t0) * 1e3 / K, 3)
 
 
 def main():
@@ -213,6 +252,7 @@ def main():
     ap.add_argument("--op-sites", action="store_true", help="GPU kernels of one eager step by the package line that launched them")
     ap.add_argument("--varying", type=int, default=0, metavar="K", help="K batches of different topology: the eager loop on fresh device batches against ONE captured step with a capacity")
     ap.add_argument("--slack", type=float, default=0.0, help="--varying: capacity_of(batches, slack)")
+    ap.add_argument("--device-lift", action="store_true", help="--varying: also step(points=...), the complexes lifted on the device, and the host time of the lift")
     ap.add_argument("--pkg-root", default=None, help="import the package from this tree instead of the tool's own")
     args = ap.parse_args()
     if args.pkg_root:
