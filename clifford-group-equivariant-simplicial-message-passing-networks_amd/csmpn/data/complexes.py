@@ -16,6 +16,12 @@ then lets PyG collate graphs into a batch with `follow_batch=["node_types", "x_i
   hull_complex(points) / rips_complex(...)   the two complex constructions the task data use
                                              (utils.py:210-247 convex hull faces; utils.py:106-137
                                              distance-thresholded cliques)
+  knn_edges / knn_clique_complex(points, k)  the third one, md17's aspirin configuration: the 2- and
+                                             3-cliques of the k-nearest-neighbour graph
+                                             (csmpn/data/md17.py:64 knn_graph; utils.py:151-207
+                                             simplicial_lift) with the adjacencies of
+                                             utils.py:322-375 generate_adjacencies, which has NO
+                                             fully connected 0-0 block: lift(..., vertex_block=False)
   collate(complexes)                          the batch the task models read: x_ind (vertex ids
                                              LOCAL to each graph, as in the reference: x_ind has no
                                              `__inc__`), node_types, edge_index (offset per graph),
@@ -50,8 +56,9 @@ class SimplicialComplex:
         return int(self.x_ind.shape[0])
 
 
-def lift(n_vertices: int, top_simplices: Sequence[Sequence[int]], max_dim: int = 2):
-    """All faces up to `max_dim` of the given simplices and the reference's adjacencies.
+def lift(n_vertices: int, top_simplices: Sequence[Sequence[int]], max_dim: int = 2, vertex_block: bool = True):
+    """All faces up to `max_dim` of the given simplices and the reference's adjacencies. vertex_block=False leaves out the
+    fully connected 0-0 block over the non-edges (the clique lift of a graph, utils.py:322-375, has none).
 
     Returns (x_dict, adj): x_dict[d] = int64 [n_d, d+1] (sorted vertex tuples, lexicographic order),
     adj["s_t"] = int64 [2, n] (source index in dimension s, target index in dimension t)."""
@@ -85,7 +92,7 @@ def lift(n_vertices: int, top_simplices: Sequence[Sequence[int]], max_dim: int =
                     add(f"{k - 1}_{k}", index[k - 1][b], si)
     # fully connected 0-0 block over the non-edges; the test `[i, j] not in edges_present` compares with
     # SORTED vertex lists, so (i, j) with i > j is added even when {i, j} is an edge (utils.py:91-97)
-    if max_dim >= 1:
+    if max_dim >= 1 and vertex_block:
         present = set(ordered[1])
         for i in range(n_vertices):
             for j in range(n_vertices):
@@ -148,6 +155,60 @@ def rips_complex(points: np.ndarray, dis: float, max_dim: int = 2) -> Simplicial
                 tops.append(sub)
     x_dict, adj = lift(V, tops, max_dim)
     return to_complex(V, x_dict, adj, max_dim)
+
+
+def _pair_sums(points: np.ndarray) -> np.ndarray:
+    """s[a, b] = sum_j (p_a[j] - p_b[j])^2 in float64, j ascending, one rounding per product and per sum (what
+    csrc/lift.hip takes); a NaN sum counts as +infinity."""
+    pts = np.asarray(points, dtype=np.float64)
+    s = np.zeros((len(pts), len(pts)), dtype=np.float64)
+    for j in range(pts.shape[1]):
+        d = pts[:, None, j] - pts[None, :, j]
+        s = s + d * d
+    s[np.isnan(s)] = np.inf
+    return s
+
+
+def knn_edges(points: np.ndarray, k: int) -> torch.Tensor:
+    """The directed k-nearest-neighbour list of `points` [V, n] as int64 [2, E] (row 0 = the neighbour, row 1 = the vertex:
+    the source_to_target flow of knn_graph), targets ascending, the neighbours of a target ascending.
+
+    With s(a, b) the float64 sum of _pair_sums, the rank of b for a is the number of c outside {a, b} with s(a, c) < s(a, b),
+    or s(a, c) == s(a, b) and c < b; b is a neighbour of a iff that rank is below k. Ties - coincident points and NaN
+    vertices among them - go to the smaller index; k >= V - 1 makes every other vertex a neighbour. On points with pairwise
+    distinct distances this is THE k-nearest-neighbour graph, whatever the implementation; how torch_cluster.knn_graph
+    breaks ties is a detail of its search and is not restated here."""
+    if int(k) < 1:
+        raise ValueError("knn_edges: k must be at least 1")
+    s = _pair_sums(points)
+    V = len(s)
+    src, dst = [], []
+    for a in range(V):
+        others = [b for b in range(V) if b != a]
+        others.sort(key=lambda b: (s[a, b], b))
+        for b in sorted(others[:int(k)]):
+            src.append(b)
+            dst.append(a)
+    return torch.tensor([src, dst], dtype=torch.int64).reshape(2, -1)
+
+
+def knn_clique_complex(points: np.ndarray, k: int, max_dim: int = 2) -> SimplicialComplex:
+    """The clique complex of the undirected k-nearest-neighbour graph of `points` (knn_edges: {a, b} is an edge iff b is a
+    neighbour of a or a one of b - what nx.Graph makes of the directed list): the vertices, the edges and, for max_dim = 2,
+    every triple whose three pairs are edges (utils.py:151-207), with the adjacencies of lift(..., vertex_block=False).
+    The tie rule is knn_edges' own; see there what is and is not claimed about torch_cluster."""
+    ei = knn_edges(points, k)
+    V = len(np.asarray(points))
+    adj = np.zeros((V, V), dtype=bool)
+    adj[ei[0].numpy(), ei[1].numpy()] = True
+    adj |= adj.T
+    tops = []
+    for d in range(1, max_dim + 1):
+        for sub in itertools.combinations(range(V), d + 1):
+            if all(adj[a, b] for a, b in itertools.combinations(sub, 2)):
+                tops.append(sub)
+    x_dict, adjs = lift(V, tops, max_dim, vertex_block=False)
+    return to_complex(V, x_dict, adjs, max_dim)
 
 
 class SimplicialBatch:
@@ -257,11 +318,14 @@ class SimplicialBatch:
                 build(plan[key])
         return self
 
-    def relift_(self, points: torch.Tensor, dis: float, vertex_features: Optional[Dict[str, torch.Tensor]] = None) -> "SimplicialBatch":
+    def relift_(self, points: torch.Tensor, dis: Optional[float] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
+                knn: Optional[int] = None) -> "SimplicialBatch":
         """Make this DEVICE batch hold the Vietoris-Rips complexes of `points` (device float32 [B * V, n], the V vertices of
         graph g contiguous; B and V are this batch's) at threshold `dis`, at the capacity the batch was built with: the
         structure tensors are written by ops.rips_lift (csmpn_rips_lift) as pad_batch(collate([rips_complex(...)]), capacity)
-        would lay them out, then everything derived from them is rebuilt in place as in refresh_. vertex_features
+        would lay them out, then everything derived from them is rebuilt in place as in refresh_. With knn=k instead of
+        dis (exactly one of the two, else ValueError) the complexes are the clique complexes of the k-nearest-neighbour
+        graphs, knn_clique_complex(points, k), written by ops.knn_lift (csmpn_knn_lift). vertex_features
         {name: per-vertex tensor [B * V, ...]}: the per-simplex tensor `name` is zeroed and gets these rows at the vertex
         rows of the new batch. plan() and csr() must have been called. After the first call: no allocation, no host
         synchronisation. A complex that does not fit the capacity leaves the batch as it was (the features excepted, which
@@ -269,6 +333,8 @@ class SimplicialBatch:
         n_real_edges are dropped: the real counts live on the device, in plan()["lift_counts"] (rows per dimension,
         adjacencies)."""
         from csmpn_hip import ops
+        if (dis is None) == (knn is None):
+            raise ValueError("relift_: pass exactly one of dis=... (Rips) and knn=... (k-nearest-neighbour cliques)")
         plan = getattr(self, "_plan", None)
         if plan is None or self._csr is None:
             raise RuntimeError("relift_: call plan() and csr() on the batch first")
@@ -285,13 +351,15 @@ class SimplicialBatch:
                 raise ValueError(f"relift_: {name!r} is not a per-simplex feature tensor of the batch")
             if tuple(value.shape) != (rows[0],) + tuple(t.shape[1:]):
                 raise ValueError(f"relift_: vertex feature {name!r} has shape {tuple(value.shape)}, expected {(rows[0],) + tuple(t.shape[1:])}")
-        if "lift_ws" not in plan:
-            plan["lift_ws"] = ops.rips_lift_workspace(B, rows[0] // B, max_dim, dev)
+        if "lift_ws" not in plan:      # one workspace serves both lifts: the larger of the two queries (they are equal today)
+            sizes = [query(B, rows[0] // B, max_dim, dev) for query in (ops.rips_lift_workspace, ops.knn_lift_workspace)]
+            plan["lift_ws"] = max(sizes, key=lambda t: t.numel())
             plan["lift_status"] = torch.zeros(1, dtype=torch.int32, device=dev)
             plan["lift_counts"] = torch.zeros(max_dim + 2, dtype=torch.int64, device=dev)
-        ops.rips_lift(points, B, dis, max_dim, rows, int(self.edge_index.shape[1]), self.x_ind, self.node_types, self.batch,
-                      self.x_ind_batch, self.ptr, self.x_ind_ptr, self.edge_index, getattr(self, "edge_types", None),
-                      plan["lift_counts"], plan["lift_status"], plan["lift_ws"])
+        run, param = (ops.rips_lift, dis) if knn is None else (ops.knn_lift, knn)
+        run(points, B, param, max_dim, rows, int(self.edge_index.shape[1]), self.x_ind, self.node_types, self.batch,
+            self.x_ind_batch, self.ptr, self.x_ind_ptr, self.edge_index, getattr(self, "edge_types", None),
+            plan["lift_counts"], plan["lift_status"], plan["lift_ws"])
         for k in ("n_real_rows", "n_real_edges"):
             if hasattr(self, k):
                 delattr(self, k)
@@ -503,12 +571,14 @@ def pad_batch(batch: "SimplicialBatch", capacity: BatchCapacity, simplex_feature
     return padded
 
 
-# ------------------------------------------------------------------------------- Rips complexes built on the device
+# ------------------------------------------------------------------------------- complexes built on the device
 #
 # A complex that depends on the current positions (a loader that does not pre-lift, jittered positions, a rollout that
 # re-lifts from predicted positions) is lifted on the device at a fixed capacity (csmpn_rips_lift, csrc/lift.hip): the
 # structure tensors come out exactly as pad_batch(collate([rips_complex(...)])) lays them out, and relift_ rebuilds the
-# rest in place in front of a replayed step.
+# rest in place in front of a replayed step. The clique complex of the k-nearest-neighbour graph (knn_clique_complex, the
+# reference's aspirin configuration) is lifted the same way by csmpn_knn_lift: knn_capacity, knn_batch_device,
+# relift_(points, knn=k).
 
 
 def rips_adjacencies(n_graphs: int, verts_per_graph: int, n_edges: int, n_triangles: int) -> int:
@@ -532,6 +602,29 @@ def rips_capacity(n_graphs: int, verts_per_graph: int, max_edges: int, max_trian
     return BatchCapacity(rows, rips_adjacencies(n_graphs, verts_per_graph, max_edges, max_triangles))
 
 
+def clique_adjacencies(n_edges: int, n_triangles: int) -> int:
+    """Adjacencies of clique complexes (lift(..., vertex_block=False)) with n_edges 1-simplices and n_triangles 2-simplices in
+    all: 2 n1 each of 0_0 (through a shared edge), 0_1 and 1_0, 6 n2 of 1_1 and 3 n2 each of 1_2 and 2_1."""
+    return 6 * int(n_edges) + 12 * int(n_triangles)
+
+
+def knn_capacity(n_graphs: int, verts_per_graph: int, k: int, max_triangles: int, max_edges: Optional[int] = None,
+                 max_dim: int = 2) -> BatchCapacity:
+    """The capacity that serves every batch of n_graphs k-nearest-neighbour clique complexes on verts_per_graph vertices each
+    with at most max_triangles 2-simplices and max_edges 1-simplices in all (default: the bound n_graphs * min(k V,
+    V (V - 1) / 2) - every vertex names k neighbours) - with the one spare 1-simplex of rips_capacity."""
+    if max_dim not in (1, 2):
+        raise ValueError("knn_capacity: max_dim must be 1 or 2")
+    if n_graphs < 1 or verts_per_graph < max_dim + 1 or k < 1 or max_triangles < 0 or (max_edges is not None and max_edges < 0):
+        raise ValueError("knn_capacity: need n_graphs >= 1, verts_per_graph >= max_dim + 1, k >= 1 and counts >= 0")
+    if max_edges is None:
+        max_edges = n_graphs * min(k * verts_per_graph, verts_per_graph * (verts_per_graph - 1) // 2)
+    if max_dim == 1:
+        max_triangles = 0
+    rows = (n_graphs * verts_per_graph, max_edges + 1) + ((max_triangles,) if max_dim == 2 else ())
+    return BatchCapacity(rows, clique_adjacencies(max_edges, max_triangles))
+
+
 def rips_batch_device(points: torch.Tensor, n_graphs: int, dis: float, capacity: BatchCapacity,
                       features: Optional[Dict[str, torch.Tensor]] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
                       x_ind_cols: Optional[int] = None) -> SimplicialBatch:
@@ -540,22 +633,35 @@ def rips_batch_device(points: torch.Tensor, n_graphs: int, dis: float, capacity:
     (per-graph labels, per-vertex targets); vertex_features {name: per-vertex tensor [n_graphs * V, ...]}: per-simplex
     tensors [capacity.rows, ...] that hold these rows at the vertex rows and zeros elsewhere. Synchronises once;
     ValueError if the complex does not fit the capacity."""
+    return _lifted_batch_device("rips_batch_device", "rips_lift", points, n_graphs, dis, capacity, features, vertex_features, x_ind_cols)
+
+
+def knn_batch_device(points: torch.Tensor, n_graphs: int, k: int, capacity: BatchCapacity,
+                     features: Optional[Dict[str, torch.Tensor]] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
+                     x_ind_cols: Optional[int] = None) -> SimplicialBatch:
+    """rips_batch_device for the k-nearest-neighbour clique complexes of the points (knn_clique_complex; csmpn_knn_lift) -
+    the batch relift_(points, knn=k) is then called on."""
+    return _lifted_batch_device("knn_batch_device", "knn_lift", points, n_graphs, k, capacity, features, vertex_features, x_ind_cols)
+
+
+def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, vertex_features, x_ind_cols) -> SimplicialBatch:
+    """The body of rips_batch_device (op = "rips_lift", param = dis) and knn_batch_device (op = "knn_lift", param = k)."""
     from csmpn_hip import ops
     if not points.is_cuda:
-        raise RuntimeError("rips_batch_device needs device points (no CPU fallback)")
+        raise RuntimeError(f"{what} needs device points (no CPU fallback)")
     dev, max_dim, S, E, B = points.device, capacity.max_dim, capacity.rows, capacity.edges, int(n_graphs)
     i64 = lambda *shape: torch.zeros(*shape, dtype=torch.int64, device=dev)
     tensors = dict(x_ind=i64(S, max_dim + 1 if x_ind_cols is None else int(x_ind_cols)), node_types=i64(S), edge_index=i64(2, E),
                    edge_types=i64(E, 2), batch=i64(S), ptr=i64(B + 1), x_ind_batch=i64(S), x_ind_ptr=i64(B + 1))
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     counts = i64(max_dim + 2)
-    ws = ops.rips_lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev)
-    ops.rips_lift(points, B, dis, max_dim, capacity.simplices, E, tensors["x_ind"], tensors["node_types"], tensors["batch"],
-                  tensors["x_ind_batch"], tensors["ptr"], tensors["x_ind_ptr"], tensors["edge_index"], tensors["edge_types"], counts,
-                  status, ws)
+    ws = getattr(ops, op + "_workspace")(B, int(points.shape[0]) // max(B, 1), max_dim, dev)
+    getattr(ops, op)(points, B, param, max_dim, capacity.simplices, E, tensors["x_ind"], tensors["node_types"], tensors["batch"],
+                     tensors["x_ind_batch"], tensors["ptr"], tensors["x_ind_ptr"], tensors["edge_index"], tensors["edge_types"], counts,
+                     status, ws)
     word = int(status.item())
     if word:
-        raise ValueError(f"rips_batch_device: the complex does not fit the capacity {capacity} (status {word:#x}: bit 1 / 2 = too "
+        raise ValueError(f"{what}: the complex does not fit the capacity {capacity} (status {word:#x}: bit 1 / 2 = too "
                          "many 1- / 2-simplices, bit 3 = too many adjacencies, bit 4 = filler adjacencies without a filler row)")
     vertex_rows = torch.nonzero(tensors["node_types"] == 0, as_tuple=False).flatten()
     for name, value in (vertex_features or {}).items():

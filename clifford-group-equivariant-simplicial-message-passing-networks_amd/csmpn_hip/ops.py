@@ -1417,7 +1417,7 @@ def simplex_tables(x_ind, node_types, x_ind_batch, x_ind_ptr, max_dim, rows, ver
 
 # --------------------------------------------------------------------------------- the Rips lift of a batch on the device
 
-# bits of the status word of rips_lift; bit d (d = 1, 2) = more d-simplices than the capacity
+# bits of the status word of rips_lift / knn_lift; bit d (d = 1, 2) = more d-simplices than the capacity
 LIFT_STATUS_EDGES, LIFT_STATUS_NO_FILLER_ROW = 8, 16
 
 
@@ -1427,23 +1427,19 @@ def rips_lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, devic
                        dtype=torch.uint8, device=device)
 
 
-def rips_lift(points, n_graphs, dis, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch, x_ind_batch, ptr,
-              x_ind_ptr, edge_index, edge_types, counts, status, workspace):
-    """csmpn_rips_lift: the structure tensors of pad_batch(collate([rips_complex(points of graph g, dis, max_dim)]), capacity)
-    written into the given int64 buffers of the capacity's shapes (x_ind [S, M], node_types / batch / x_ind_batch [S],
-    ptr / x_ind_ptr [B + 1], edge_index [2, E], edge_types = None or [E, 2], counts = None or [max_dim + 2]) from
-    points float32 [B * V, n] on the current stream: no allocation, no host round trip. A batch that does not fit leaves the
-    buffers as they were and sets bits of `status` (None or a 4-byte device word)."""
+def _lift_arguments(what, points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch, x_ind_batch, ptr,
+                    x_ind_ptr, edge_index, edge_types, counts, status):
+    """The tensor validation rips_lift and knn_lift share; returns (B, V, E, the capacity rows as a C array)."""
     if not points.is_cuda:
-        raise RuntimeError("rips_lift needs device tensors (no CPU fallback)")
+        raise RuntimeError(f"{what} needs device tensors (no CPU fallback)")
     if points.dtype != torch.float32 or points.dim() != 2 or not points.is_contiguous():
-        raise RuntimeError("rips_lift: points must be a contiguous float32 tensor [B * V, n]")
+        raise RuntimeError(f"{what}: points must be a contiguous float32 tensor [B * V, n]")
     B, rows = int(n_graphs), [int(r) for r in capacity_rows]
     if B <= 0 or points.shape[0] % B:
-        raise RuntimeError(f"rips_lift: {points.shape[0]} points do not divide into {B} graphs")
+        raise RuntimeError(f"{what}: {points.shape[0]} points do not divide into {B} graphs")
     S, E, nd = sum(rows), int(capacity_edges), int(max_dim) + 1
     if len(rows) != nd:
-        raise RuntimeError(f"rips_lift: max_dim = {max_dim} needs {nd} row capacities")
+        raise RuntimeError(f"{what}: max_dim = {max_dim} needs {nd} row capacities")
     shapes = (("x_ind", x_ind, None), ("node_types", node_types, (S,)), ("batch", batch, (S,)), ("x_ind_batch", x_ind_batch, (S,)),
               ("ptr", ptr, (B + 1,)), ("x_ind_ptr", x_ind_ptr, (B + 1,)), ("edge_index", edge_index, (2, E)),
               ("edge_types", edge_types, (E, 2)), ("counts", counts, (nd + 1,)))
@@ -1451,16 +1447,48 @@ def rips_lift(points, n_graphs, dis, max_dim, capacity_rows, capacity_edges, x_i
         if t is None and name in ("edge_types", "counts"):
             continue
         if t.dtype != torch.int64 or not t.is_contiguous() or t.device != points.device or (shape is not None and tuple(t.shape) != shape):
-            raise RuntimeError(f"rips_lift: {name} must be a contiguous int64 tensor{'' if shape is None else ' ' + str(list(shape))} on the device of points")
+            raise RuntimeError(f"{what}: {name} must be a contiguous int64 tensor{'' if shape is None else ' ' + str(list(shape))} on the device of points")
     if x_ind.dim() != 2 or int(x_ind.shape[0]) != S:
-        raise RuntimeError(f"rips_lift: x_ind must be [{S}, M]")
+        raise RuntimeError(f"{what}: x_ind must be [{S}, M]")
     if status is not None and (status.element_size() != 4 or status.numel() < 1 or status.device != points.device):
-        raise RuntimeError("rips_lift: status must be a 4-byte device word")
+        raise RuntimeError(f"{what}: status must be a 4-byte device word")
+    return B, int(points.shape[0]) // B, E, (C.c_int64 * nd)(*rows)
+
+
+def rips_lift(points, n_graphs, dis, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch, x_ind_batch, ptr,
+              x_ind_ptr, edge_index, edge_types, counts, status, workspace):
+    """csmpn_rips_lift: the structure tensors of pad_batch(collate([rips_complex(points of graph g, dis, max_dim)]), capacity)
+    written into the given int64 buffers of the capacity's shapes (x_ind [S, M], node_types / batch / x_ind_batch [S],
+    ptr / x_ind_ptr [B + 1], edge_index [2, E], edge_types = None or [E, 2], counts = None or [max_dim + 2]) from
+    points float32 [B * V, n] on the current stream: no allocation, no host round trip. A batch that does not fit leaves the
+    buffers as they were and sets bits of `status` (None or a 4-byte device word)."""
+    B, V, E, cap = _lift_arguments("rips_lift", points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch,
+                                   x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status)
     dev = points.device
-    cap = (C.c_int64 * nd)(*rows)
     with torch.cuda.device(dev):
         check(native.lib().csmpn_rips_lift(
-            points.data_ptr(), int(points.shape[1]), B, int(points.shape[0]) // B, float(dis), int(max_dim), C.addressof(cap), E,
+            points.data_ptr(), int(points.shape[1]), B, V, float(dis), int(max_dim), C.addressof(cap), E,
+            x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), batch.data_ptr(), x_ind_batch.data_ptr(), ptr.data_ptr(),
+            x_ind_ptr.data_ptr(), edge_index.data_ptr(), _ptr(edge_types), _ptr(counts), _ptr(status), workspace.data_ptr(),
+            workspace.numel(), _stream(dev)))
+
+
+def knn_lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, device) -> torch.Tensor:
+    """Workspace of knn_lift (uninitialised device bytes)."""
+    return torch.empty(max(int(native.lib().csmpn_knn_lift_workspace_bytes(int(n_graphs), int(verts_per_graph), int(max_dim))), 16),
+                       dtype=torch.uint8, device=device)
+
+
+def knn_lift(points, n_graphs, k, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch, x_ind_batch, ptr,
+             x_ind_ptr, edge_index, edge_types, counts, status, workspace):
+    """csmpn_knn_lift: rips_lift for the clique complex of the k-nearest-neighbour graph - the structure tensors of
+    pad_batch(collate([knn_clique_complex(points of graph g, k, max_dim)]), capacity), same buffers, same status bits."""
+    B, V, E, cap = _lift_arguments("knn_lift", points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch,
+                                   x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status)
+    dev = points.device
+    with torch.cuda.device(dev):
+        check(native.lib().csmpn_knn_lift(
+            points.data_ptr(), int(points.shape[1]), B, V, int(k), int(max_dim), C.addressof(cap), E,
             x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), batch.data_ptr(), x_ind_batch.data_ptr(), ptr.data_ptr(),
             x_ind_ptr.data_ptr(), edge_index.data_ptr(), _ptr(edge_types), _ptr(counts), _ptr(status), workspace.data_ptr(),
             workspace.numel(), _stream(dev)))

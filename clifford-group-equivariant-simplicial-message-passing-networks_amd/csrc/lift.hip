@@ -4,6 +4,9 @@
 // behind the real part included - from the vertex positions, without an allocation, a host round trip or an atomic on an
 // output: every position of every entry is computed, never claimed.
 //
+// csmpn_knn_lift is the same lift of the clique complex of the k-nearest-neighbour graph (knn_clique_complex): another
+// kernel produces the neighbour masks, and the adjacencies have no 0_0 block over the non-edges (kVertexBlock = false).
+//
 // A graph has at most 64 vertices, so ONE 64-bit neighbour mask per vertex (a wave ballot over the other vertices) carries
 // it, and every index is a popcount of masks plus a scan: with upper[a] = mask[a] restricted to b > a,
 //   index of the edge (a, b), a < b      = sum_{a' < a} popc(upper[a']) + popc(upper[a] & below(b))
@@ -12,6 +15,7 @@
 // Both scans are kept per vertex a (64 entries in LDS); the part inside a's row of edges is a wave scan over the lanes b.
 //
 //   count    one workgroup per graph: the masks -> workspace, the graph's numbers of 1- and 2-simplices
+//            (lift_count_kernel: pairs within dis; lift_knn_kernel: the symmetrised k nearest neighbours)
 //   offsets  ONE workgroup: the totals against the capacity -> fit flag, status word; where the batch fits, the scan of the
 //            graphs' row and adjacency counts (256 graphs per pass) -> ptr / x_ind_ptr, counts, the offsets of every graph
 //   scatter  one workgroup per graph + workgroups for the fillers; all of them return at once when the fit flag is clear,
@@ -91,28 +95,9 @@ __device__ __forceinline__ void put_adj(const Outputs& o, long long pos, long lo
     }
 }
 
-// one workgroup per graph: mask[a] bit b = (a != b and |p_a - p_b|^2 <= dis^2, summed in double over k ascending)
-__global__ __launch_bounds__(kBlock) void lift_count_kernel(const float* points, int P, int V, double dis2, int max_dim,
-                                                             u64* masks, int* n1, int* n2) {
-    __shared__ u64 m[kMaxVerts];
-    const long g = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* pg = points + g * V * (long)P;
-    for (int a = wave; a < V; a += kWaves) {
-        bool close = false;
-        if (lane < V && lane != a) {
-            double s = 0.0;
-            for (int k = 0; k < P; ++k) {
-                const double d = (double)pg[a * P + k] - (double)pg[lane * P + k];
-                s = __dadd_rn(s, __dmul_rn(d, d));            // no contraction: the sum the host takes
-            }
-            close = s <= dis2;                                // false for a NaN
-        }
-        const u64 mk = __ballot(close);
-        if (lane == 0) m[a] = mk;
-    }
-    __syncthreads();
-    if (wave != 0) return;
+// The end of both mask kernels, run by wave 0 once m[0 .. V) is complete in LDS: the masks -> workspace, the graph's numbers
+// of 1-simplices (bits above the diagonal) and 2-simplices (common upper neighbours of the two ends of every edge).
+__device__ __forceinline__ void count_tail(const u64* m, long g, int V, int max_dim, int lane, u64* masks, int* n1, int* n2) {
     int c1 = 0, c2 = 0;
     if (lane < V) {
         const u64 ma = m[lane], up = ma & above(lane);
@@ -135,13 +120,85 @@ __global__ __launch_bounds__(kBlock) void lift_count_kernel(const float* points,
     }
 }
 
-// one workgroup: totals against the capacity; if the batch fits, the offsets of every graph and ptr / x_ind_ptr / counts
+// one workgroup per graph: mask[a] bit b = (a != b and |p_a - p_b|^2 <= dis^2, summed in double over k ascending)
+__global__ __launch_bounds__(kBlock) void lift_count_kernel(const float* points, int P, int V, double dis2, int max_dim,
+                                                             u64* masks, int* n1, int* n2) {
+    __shared__ u64 m[kMaxVerts];
+    const long g = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* pg = points + g * V * (long)P;
+    for (int a = wave; a < V; a += kWaves) {
+        bool close = false;
+        if (lane < V && lane != a) {
+            double s = 0.0;
+            for (int k = 0; k < P; ++k) {
+                const double d = (double)pg[a * P + k] - (double)pg[lane * P + k];
+                s = __dadd_rn(s, __dmul_rn(d, d));            // no contraction: the sum the host takes
+            }
+            close = s <= dis2;                                // false for a NaN
+        }
+        const u64 mk = __ballot(close);
+        if (lane == 0) m[a] = mk;
+    }
+    __syncthreads();
+    if (wave == 0) count_tail(m, g, V, max_dim, lane, masks, n1, n2);
+}
+
+// one workgroup per graph: mask[a] bit b = (b is one of the k nearest neighbours of a, or a one of b's). With s(a, b) the
+// sum of lift_count_kernel (a NaN counts as +infinity), the rank of b for a is the number of c outside {a, b} with
+// s(a, c) < s(a, b), or s(a, c) == s(a, b) and c < b; b is a neighbour of a iff that rank is below k. The wave of a holds
+// the row s(a, .) one value per lane and reads it across the lanes: no LDS for the row, no scratch.
+__global__ __launch_bounds__(kBlock) void lift_knn_kernel(const float* points, int P, int V, int k, int max_dim, u64* masks,
+                                                           int* n1, int* n2) {
+    __shared__ u64 dir[kMaxVerts], m[kMaxVerts];
+    const long g = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* pg = points + g * V * (long)P;
+    for (int a = wave; a < V; a += kWaves) {
+        const bool in = lane < V && lane != a;
+        double s = __longlong_as_double(0x7ff0000000000000ll);
+        if (in) {
+            double t = 0.0;
+            for (int j = 0; j < P; ++j) {
+                const double d = (double)pg[a * P + j] - (double)pg[lane * P + j];
+                t = __dadd_rn(t, __dmul_rn(d, d));            // no contraction: the sum the host takes
+            }
+            if (t == t) s = t;                                // a NaN stays +infinity
+        }
+        int rank = 0;
+        for (int c = 0; c < V; ++c) {                         // c is wave-uniform
+            const double sc = __shfl(s, c, 64);
+            rank += c != a && c != lane && (sc < s || (sc == s && c < lane)) ? 1 : 0;
+        }
+        const u64 d = __ballot(in && rank < k);
+        if (lane == 0) dir[a] = d;
+    }
+    __syncthreads();
+    if (wave == 0) {                                          // the undirected graph: bit b of dir[a] | bit a of dir[b]
+        u64 sym = 0ull;
+        if (lane < V) {
+            sym = dir[lane];
+            for (int b = 0; b < V; ++b) sym |= ((dir[b] >> lane) & 1ull) << b;
+        }
+        m[lane] = sym;
+    }
+    __syncthreads();
+    if (wave == 0) count_tail(m, g, V, max_dim, lane, masks, n1, n2);
+}
+
+// one workgroup: totals against the capacity; if the batch fits, the offsets of every graph and ptr / x_ind_ptr / counts.
+// kVertexBlock: a graph's adjacencies hold the 0_0 block over the non-edges (Rips), V (V - 1) + 5 n1 + 12 n2 of them; without
+// it (kNN cliques) 6 n1 + 12 n2. A template parameter, here and in the scatter kernel: the Rips instantiations are the
+// kernels without the switch, and the kNN instantiation of the scatter carries neither the block-2 store nor its index
+// arithmetic - no wave-uniform branch in the pair loop and no register for it.
+template <bool kVertexBlock>
 __global__ __launch_bounds__(kBlock) void lift_offsets_kernel(const int* n1, const int* n2, long B, int V, int max_dim, Capacity cap,
                                                                Header* hdr, long long* row_off, long long* adj_off, int64_t* ptr,
                                                                int64_t* x_ind_ptr, int64_t* counts, unsigned* status) {
     using Scan = hipcub::BlockScan<long long, kBlock>;
     __shared__ typename Scan::TempStorage temp;
-    const long long VV = (long long)V * (V - 1);
+    const long long VV = kVertexBlock ? (long long)V * (V - 1) : 0ll;     // adjacencies of a graph = VV + per_edge n1 + 12 n2
+    const long long per_edge = kVertexBlock ? 5 : 6;
     long long N1 = 0, N2 = 0;
     for (long base = 0; base < B; base += kBlock) {
         const long g = base + threadIdx.x;
@@ -153,7 +210,7 @@ __global__ __launch_bounds__(kBlock) void lift_offsets_kernel(const int* n1, con
         __syncthreads();
         N2 += sum;
     }
-    const long long E = B * VV + 5 * N1 + 12 * N2;
+    const long long E = B * VV + per_edge * N1 + 12 * N2;
     unsigned bad = 0;
     if (N1 > cap.rows[1]) bad |= 1u << 1;
     if (max_dim >= 2 && N2 > cap.rows[2]) bad |= 1u << 2;
@@ -179,7 +236,7 @@ __global__ __launch_bounds__(kBlock) void lift_offsets_kernel(const int* n1, con
             x_ind_ptr[g] = rows + excl;
         }
         rows += sum;
-        Scan(temp).ExclusiveSum(g < B ? VV + 5 * a1 + 12 * a2 : 0ll, excl, sum);
+        Scan(temp).ExclusiveSum(g < B ? VV + per_edge * a1 + 12 * a2 : 0ll, excl, sum);
         __syncthreads();
         if (g < B) adj_off[g] = adjs + excl;
         adjs += sum;
@@ -204,12 +261,14 @@ __global__ __launch_bounds__(kBlock) void lift_offsets_kernel(const int* n1, con
 // The real part of graph g. Adjacency blocks, each at its closed-form offset behind adj_off[g] (rows offset by row_off[g]):
 //   1  0_0  for s, for the neighbours u of s ascending: (u, s)                                              2 n1
 //   2  0_0  for i, for j: (i, j) for every ordered pair i != j except the pairs i < j that are an edge      V (V - 1) - n1
+//           (kVertexBlock only: without it block 3 follows block 1)
 //   3  0_1  for every edge e = (a, b): (a, e), (b, e)                                                       2 n1
 //   4  1_0  the flips of block 3                                                                            2 n1
 //   5  1_1  for every edge s = (a, b), for the common neighbours w ascending: ({a, w}, s), ({b, w}, s)       6 n2
 //   6  1_2  for every triangle t = (a, b, c): ((a, b), t), ((a, c), t), ((b, c), t)                         3 n2
 //   7  2_1  the flips of block 6                                                                            3 n2
 // A wave takes the vertices a = wave, wave + 4, ...; its lane b holds the pair (a, b).
+template <bool kVertexBlock>
 __device__ void scatter_graph(long g, int V, int max_dim, const u64* masks, const int* n1s, const int* n2s,
                               const long long* row_off, const long long* adj_off, const Outputs& o) {
     __shared__ u64 m[kMaxVerts];
@@ -234,15 +293,15 @@ __device__ void scatter_graph(long g, int V, int max_dim, const u64* masks, cons
     }
     __syncthreads();
     const long long n1 = n1s[g], n2 = n2s[g], row0 = row_off[g], adj0 = adj_off[g];
-    const long long VV = (long long)V * (V - 1);
-    const long long o1 = adj0, o2 = o1 + 2 * n1, o3 = adj0 + VV + n1, o4 = o3 + 2 * n1, o5 = o4 + 2 * n1, o6 = o5 + 6 * n2,
+    const long long VV = kVertexBlock ? (long long)V * (V - 1) : 0ll;
+    const long long o1 = adj0, o2 = o1 + 2 * n1, o3 = kVertexBlock ? adj0 + VV + n1 : o2, o4 = o3 + 2 * n1, o5 = o4 + 2 * n1, o6 = o5 + 6 * n2,
                     o7 = o6 + 3 * n2;
     const long long e0 = row0 + V, t0 = e0 + n1;              // first edge row, first triangle row
     if (tid < V) put_row(o, row0 + tid, 0, g, tid, 0, 0);
     for (int a = wave; a < V; a += kWaves) {
         const u64 ma = m[a], up = ma & above(a), mb = m[lane];
         if ((ma >> lane) & 1ull) put_adj(o, o1 + deg_s[a] + __popcll(ma & below(lane)), row0 + lane, row0 + a, 0, 0);
-        if (lane < V && lane != a && !(lane > a && ((ma >> lane) & 1ull)))
+        if (kVertexBlock && lane < V && lane != a && !(lane > a && ((ma >> lane) & 1ull)))
             put_adj(o, o2 + (long long)a * (V - 1) - up_s[a] + lane - (lane > a ? 1 : 0) - __popcll(up & below(lane)), row0 + a,
                     row0 + lane, 0, 0);
         const bool edge = (up >> lane) & 1ull;                // the pair (a, lane), a < lane, is an edge
@@ -303,12 +362,13 @@ __device__ void scatter_fillers(long block, long n_blocks, long B, int max_dim, 
     }
 }
 
+template <bool kVertexBlock>
 __global__ __launch_bounds__(kBlock) void lift_scatter_kernel(long B, int V, int max_dim, Capacity cap, const Header* hdr,
                                                                const u64* masks, const int* n1, const int* n2, const long long* row_off,
                                                                const long long* adj_off, Outputs o) {
     if (!hdr->fit) return;
     if ((long)blockIdx.x < B)
-        scatter_graph((long)blockIdx.x, V, max_dim, masks, n1, n2, row_off, adj_off, o);
+        scatter_graph<kVertexBlock>((long)blockIdx.x, V, max_dim, masks, n1, n2, row_off, adj_off, o);
     else
         scatter_fillers((long)blockIdx.x - B, (long)gridDim.x - B, B, max_dim, cap, hdr, o);
 }
@@ -319,50 +379,67 @@ inline bool sizes_ok(int64_t n_graphs, int32_t V, int32_t max_dim) {
     return (max_dim == 1 || max_dim == 2) && V > max_dim && V <= kMaxVerts && n_graphs > 0 && n_graphs < (1ll << 31) / V;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t csmpn_rips_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim) {
-    if (!sizes_ok(n_graphs, verts_per_graph, max_dim)) return 0;
+inline size_t workspace_bytes_of(int64_t n_graphs, int32_t V, int32_t max_dim) {
+    if (!sizes_ok(n_graphs, V, max_dim)) return 0;
     const size_t B = (size_t)n_graphs;
     // alignment slack + header | masks | n1 | n2 | row offsets | adjacency offsets
-    return 256 + 256 + align256(sizeof(u64) * B * (size_t)verts_per_graph) + 2 * align256(sizeof(int) * B) +
-           2 * align256(sizeof(long long) * B);
+    return 256 + 256 + align256(sizeof(u64) * B * (size_t)V) + 2 * align256(sizeof(int) * B) + 2 * align256(sizeof(long long) * B);
 }
 
-int csmpn_rips_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, double dis, int32_t max_dim,
-                    const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
-                    int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
-                    int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const int V = verts_per_graph;
-    if (max_dim < 0) return csmpn_fail(CSMPN_ERR_INVALID, "max_dim %d is negative", (int)max_dim);
-    if (max_dim != 1 && max_dim != 2) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "rips lift: max_dim %d (1 or 2)", (int)max_dim);
-    if (V > kMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "rips lift: %d vertices per graph > %d (one 64-bit mask per vertex)", V, kMaxVerts);
-    if (V <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "rips lift: %d vertices per graph, max_dim %d needs %d", V, (int)max_dim, (int)max_dim + 1);
-    if (n_graphs <= 0 || n_graphs >= (1ll << 31) / V) return csmpn_fail(CSMPN_ERR_INVALID, "bad sizes n_graphs=%lld verts_per_graph=%d", (long long)n_graphs, V);
-    if (point_dim <= 0) return csmpn_fail(CSMPN_ERR_INVALID, "point_dim %d", (int)point_dim);
-    if (!(dis >= 0.0)) return csmpn_fail(CSMPN_ERR_INVALID, "dis %g is negative or not a number", dis);
-    if (x_ind_cols <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "x_ind has %d columns, max_dim %d needs %d", (int)x_ind_cols, (int)max_dim, (int)max_dim + 1);
-    if (!points || !capacity_rows || !x_ind || !node_types || !batch || !x_ind_batch || !ptr || !x_ind_ptr || !edge_index)
+struct LiftArgs {                // what csmpn_rips_lift and csmpn_knn_lift share
+    const float* points;
+    int32_t point_dim;
+    int64_t n_graphs;
+    int32_t verts_per_graph, max_dim;
+    const int64_t* capacity_rows;
+    int64_t capacity_edges;
+    int64_t* x_ind;
+    int32_t x_ind_cols;
+    int64_t *node_types, *batch, *x_ind_batch, *ptr, *x_ind_ptr, *edge_index, *edge_types, *counts;
+    uint32_t* status;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+};
+
+// the checks both entries share, before the first HIP call; `what` names the entry in the messages. dis >= 0: the Rips
+// threshold, knn_k: the k of the kNN entry (0 for the Rips entry) - each checked where csmpn_rips_lift has always checked dis.
+int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, bool knn, Capacity* cap) {
+    const int V = a.verts_per_graph, max_dim = a.max_dim;
+    if (max_dim < 0) return csmpn_fail(CSMPN_ERR_INVALID, "max_dim %d is negative", max_dim);
+    if (max_dim != 1 && max_dim != 2) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: max_dim %d (1 or 2)", what, max_dim);
+    if (V > kMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > %d (one 64-bit mask per vertex)", what, V, kMaxVerts);
+    if (V <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "%s: %d vertices per graph, max_dim %d needs %d", what, V, max_dim, max_dim + 1);
+    if (a.n_graphs <= 0 || a.n_graphs >= (1ll << 31) / V) return csmpn_fail(CSMPN_ERR_INVALID, "bad sizes n_graphs=%lld verts_per_graph=%d", (long long)a.n_graphs, V);
+    if (a.point_dim <= 0) return csmpn_fail(CSMPN_ERR_INVALID, "point_dim %d", (int)a.point_dim);
+    if (!knn && !(dis >= 0.0)) return csmpn_fail(CSMPN_ERR_INVALID, "dis %g is negative or not a number", dis);
+    if (knn && knn_k < 1) return csmpn_fail(CSMPN_ERR_INVALID, "%s: k = %d (at least 1)", what, knn_k);
+    if (a.x_ind_cols <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "x_ind has %d columns, max_dim %d needs %d", (int)a.x_ind_cols, max_dim, max_dim + 1);
+    if (!a.points || !a.capacity_rows || !a.x_ind || !a.node_types || !a.batch || !a.x_ind_batch || !a.ptr || !a.x_ind_ptr || !a.edge_index)
         return csmpn_fail(CSMPN_ERR_INVALID, "null pointer");
-    Capacity cap{};
     long long total = 0;
     for (int d = 0; d <= max_dim; ++d) {
-        cap.rows[d] = capacity_rows[d];
-        if (cap.rows[d] < 0 || cap.rows[d] >= (1ll << 31)) return csmpn_fail(CSMPN_ERR_INVALID, "capacity %lld of dimension %d", cap.rows[d], d);
-        total += cap.rows[d];
+        cap->rows[d] = a.capacity_rows[d];
+        if (cap->rows[d] < 0 || cap->rows[d] >= (1ll << 31)) return csmpn_fail(CSMPN_ERR_INVALID, "capacity %lld of dimension %d", cap->rows[d], d);
+        total += cap->rows[d];
     }
-    cap.edges = capacity_edges;
-    if (cap.rows[0] != n_graphs * V)
-        return csmpn_fail(CSMPN_ERR_INVALID, "capacity_rows[0] = %lld, the batch has %lld vertices (vertex rows are never padded)", cap.rows[0], (long long)(n_graphs * V));
-    if (total >= (1ll << 31) || cap.edges < 0 || cap.edges >= (1ll << 31))
-        return csmpn_fail(CSMPN_ERR_INVALID, "bad capacity: %lld rows, %lld adjacencies", total, cap.edges);
-    const size_t need = csmpn_rips_lift_workspace_bytes(n_graphs, V, max_dim);
-    if (!workspace || workspace_bytes < need) return csmpn_fail(CSMPN_ERR_INVALID, "rips lift workspace too small: %zu < %zu", workspace_bytes, need);
-    const size_t B = (size_t)n_graphs;
-    char* ws = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(workspace)));   // may cost up to 255 of the spare bytes
+    cap->edges = a.capacity_edges;
+    if (cap->rows[0] != a.n_graphs * V)
+        return csmpn_fail(CSMPN_ERR_INVALID, "capacity_rows[0] = %lld, the batch has %lld vertices (vertex rows are never padded)", cap->rows[0], (long long)(a.n_graphs * V));
+    if (total >= (1ll << 31) || cap->edges < 0 || cap->edges >= (1ll << 31))
+        return csmpn_fail(CSMPN_ERR_INVALID, "bad capacity: %lld rows, %lld adjacencies", total, cap->edges);
+    const size_t need = workspace_bytes_of(a.n_graphs, V, max_dim);
+    if (!a.workspace || a.workspace_bytes < need) return csmpn_fail(CSMPN_ERR_INVALID, "%s workspace too small: %zu < %zu", what, a.workspace_bytes, need);
+    return CSMPN_OK;
+}
+
+// Behind the argument checks: the workspace carved up, then the three launches. knn_k = 0: the masks of the pairs within
+// `dis` and the adjacencies with the vertex block (Rips); knn_k >= 1: the masks of the k nearest neighbours, no vertex block.
+int launch_lift(const char* what, const LiftArgs& a, const Capacity& cap, double dis, int knn_k) {
+    hipStream_t st = (hipStream_t)a.stream;
+    const int V = a.verts_per_graph, max_dim = a.max_dim, P = a.point_dim;
+    const size_t B = (size_t)a.n_graphs;
+    char* ws = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(a.workspace)));   // may cost up to 255 of the spare bytes
     Header* hdr = reinterpret_cast<Header*>(ws);
     ws += 256;
     u64* masks = reinterpret_cast<u64*>(ws);
@@ -374,19 +451,60 @@ int csmpn_rips_lift(const float* points, int32_t point_dim, int64_t n_graphs, in
     long long* row_off = reinterpret_cast<long long*>(ws);
     ws += align256(sizeof(long long) * B);
     long long* adj_off = reinterpret_cast<long long*>(ws);
-    Outputs out{x_ind, node_types, batch, x_ind_batch, edge_index, edge_types, (int)x_ind_cols, cap.edges};
+    Outputs out{a.x_ind, a.node_types, a.batch, a.x_ind_batch, a.edge_index, a.edge_types, (int)a.x_ind_cols, cap.edges};
     const long long fill_items = std::max(cap.rows[1] + cap.rows[2], cap.edges);
     const long fill_blocks = (long)std::min<long long>(std::max<long long>((fill_items + kBlock - 1) / kBlock, 1), kMaxFillBlocks);
-    hipLaunchKernelGGL(lift_count_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, points, (int)point_dim, V, dis * dis, (int)max_dim,
-                       masks, n1, n2);
-    hipLaunchKernelGGL(lift_offsets_kernel, dim3(1), dim3(kBlock), 0, st, (const int*)n1, (const int*)n2, (long)B, V, (int)max_dim, cap,
-                       hdr, row_off, adj_off, ptr, x_ind_ptr, counts, (unsigned*)status);
-    hipLaunchKernelGGL(lift_scatter_kernel, dim3((unsigned)(B + fill_blocks)), dim3(kBlock), 0, st, (long)B, V, (int)max_dim, cap,
-                       (const Header*)hdr, (const u64*)masks, (const int*)n1, (const int*)n2, (const long long*)row_off,
-                       (const long long*)adj_off, out);
+    const dim3 per_graph((unsigned)B), one(1), scatter((unsigned)(B + fill_blocks)), block(kBlock);
+    if (knn_k > 0) {
+        hipLaunchKernelGGL(lift_knn_kernel, per_graph, block, 0, st, a.points, P, V, knn_k, max_dim, masks, n1, n2);
+        hipLaunchKernelGGL(lift_offsets_kernel<false>, one, block, 0, st, (const int*)n1, (const int*)n2, (long)B, V, max_dim, cap, hdr,
+                           row_off, adj_off, a.ptr, a.x_ind_ptr, a.counts, (unsigned*)a.status);
+        hipLaunchKernelGGL(lift_scatter_kernel<false>, scatter, block, 0, st, (long)B, V, max_dim, cap, (const Header*)hdr,
+                           (const u64*)masks, (const int*)n1, (const int*)n2, (const long long*)row_off, (const long long*)adj_off, out);
+    } else {
+        hipLaunchKernelGGL(lift_count_kernel, per_graph, block, 0, st, a.points, P, V, dis * dis, max_dim, masks, n1, n2);
+        hipLaunchKernelGGL(lift_offsets_kernel<true>, one, block, 0, st, (const int*)n1, (const int*)n2, (long)B, V, max_dim, cap, hdr,
+                           row_off, adj_off, a.ptr, a.x_ind_ptr, a.counts, (unsigned*)a.status);
+        hipLaunchKernelGGL(lift_scatter_kernel<true>, scatter, block, 0, st, (long)B, V, max_dim, cap, (const Header*)hdr,
+                           (const u64*)masks, (const int*)n1, (const int*)n2, (const long long*)row_off, (const long long*)adj_off, out);
+    }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "rips lift kernels: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "%s kernels: %s", what, hipGetErrorString(e));
     return CSMPN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t csmpn_rips_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim) {
+    return workspace_bytes_of(n_graphs, verts_per_graph, max_dim);
+}
+
+size_t csmpn_knn_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim) {
+    return workspace_bytes_of(n_graphs, verts_per_graph, max_dim);
+}
+
+int csmpn_rips_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, double dis, int32_t max_dim,
+                    const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                    int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                    int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const LiftArgs a{points, point_dim, n_graphs, verts_per_graph, max_dim, capacity_rows, capacity_edges, x_ind, x_ind_cols, node_types,
+                     batch, x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status, workspace, workspace_bytes, stream};
+    Capacity cap{};
+    if (const int rc = check_lift_args("rips lift", a, dis, 0, false, &cap)) return rc;
+    return launch_lift("rips lift", a, cap, dis, 0);
+}
+
+int csmpn_knn_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, int32_t k, int32_t max_dim,
+                   const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                   int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                   int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const LiftArgs a{points, point_dim, n_graphs, verts_per_graph, max_dim, capacity_rows, capacity_edges, x_ind, x_ind_cols, node_types,
+                     batch, x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status, workspace, workspace_bytes, stream};
+    Capacity cap{};
+    if (const int rc = check_lift_args("knn lift", a, 0.0, (int)k, true, &cap)) return rc;
+    return launch_lift("knn lift", a, cap, 0.0, (int)k);
 }
 
 }  // extern "C"

@@ -466,6 +466,24 @@ int csmpn_rips_lift(const float* points, int32_t point_dim, int64_t n_graphs, in
                     int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
                     int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same lift of the clique complex of the k-nearest-neighbour graph: the structure tensors of exactly the batch that
+ *   pad_batch(collate([knn_clique_complex(points_g, k, max_dim) for g]), BatchCapacity(capacity_rows, capacity_edges))
+ * builds on the host. Every argument but `k`, every contract (three launches on `stream`, no allocation, no host round trip,
+ * no atomic on an output), the status bits 1..4 of a batch that does not fit (every output is left as it was), the limits
+ * and the workspace are those of csmpn_rips_lift; k < 1: CSMPN_ERR_INVALID.
+ *   With s(a, b) = sum_j ((double)p_a[j] - (double)p_b[j])^2, summed in double over j ascending (a NaN sum counts as
+ *   +infinity), the rank of b for a is the number of vertices c outside {a, b} of the graph with s(a, c) < s(a, b), or
+ *   s(a, c) == s(a, b) and c < b: ties - coincident points and NaN vertices among them - go to the smaller index. b is a
+ *   neighbour of a iff that rank is below k (k >= verts_per_graph - 1: every other vertex); {a, b} is an edge iff b is a
+ *   neighbour of a or a one of b; the 2-simplices (max_dim = 2) are the triples whose three pairs are edges.
+ * A graph's adjacencies are those of csmpn_rips_lift in its order WITHOUT the 0_0 block over the non-edges: 6 n1 + 12 n2 for
+ * n1 edges and n2 triangles. */
+size_t csmpn_knn_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim);
+int csmpn_knn_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, int32_t k, int32_t max_dim,
+                   const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                   int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                   int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fused simplex feature embedding (round 3; hulls_cssmpnn.py:96-125: vertex features of every d-simplex in all (d+1)!
  * vertex orders -> CEMLP -> sum over the orders), for the shapes the wide parity-lane kernels serve as standalone CEMLPs
  * (Cl(5,0) / Cl(4,1), 16 / 24 / 28 / 32 output channels, at most 8 input channels = verts_per_row * channels_per_vertex);

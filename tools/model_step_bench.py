@@ -18,6 +18,9 @@ JSON line with the step times and the simplices / adjacencies of the batch.
   graphed_device_lift_ms_per_step   csmpn_rips_lift + the in-place rebuild + the feature scatter + replay
   graphed_host_lifted_ms_per_step   step(batch=pre-lifted host batch) again, measured right behind it
   host_lift_ms_per_batch            rips_complex + collate + pad_batch of one batch on the host (what step(batch=...) leaves out)
+--knn K (with --device-lift, md17): the batches are the clique complexes of the K-nearest-neighbour graphs
+  (knn_clique_complex: the reference's aspirin configuration has K = 3) instead of Rips complexes, lifted on the device by
+  step(points=..., knn=K) (csmpn_knn_lift); the same four figures, and the capacity's rows / adjacencies
 --pkg-root: import the package from another tree (a build of another commit) with this same tool file; a tree without
   the capacity interface reports the eager figure only.
 """
@@ -139,12 +142,13 @@ def make_batch(args, rng, cx):
         features = ["pos", "vel", "y"]
     else:
         # MD17-shaped batch (md17_cssmpnn.py; csmpn/configs/md17.yaml: Cl(3,0), 32 channels, 5 layers): 21 atoms
-        # (aspirin), 10 frames, Vietoris-Rips complex of the first frame, random positions / velocities / charges
+        # (aspirin), 10 frames, Vietoris-Rips complex of the first frame (--knn K: the clique complex of its K-nearest-neighbour
+        # graph), random positions / velocities / charges
         V, F, graphs, dis = 21, 10, [], 1.8
         for _ in range(args.batch):
             base = (1.6 * rng.standard_normal((V, 3))).astype(np.float32)
             points.append(base)
-            c = cx.rips_complex(base, dis=dis, max_dim=2)
+            c = cx.knn_clique_complex(base, args.knn, max_dim=2) if args.knn else cx.rips_complex(base, dis=dis, max_dim=2)
             S = c.n_simplices
             loc = torch.zeros(S, F, 3); vel = torch.zeros(S, F, 3); ch = torch.zeros(S, F, 1)
             loc[:V] = torch.from_numpy(base)[:, None, :] + 0.05 * torch.from_numpy(rng.standard_normal((V, F, 3)).astype(np.float32))
@@ -158,6 +162,8 @@ def make_batch(args, rng, cx):
         features = ["loc", "vel", "charges", "y"]
     if points:
         batch.lift_points, batch.lift_dis = np.concatenate(points, axis=0), dis
+        if args.knn:
+            batch.lift_knn = args.knn
     return batch, features
 
 
@@ -218,7 +224,9 @@ def device_lift(args, out, cx, gs, batches, features, cap, dev):
     replay - beside step(batch=pre-lifted host batch) of the same run, and what the host lift of such a batch costs."""
     if not hasattr(gs, "load_points") or not hasattr(batches[0], "lift_points"):
         raise SystemExit("--device-lift needs a Rips model (md17, motion, nba) and a tree with the device lift")
-    K, dis = len(batches), batches[0].lift_dis
+    K, dis, knn = len(batches), batches[0].lift_dis, getattr(batches[0], "lift_knn", None)
+    how = dict(dis=dis) if knn is None else dict(knn=knn)
+    host = (lambda g: cx.rips_complex(g, dis=dis, max_dim=2)) if knn is None else (lambda g: cx.knn_clique_complex(g, knn, max_dim=2))
     names = [k for k in features if k != "y"]
     on_dev = []
     for b in batches:
@@ -227,7 +235,7 @@ def device_lift(args, out, cx, gs, batches, features, cap, dev):
 
     def lifted(i):
         pts, vf, y = on_dev[i % K]
-        return gs.step(features={"y": y}, points=pts, vertex_features=vf, dis=dis)
+        return gs.step(features={"y": y}, points=pts, vertex_features=vf, **how)
 
     out["graphed_device_lift_ms_per_step"] = round(timed(lifted, args.steps), 3)
     out["graphed_host_lifted_ms_per_step"] = round(timed(lambda i: gs.step(batch=batches[i % K]), args.steps), 3)
@@ -235,7 +243,7 @@ def device_lift(args, out, cx, gs, batches, features, cap, dev):
     t0 = time.perf_counter()
     for b in batches:
         p = b.lift_points.reshape(b.num_graphs, -1, b.lift_points.shape[-1])
-        cx.pad_batch(cx.collate([cx.rips_complex(g, dis=dis, max_dim=2) for g in p]), cap)
+        cx.pad_batch(cx.collate([host(g) for g in p]), cap)
     out["host_lift_ms_per_batch"] = round((time.perf_counter() - t0) * 1e3 / K, 3)
 
 
@@ -253,8 +261,11 @@ def main():
     ap.add_argument("--varying", type=int, default=0, metavar="K", help="K batches of different topology: the eager loop on fresh device batches against ONE captured step with a capacity")
     ap.add_argument("--slack", type=float, default=0.0, help="--varying: capacity_of(batches, slack)")
     ap.add_argument("--device-lift", action="store_true", help="--varying: also step(points=...), the complexes lifted on the device, and the host time of the lift")
+    ap.add_argument("--knn", type=int, default=0, metavar="K", help="--device-lift, md17: clique complexes of the K-nearest-neighbour graphs instead of Rips complexes")
     ap.add_argument("--pkg-root", default=None, help="import the package from this tree instead of the tool's own")
     args = ap.parse_args()
+    if args.knn and (args.model != "md17" or not args.device_lift or args.knn < 1):
+        raise SystemExit("--knn K (K >= 1) goes with --model md17 --varying ... --device-lift")
     if args.pkg_root:
         sys.path.insert(0, os.path.abspath(args.pkg_root))
     importlib.import_module(PKG)
