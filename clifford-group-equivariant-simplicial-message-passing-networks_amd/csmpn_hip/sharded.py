@@ -28,6 +28,7 @@ the bytes of A, and both collectives use all xGMI links at once.
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -36,11 +37,109 @@ import torch.distributed as dist
 from . import ops
 
 
-def shard_bounds(n_edges: int, world: int, rank: int):
-    """Contiguous, balanced shard [lo, hi) of the edge list for `rank`."""
-    base, rem = divmod(n_edges, world)
+def shard_bounds(n: int, world: int, rank: int):
+    """Contiguous, balanced part [lo, hi) of `n` items (the edge list) for `rank`: the first n % world parts are one longer."""
+    base, rem = divmod(n, world)
     lo = rank * base + min(rank, rem)
     return lo, lo + base + (1 if rank < rem else 0)
+
+
+node_bounds = shard_bounds     # partitioning B without balancing: the same cut of the node range
+
+
+# ===================================================================================== bookkeeping shared by both partitionings
+
+
+def _split_params(spec, lp):
+    """A layer's flat parameter list -> (edge-model part, node-model part)."""
+    ne = spec.edge.nblk * ops.NP
+    return lp[:ne], lp[ne:]
+
+
+def _offsets(counts):
+    """[0, c0, c0 + c1, ...]: where every layer's parameters start in the flat list of a chain."""
+    offs = [0]
+    for cnt in counts:
+        offs.append(offs[-1] + cnt)
+    return offs
+
+
+def _acc(a, b):
+    """a + b where either may be None."""
+    return b if a is None else (a if b is None else a + b)
+
+
+def _save(ctx, tensors, optional, params, counts=()):
+    """What a Function keeps for its backward: `tensors`, the entries of `optional` (the attributes) and of `params` that
+    are not None, and the per-layer parameter offsets of a chain."""
+    ctx.n_tensors = len(tensors)
+    ctx.has = [t is not None for t in optional]
+    ctx.mask = [p is not None for p in params]
+    ctx.offs = _offsets(counts)
+    ctx.save_for_backward(*tensors, *[t for t in optional if t is not None], *[p for p in params if p is not None])
+
+
+def _restore(ctx):
+    """(tensors, optional, params) as given to _save, None where None was given."""
+    it = iter(ctx.saved_tensors)
+    tensors = [next(it) for _ in range(ctx.n_tensors)]
+    optional = [next(it) if m else None for m in ctx.has]
+    return tensors, optional, [next(it) if m else None for m in ctx.mask]
+
+
+def _pack(views, lead=None):
+    """[lead | the views that are not None] as one flat tensor."""
+    return torch.cat(([] if lead is None else [lead.reshape(-1)]) + [v.reshape(-1) for v in views if v is not None])
+
+
+def _cut_views(flat, shapes, off=0):
+    """Views of `flat` laid end to end from `off`, one per shape (None stays None): the inverse of _pack."""
+    out = []
+    for shp in shapes:
+        if shp is None:
+            out.append(None)
+        else:
+            cnt = math.prod(shp)
+            out.append(flat[off:off + cnt].view(shp))
+            off += cnt
+    return out
+
+
+def _all_reduce_views(views, group, lead=None):
+    """ONE all-reduce (sum) of [lead | views] as a flat tensor -> (reduced lead, views of the result)."""
+    if lead is None and all(v is None for v in views):
+        return None, views
+    flat = _pack(views, lead)
+    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+    off = 0 if lead is None else lead.numel()
+    return (None if lead is None else flat[:off].view_as(lead),
+            _cut_views(flat, [None if v is None else v.shape for v in views], off))
+
+
+class _Capture:
+    """HIP-graph capture of a step's segments. The constructor runs `warm_up` once on a side stream, outside capture
+    (kernel attributes, workspaces, allocator); every call then captures one function into a graph of its own, all in one
+    memory pool, and returns (graph, what the function returned). Thread-local capture mode: the process group's
+    watchdog thread polls events while we capture."""
+
+    def __init__(self, warm_up):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            warm_up()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.pool = None
+
+    def __call__(self, fn):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self.pool, capture_error_mode="thread_local"):
+            res = fn()
+        self.pool = self.pool or g.pool()
+        return g, res
+
+
+# ===================================================================================== partitioning A
 
 
 class ShardPlan:
@@ -55,63 +154,47 @@ class ShardPlan:
         self.n_nodes = n_nodes
 
 
+def _shard_backward(be, spec, plan: ShardPlan, h, agg, attrs, lp, gout, want, st):
+    """Backward of the edge-sharded layer up to its collective: node backward on all nodes (replicated), edge backward
+    on the shard. attrs = (edge_attr, node_attr), want = (d/d edge_attr?, d/d node_attr?), st = (edge, node) states.
+    -> d/dh of the node stage, partial d/dh of the shard's edges, d/d edge_attr, d/d node_attr, edge-model and node-model
+    parameter gradients. (Its forward is one backend call on either side of the all-reduce of agg: nothing to share.)"""
+    pe, pn = _split_params(spec, lp)
+    gh_node, g_agg, g_na, views_n = be.node_backward(spec, plan.deg, h, agg, attrs[1], pn, gout, want[1], st[1])
+    # partial d/dh of this shard starts from zero so that the all-reduce sums shards only
+    gh_edge = torch.zeros_like(h)
+    g_ea, views_e = be.edge_backward(spec, plan.csr, h, attrs[0], pe, g_agg, gh_edge, want[0], st[0])
+    return gh_node, gh_edge, g_ea, g_na, views_e, views_n
+
+
 class _ShardedEgclFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, edge_attr, node_attr, spec, plan: ShardPlan, backend, group, *params):
         h = h.contiguous()
-        ne = spec.edge.nblk * ops.NP
-        pe, pn = params[:ne], params[ne:]
+        pe, pn = _split_params(spec, params)
         agg, st_e = backend.edge_forward(spec, plan.csr, h, edge_attr, pe)
         if _multi(group):
             dist.all_reduce(agg, op=dist.ReduceOp.SUM, group=group)
         out, st_n = backend.node_forward(spec, plan.deg, h, agg, node_attr, pn)
-        ctx.st_e, ctx.st_n = st_e, st_n
+        ctx.st = (st_e, st_n)
         ctx.spec, ctx.plan, ctx.backend, ctx.group = spec, plan, backend, group
-        ctx.has_ea, ctx.has_na = edge_attr is not None, node_attr is not None
-        ctx.mask = [p is not None for p in params]
-        saved = [h, agg] + ([edge_attr] if ctx.has_ea else []) + ([node_attr] if ctx.has_na else [])
-        ctx.save_for_backward(*saved, *[p for p in params if p is not None])
+        _save(ctx, [h, agg], [edge_attr, node_attr], params)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        spec, plan, backend, group = ctx.spec, ctx.plan, ctx.backend, ctx.group
-        saved = list(ctx.saved_tensors)
-        h, agg = saved[0], saved[1]
-        pos = 2
-        edge_attr = node_attr = None
-        if ctx.has_ea:
-            edge_attr = saved[pos]; pos += 1
-        if ctx.has_na:
-            node_attr = saved[pos]; pos += 1
-        it = iter(saved[pos:])
-        params = [next(it) if m else None for m in ctx.mask]
-        ne = spec.edge.nblk * ops.NP
-        pe, pn = params[:ne], params[ne:]
-        gout = gout.contiguous()
-        gh_node, g_agg, g_na, views_n = backend.node_backward(spec, plan.deg, h, agg, node_attr, pn, gout,
-                                                              ctx.needs_input_grad[2], ctx.st_n)
-        # partial d/dh of this shard starts from zero so that the all-reduce sums shards only
-        gh_edge = torch.zeros_like(h)
-        g_ea, views_e = backend.edge_backward(spec, plan.csr, h, edge_attr, pe, g_agg, gh_edge,
-                                              ctx.needs_input_grad[1], ctx.st_e)
-        if _multi(group):
+        (h, agg), attrs, params = _restore(ctx)
+        gh_node, gh_edge, g_ea, g_na, views_e, views_n = _shard_backward(
+            ctx.backend, ctx.spec, ctx.plan, h, agg, attrs, params, gout.contiguous(), ctx.needs_input_grad[1:3], ctx.st)
+        if _multi(ctx.group):
             # one collective: [d/dh | edge-model parameter gradients]
-            pieces = [gh_edge.reshape(-1)] + [v.reshape(-1) for v in views_e if v is not None]
-            packed = torch.cat(pieces)
-            dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
-            off = gh_edge.numel()
-            gh_edge = packed[:off].view_as(h)
-            out_views = []
-            for v in views_e:
-                if v is None:
-                    out_views.append(None)
-                else:
-                    out_views.append(packed[off:off + v.numel()].view(v.shape))
-                    off += v.numel()
-            views_e = out_views
+            gh_edge, views_e = _all_reduce_views(views_e, ctx.group, lead=gh_edge)
         gh = gh_node + gh_edge
         return (gh, g_ea, g_na, None, None, None, None, *views_e, *views_n)
+
+
+def _layer_params(layer):
+    return layer.edge_model.flat_params() + layer.node_model.flat_params()
 
 
 class ShardedEGCL(torch.nn.Module):
@@ -127,10 +210,8 @@ class ShardedEGCL(torch.nn.Module):
         return ShardPlan(edge_index_local, n_nodes, self.backend, self.group)
 
     def forward(self, h, plan: ShardPlan, edge_attr_local=None, node_attr=None):
-        layer = self.layer
-        params = layer.edge_model.flat_params() + layer.node_model.flat_params()
-        return _ShardedEgclFn.apply(h, edge_attr_local, node_attr, layer.spec(), plan, self.backend, self.group,
-                                    *params)
+        return _ShardedEgclFn.apply(h, edge_attr_local, node_attr, self.layer.spec(), plan, self.backend, self.group,
+                                    *_layer_params(self.layer))
 
 
 class GraphedShardedStep:
@@ -162,7 +243,6 @@ class GraphedShardedStep:
         # shard (targets < N/2 | >= N/2), so that the all-reduce of the first half of the aggregate
         # travels while the second half is still being computed. Needs the saved block inputs to be
         # one [rows, O, D] array (two-block edge model) and the default backend.
-        import os
         self._split = None
         if (self._multi and be is ops.HipBackend and spec.edge.nblk == 2
                 and os.environ.get("CSMPN_SPLIT_FWD", "1") != "0"):
@@ -195,39 +275,27 @@ class GraphedShardedStep:
 
         def part2(agg, st_e):
             out, st_n = be.node_forward(spec, plan.deg, h_, agg, na, pn)
-            gh_node, g_agg, _g_na, views_n = be.node_backward(spec, plan.deg, h_, agg, na, pn, self.gout, False, st_n)
-            gh_edge = torch.zeros_like(h_)
-            _g_ea, views_e = be.edge_backward(spec, plan.csr, h_, ea, pe, g_agg, gh_edge, False, st_e)
-            packed = torch.cat([gh_edge.reshape(-1)] + [v.reshape(-1) for v in views_e if v is not None])
-            return out, gh_node, packed, views_e, views_n
+            gh_node, gh_edge, _g_ea, _g_na, views_e, views_n = _shard_backward(
+                be, spec, plan, h_, agg, (ea, na), pe + pn, self.gout, (False, False), (st_e, st_n))
+            return out, gh_node, _pack(views_e, lead=gh_edge), views_e, views_n
 
-        # warm-up outside capture (kernel attributes, workspaces, allocator)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        def warm_up():
             if self._split:
                 agg, st_e, per_row = part1_lo()
                 part1_hi(agg, st_e[1], per_row)
             else:
                 agg, st_e = part1()
             part2(agg, st_e)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
 
-        self.g1, self.g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        # thread-local capture mode: the process group's watchdog thread polls events while we capture
+        capture = _Capture(warm_up)
         self.g1b = None
-        with torch.cuda.graph(self.g1, capture_error_mode="thread_local"):
-            if self._split:
-                self.agg, self._st_e, per_row = part1_lo()
-            else:
-                self.agg, self._st_e = part1()
         if self._split:
-            self.g1b = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g1b, pool=self.g1.pool(), capture_error_mode="thread_local"):
-                part1_hi(self.agg, self._st_e[1], per_row)
-        with torch.cuda.graph(self.g2, pool=self.g1.pool(), capture_error_mode="thread_local"):
-            self.out, self.gh_node, self.packed, views_e, self.views_n = part2(self.agg, self._st_e)
+            self.g1, (self.agg, self._st_e, per_row) = capture(part1_lo)
+            self.g1b, _ = capture(lambda: part1_hi(self.agg, self._st_e[1], per_row))
+        else:
+            self.g1, (self.agg, self._st_e) = capture(part1)
+        self.g2, (self.out, self.gh_node, self.packed, views_e, self.views_n) = capture(
+            lambda: part2(self.agg, self._st_e))
         self._edge_shapes = [None if v is None else tuple(v.shape) for v in views_e]
         self.gh = torch.empty_like(h_)
 
@@ -250,27 +318,10 @@ class GraphedShardedStep:
 
     def results(self):
         """(out, d/dh, edge-model parameter gradients, node-model parameter gradients) of the last run()."""
-        off, views_e = self.h.numel(), []
-        for shp in self._edge_shapes:
-            if shp is None:
-                views_e.append(None)
-            else:
-                cnt = 1
-                for s in shp:
-                    cnt *= s
-                views_e.append(self.packed[off:off + cnt].view(shp))
-                off += cnt
-        return self.out, self.gh, views_e, list(self.views_n)
+        return self.out, self.gh, _cut_views(self.packed, self._edge_shapes, self.h.numel()), list(self.views_n)
 
 
 # ===================================================================================== partitioning B
-
-
-def node_bounds(n_nodes: int, world: int, rank: int):
-    """Equal-width node slice of `rank` (the last slices are one shorter when N does not divide by the world size)."""
-    base, rem = divmod(n_nodes, world)
-    lo = rank * base + min(rank, rem)
-    return lo, lo + base + (1 if rank < rem else 0)
 
 
 def balanced_node_cuts(in_degree: torch.Tensor, world: int, boundaries=None):
@@ -350,52 +401,40 @@ def _fused_collectives(group) -> bool:
     return "nccl" in str(dist.get_backend(group)).lower()
 
 
-def _all_gather_rows(full, part, group):
-    """full[W * n] <- concat over ranks of part[n] (rows)."""
-    if _fused_collectives(group):
-        dist.all_gather_into_tensor(full, part, group=group)
-    else:
-        chunks = list(full.chunk(dist.get_world_size(group), dim=0))
-        dist.all_gather(chunks, part, group=group)
-
-
-def _reduce_scatter_rows(part, full, group):
-    """part[n] <- this rank's row slice of the sum over ranks of full[W * n]."""
-    if _fused_collectives(group):
-        dist.reduce_scatter_tensor(part, full, op=dist.ReduceOp.SUM, group=group)
-    else:   # gloo has no reduce-scatter: all-reduce and slice
-        dist.all_reduce(full, op=dist.ReduceOp.SUM, group=group)
-        w, r = dist.get_world_size(group), dist.get_rank(group)
-        part.copy_(full.chunk(w, dim=0)[r])
-
-
 class _Pending:
     """Handle of a collective in flight (async_op=True): wait() orders the current stream behind it, then runs the
-    epilogue the blocking form would have run (gloo's reduce-scatter stand-in slices the all-reduced rows)."""
+    epilogue of the collective (gloo's reduce-scatter stand-in slices the all-reduced rows). The blocking forms go
+    through wait() too; their work object is None."""
 
-    def __init__(self, works, epilogue=None):
-        self.works, self.epilogue = works, epilogue
+    def __init__(self, work, epilogue=None):
+        self.work, self.epilogue = work, epilogue
 
     def wait(self):
-        for w in self.works:
-            w.wait()
+        if self.work is not None:
+            self.work.wait()
         if self.epilogue is not None:
             self.epilogue()
 
 
-def _all_gather_rows_async(full, part, group) -> _Pending:
+def _all_gather_rows(full, part, group, async_op=False):
+    """full[W * n] <- concat over ranks of part[n] (rows). async_op=True: returns the _Pending to wait for."""
     if _fused_collectives(group):
-        return _Pending([dist.all_gather_into_tensor(full, part, group=group, async_op=True)])
-    chunks = list(full.chunk(dist.get_world_size(group), dim=0))
-    return _Pending([dist.all_gather(chunks, part, group=group, async_op=True)])
+        pending = _Pending(dist.all_gather_into_tensor(full, part, group=group, async_op=async_op))
+    else:
+        chunks = list(full.chunk(dist.get_world_size(group), dim=0))
+        pending = _Pending(dist.all_gather(chunks, part, group=group, async_op=async_op))
+    return pending if async_op else pending.wait()
 
 
-def _reduce_scatter_rows_async(part, full, group) -> _Pending:
+def _reduce_scatter_rows(part, full, group, async_op=False):
+    """part[n] <- this rank's row slice of the sum over ranks of full[W * n]. async_op=True: returns the _Pending."""
     if _fused_collectives(group):
-        return _Pending([dist.reduce_scatter_tensor(part, full, op=dist.ReduceOp.SUM, group=group, async_op=True)])
-    w, r = dist.get_world_size(group), dist.get_rank(group)
-    return _Pending([dist.all_reduce(full, op=dist.ReduceOp.SUM, group=group, async_op=True)],
-                    lambda: part.copy_(full.chunk(w, dim=0)[r]))
+        pending = _Pending(dist.reduce_scatter_tensor(part, full, op=dist.ReduceOp.SUM, group=group, async_op=async_op))
+    else:   # gloo has no reduce-scatter: all-reduce and slice
+        w, r = dist.get_world_size(group), dist.get_rank(group)
+        pending = _Pending(dist.all_reduce(full, op=dist.ReduceOp.SUM, group=group, async_op=async_op),
+                           lambda: part.copy_(full.chunk(w, dim=0)[r]))
+    return pending if async_op else pending.wait()
 
 
 def agree_all(local_ok: bool, group=None, device=None) -> bool:
@@ -497,91 +536,163 @@ class DstPlan:
         return padded.index_select(0, self.pos_of_node)
 
 
+class _Own:
+    """What the stages of partitioning B read of this rank's slice: its bounds, the CSR of the owned edges, and the
+    in-degree and node_attr rows of [lo, hi)."""
+
+    def __init__(self, plan: DstPlan, node_attr):
+        self.lo, self.hi, self.csr = plan.lo, plan.hi, plan.csr
+        self.na = None if node_attr is None else node_attr[self.lo:self.hi].contiguous()
+        self.deg = plan.deg[self.lo:self.hi].contiguous()
+
+
+def _dst_node_forward(be, spec, own: _Own, x, agg, pn):
+    """Node update of the owned slice -> (out_loc [hi - lo, ...], node state)."""
+    lo, hi = own.lo, own.hi
+    return be.node_forward(spec, own.deg, x[lo:hi].contiguous(), agg[lo:hi].contiguous(), own.na, pn)
+
+
+def _dst_forward(be, spec, own: _Own, x, edge_attr, lp):
+    """Forward of ONE destination-partitioned layer on this rank's slice, x [N, C, D] replicated in: edge stage on the
+    owned edges, node update of the owned nodes -> (agg, out_loc, (edge state, node state)). No collective."""
+    pe, pn = _split_params(spec, lp)
+    agg, st_e = be.edge_forward(spec, own.csr, x, edge_attr, pe)      # complete on [lo, hi)
+    out_loc, st_n = _dst_node_forward(be, spec, own, x, agg, pn)
+    return agg, out_loc, (st_e, st_n)
+
+
+def _dst_node_backward(be, spec, own: _Own, x, agg, pn, g_loc, want_gna, st_n):
+    """Node backward on the slice, g_loc = d/d(output slice) -> (d/dh of the node stage [hi - lo], d/d agg [N] (zero
+    outside the slice), d/d node_attr of the slice, node-model parameter gradients)."""
+    lo, hi = own.lo, own.hi
+    gh_node, g_agg_loc, g_na_loc, views_n = be.node_backward(
+        spec, own.deg, x[lo:hi].contiguous(), agg[lo:hi].contiguous(), own.na, pn, g_loc, want_gna, st_n)
+    g_agg = torch.zeros_like(agg)
+    g_agg[lo:hi] = g_agg_loc
+    return gh_node, g_agg, g_na_loc, views_n
+
+
+def _dst_backward(be, spec, own: _Own, x, agg, edge_attr, lp, g_loc, want, st):
+    """Backward of ONE destination-partitioned layer up to its collectives. want = (d/d edge_attr?, d/d node_attr?),
+    st = what _dst_forward returned. -> (d/dh of the node stage [hi - lo], d/dh of the edge stage [N]: rows of any rank,
+    d/d edge_attr, d/d node_attr of the slice, the layer's parameter gradients in flat_params() order)."""
+    pe, pn = _split_params(spec, lp)
+    gh_node, g_agg, g_na_loc, views_n = _dst_node_backward(be, spec, own, x, agg, pn, g_loc, want[1], st[1])
+    gh_edge = torch.zeros_like(x)          # +g -> owned targets, -g -> any source
+    g_ea, views_e = be.edge_backward(spec, own.csr, x, edge_attr, pe, g_agg, gh_edge, want[0], st[0])
+    return gh_node, gh_edge, g_ea, g_na_loc, list(views_e) + list(views_n)
+
+
+def _all_gather_slices(plan: DstPlan, rows_loc, group):
+    """[hi - lo, ...] of every rank -> [N, ...] replicated (through the padded layout)."""
+    padded = rows_loc.new_empty((plan.world * plan.per,) + tuple(rows_loc.shape[1:]))
+    _all_gather_rows(padded, plan.pad_slice(rows_loc), group)
+    return plan.from_padded(padded)
+
+
 class _DstPartStackFn(torch.autograd.Function):
     """L chained EGCL layers, destination-partitioned. h [N, C, D] replicated in, the last layer's output replicated out.
     Forward, per layer: edge stage on the owned edges -> node update of the owned slice -> ONE all-gather. Backward, per
     layer: node backward on the slice -> edge backward on the owned edges -> ONE reduce-scatter of d/dh, whose result
     (+ the node stage's d/dh) is exactly the slice of d/d(previous layer's output) the next step needs - no all-gather
     between chained layers; the replicated d/dh of the chain's input is all-gathered once, if anybody asks for it. The
-    parameter gradients of all layers travel in ONE all-reduce."""
+    parameter gradients of all layers travel in ONE all-reduce.
+
+    overlap=True (world > 1) hides the collectives of the chain under edge work. Every layer's edge stage runs in two
+    launches: the owned edges whose source is owned too (they read rows of the own slice only) and the rest.
+    Forward: the all-gather of layer k's output slice is in flight while layer k + 1 runs its local-source edges on the
+    slice it already has; the remote-source edges follow the wait. Backward: the remote-source edges go first, the
+    reduce-scatter of THEIR d/dh (the only part with rows of other ranks) travels while the local-source edges run; the
+    local part lands on owned rows and is added behind the wait. Same results as the blocking chain up to the order of
+    two float additions per row. The two forms differ in the edge launches and in where the collectives are waited for,
+    and in nothing else."""
 
     @staticmethod
-    def forward(ctx, h, edge_attr_local, node_attr, specs, plan: DstPlan, backend, group, counts, *params):
+    def forward(ctx, h, edge_attr_local, node_attr, specs, plan: DstPlan, backend, group, counts, overlap, *params):
         lo, hi = plan.lo, plan.hi
-        na_loc = None if node_attr is None else node_attr[lo:hi].contiguous()
-        deg_loc = plan.deg[lo:hi].contiguous()
+        eas = (edge_attr_local,)
+        if overlap:
+            csr_l, csr_r = plan.split()
+            eas = tuple(None if edge_attr_local is None else edge_attr_local.index_select(0, idx)
+                        for idx in (plan.idx_loc, plan.idx_rem))
+        own = _Own(plan, node_attr)
+        offs = _offsets(counts)
         hs, aggs, st = [], [], []
         x = h.contiguous()
-        off = 0
-        for spec, cnt in zip(specs, counts):
-            lp = params[off:off + cnt]
-            off += cnt
-            ne = spec.edge.nblk * ops.NP
-            pe, pn = lp[:ne], lp[ne:]
-            agg, st_e = backend.edge_forward(spec, plan.csr, x, edge_attr_local, pe)      # complete on [lo, hi)
-            out_loc, st_n = backend.node_forward(spec, deg_loc, x[lo:hi].contiguous(), agg[lo:hi].contiguous(), na_loc, pn)
-            hs.append(x); aggs.append(agg); st.append((st_e, st_n))
-            if plan.multi:
-                padded = out_loc.new_empty((plan.world * plan.per,) + tuple(out_loc.shape[1:]))
-                _all_gather_rows(padded, plan.pad_slice(out_loc), group)
-                x = plan.from_padded(padded)
+        pending, padded, x_own = None, None, None
+        for k, spec in enumerate(specs):
+            lp = params[offs[k]:offs[k + 1]]
+            if overlap:
+                pe, pn = _split_params(spec, lp)
+                # rows outside [lo, hi) of x_own are never read by the local-source edges
+                agg_l, st_l = backend.edge_forward(spec, csr_l, x if pending is None else x_own, eas[0], pe)
+                if pending is not None:
+                    pending.wait()
+                    x = plan.from_padded(padded)
+                agg_r, st_r = backend.edge_forward(spec, csr_r, x, eas[1], pe)
+                agg = agg_l + agg_r                                                   # complete on [lo, hi)
+                out_loc, st_n = _dst_node_forward(backend, spec, own, x, agg, pn)
+                st_k = ((st_l, st_r), st_n)
             else:
-                x = out_loc
+                agg, out_loc, st_k = _dst_forward(backend, spec, own, x, eas[0], lp)
+            hs.append(x); aggs.append(agg); st.append(st_k)
+            if overlap:
+                padded = out_loc.new_empty((plan.world * plan.per,) + tuple(out_loc.shape[1:]))
+                pending = _all_gather_rows(padded, plan.pad_slice(out_loc), group, async_op=True)
+                x_own = out_loc.new_zeros((plan.n_nodes,) + tuple(out_loc.shape[1:]))
+                x_own[lo:hi] = out_loc
+            else:
+                x = _all_gather_slices(plan, out_loc, group) if plan.multi else out_loc
+        if overlap:
+            pending.wait()
+            x = plan.from_padded(padded)
         ctx.st = st
-        ctx.specs, ctx.plan, ctx.backend, ctx.group, ctx.counts = specs, plan, backend, group, counts
-        ctx.has_ea, ctx.has_na = edge_attr_local is not None, node_attr is not None
-        ctx.mask = [p is not None for p in params]
-        ctx.n_layers = len(specs)
-        saved = hs + aggs + ([edge_attr_local] if ctx.has_ea else []) + ([node_attr] if ctx.has_na else [])
-        ctx.save_for_backward(*saved, *[p for p in params if p is not None])
+        ctx.specs, ctx.plan, ctx.backend, ctx.group, ctx.overlap = specs, plan, backend, group, overlap
+        _save(ctx, hs + aggs, [*eas, node_attr], params, counts)
         return x
 
     @staticmethod
     def backward(ctx, gout):
-        specs, plan, backend, group, counts = ctx.specs, ctx.plan, ctx.backend, ctx.group, ctx.counts
-        L = ctx.n_layers
-        saved = list(ctx.saved_tensors)
-        hs, aggs = saved[:L], saved[L:2 * L]
-        pos = 2 * L
-        edge_attr = node_attr = None
-        if ctx.has_ea:
-            edge_attr = saved[pos]; pos += 1
-        if ctx.has_na:
-            node_attr = saved[pos]; pos += 1
-        it = iter(saved[pos:])
-        params = [next(it) if m else None for m in ctx.mask]
+        specs, plan, backend, group, overlap, offs = ctx.specs, ctx.plan, ctx.backend, ctx.group, ctx.overlap, ctx.offs
+        L = len(specs)
+        saved, (*eas, node_attr), params = _restore(ctx)
+        hs, aggs = saved[:L], saved[L:]
         lo, hi = plan.lo, plan.hi
-        na_loc = None if node_attr is None else node_attr[lo:hi].contiguous()
-        deg_loc = plan.deg[lo:hi].contiguous()
-        offs = [0]
-        for cnt in counts:
-            offs.append(offs[-1] + cnt)
+        if overlap:
+            csr_l, csr_r = plan.split()
+        own = _Own(plan, node_attr)
+        want = ctx.needs_input_grad[1:3]
         g_loc = gout[lo:hi].contiguous()          # d/d(output slice) of the layer being processed
         views_all = [None] * len(params)
-        g_ea_total, g_na_loc_total = None, None
+        g_ea_total, g_na_loc_total = [None] * len(eas), None      # d/d edge_attr: one total per edge launch
         gh_full_single = None
         for k in range(L - 1, -1, -1):
-            spec = specs[k]
+            spec, h, agg = specs[k], hs[k], aggs[k]
             lp = params[offs[k]:offs[k + 1]]
-            ne = spec.edge.nblk * ops.NP
-            pe, pn = lp[:ne], lp[ne:]
-            h, agg = hs[k], aggs[k]
-            st_e, st_n = ctx.st[k]
-            gh_node, g_agg_loc, g_na_loc, views_n = backend.node_backward(
-                spec, deg_loc, h[lo:hi].contiguous(), agg[lo:hi].contiguous(), na_loc, pn, g_loc,
-                ctx.needs_input_grad[2], st_n)
-            g_agg = torch.zeros_like(agg)
-            g_agg[lo:hi] = g_agg_loc
-            gh_edge = torch.zeros_like(h)          # +g -> owned targets, -g -> any source
-            g_ea, views_e = backend.edge_backward(spec, plan.csr, h, edge_attr, pe, g_agg, gh_edge,
-                                                  ctx.needs_input_grad[1], st_e)
-            for i, v in enumerate(list(views_e) + list(views_n)):
+            if overlap:
+                pe, pn = _split_params(spec, lp)
+                (st_l, st_r), st_n = ctx.st[k]
+                gh_node, g_agg, g_na_loc, views_n = _dst_node_backward(backend, spec, own, h, agg, pn, g_loc, want[1], st_n)
+                gh_r = torch.zeros_like(h)             # +g -> owned targets, -g -> sources on OTHER ranks
+                g_ea_r, views_r = backend.edge_backward(spec, csr_r, h, eas[1], pe, g_agg, gh_r, want[0], st_r)
+                g_pad = gh_r.new_empty((plan.per,) + tuple(gh_r.shape[1:]))
+                pending = _reduce_scatter_rows(g_pad, plan.to_padded(gh_r), group, async_op=True)
+                gh_l = torch.zeros_like(h)             # both ends owned: rows of [lo, hi) only
+                g_ea_l, views_l = backend.edge_backward(spec, csr_l, h, eas[0], pe, g_agg, gh_l, want[0], st_l)
+                g_eas = (g_ea_l, g_ea_r)
+                views = [_acc(a, b) for a, b in zip(views_l, views_r)] + list(views_n)
+            else:
+                gh_node, gh_edge, g_ea, g_na_loc, views = _dst_backward(backend, spec, own, h, agg, eas[0], lp, g_loc,
+                                                                        want, ctx.st[k])
+                g_eas = (g_ea,)
+            for i, v in enumerate(views):
                 views_all[offs[k] + i] = v
-            if g_ea is not None:
-                g_ea_total = g_ea if g_ea_total is None else g_ea_total + g_ea
-            if g_na_loc is not None:
-                g_na_loc_total = g_na_loc if g_na_loc_total is None else g_na_loc_total + g_na_loc
-            if plan.multi:
+            g_ea_total = [_acc(t, g) for t, g in zip(g_ea_total, g_eas)]
+            g_na_loc_total = _acc(g_na_loc_total, g_na_loc)
+            if overlap:
+                pending.wait()
+                g_loc = g_pad[:hi - lo] + gh_l[lo:hi] + gh_node
+            elif plan.multi:
                 g_pad = gh_edge.new_empty((plan.per,) + tuple(gh_edge.shape[1:]))
                 _reduce_scatter_rows(g_pad, plan.to_padded(gh_edge), group)
                 g_loc = g_pad[:hi - lo] + gh_node
@@ -591,224 +702,71 @@ class _DstPartStackFn(torch.autograd.Function):
                 g_loc = gh_edge[lo:hi]
         gh = None
         if ctx.needs_input_grad[0]:
-            if plan.multi:
-                padded = g_loc.new_empty((plan.world * plan.per,) + tuple(g_loc.shape[1:]))
-                _all_gather_rows(padded, plan.pad_slice(g_loc), group)
-                gh = plan.from_padded(padded)
-            else:
-                gh = gh_full_single
-        g_na = None
+            gh = _all_gather_slices(plan, g_loc, group) if plan.multi else gh_full_single
+        g_ea = g_ea_total[0]
+        if overlap and any(t is not None for t in g_ea_total):     # the two launches' rows back in the caller's order
+            ref = g_ea_total[0] if g_ea_total[0] is not None else g_ea_total[1]
+            g_ea = ref.new_zeros((plan.edge_ids.numel(),) + tuple(ref.shape[1:]))
+            for idx, t in zip((plan.idx_loc, plan.idx_rem), g_ea_total):
+                if t is not None:
+                    g_ea[idx] = t
+        g_na = g_na_loc_total
         if plan.multi:
-            live = [v for v in views_all if v is not None]
-            if live:
-                flat = torch.cat([v.reshape(-1) for v in live])
-                dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
-                off, red = 0, []
-                for v in views_all:
-                    if v is None:
-                        red.append(None)
-                    else:
-                        red.append(flat[off:off + v.numel()].view(v.shape))
-                        off += v.numel()
-                views_all = red
+            _, views_all = _all_reduce_views(views_all, group)
             if g_na_loc_total is not None:
                 g_na = torch.zeros_like(node_attr)
                 g_na[lo:hi] = g_na_loc_total
                 dist.all_reduce(g_na, op=dist.ReduceOp.SUM, group=group)
-        else:
-            g_na = g_na_loc_total
-        return (gh, g_ea_total, g_na, None, None, None, None, None, *views_all)
+        return (gh, g_ea, g_na, None, None, None, None, None, None, *views_all)
 
 
-class _DstPartStackOverlapFn(torch.autograd.Function):
-    """_DstPartStackFn with the collectives of the chain hidden under edge work (world > 1). Every layer's edge stage
-    runs in two launches: the owned edges whose source is owned too (they read rows of the own slice only) and the rest.
-    Forward: the all-gather of layer k's output slice is in flight while layer k + 1 runs its local-source edges on the
-    slice it already has; the remote-source edges follow the wait. Backward: the remote-source edges go first, the
-    reduce-scatter of THEIR d/dh (the only part with rows of other ranks) travels while the local-source edges run; the
-    local part lands on owned rows and is added behind the wait. Same results as the blocking chain up to the order of
-    two float additions per row."""
+class _DstPartitioned(torch.nn.Module):
+    """Partitioning B behind a module: `plan(edge_index, n_nodes)` takes the WHOLE edge list (replicated topology);
+    forward takes the whole h / node_attr and this rank's rows of edge_attr (`edge_attr[plan.edge_ids]`) and runs the
+    layers of `self._chain()` as one destination-partitioned chain."""
 
-    @staticmethod
-    def forward(ctx, h, edge_attr_local, node_attr, specs, plan: DstPlan, backend, group, counts, *params):
-        lo, hi = plan.lo, plan.hi
-        csr_l, csr_r = plan.split()
-        ea_l = None if edge_attr_local is None else edge_attr_local.index_select(0, plan.idx_loc)
-        ea_r = None if edge_attr_local is None else edge_attr_local.index_select(0, plan.idx_rem)
-        na_loc = None if node_attr is None else node_attr[lo:hi].contiguous()
-        deg_loc = plan.deg[lo:hi].contiguous()
-        hs, aggs, st = [], [], []
-        x = h.contiguous()
-        pending, padded, x_own = None, None, None
-        off = 0
-        for spec, cnt in zip(specs, counts):
-            lp = params[off:off + cnt]
-            off += cnt
-            ne = spec.edge.nblk * ops.NP
-            pe, pn = lp[:ne], lp[ne:]
-            if pending is None:
-                agg_l, st_l = backend.edge_forward(spec, csr_l, x, ea_l, pe)
-            else:
-                # rows outside [lo, hi) of x_own are never read by the local-source edges
-                agg_l, st_l = backend.edge_forward(spec, csr_l, x_own, ea_l, pe)
-                pending.wait()
-                x = plan.from_padded(padded)
-                pending = None
-            agg_r, st_r = backend.edge_forward(spec, csr_r, x, ea_r, pe)
-            agg = agg_l + agg_r                                                       # complete on [lo, hi)
-            out_loc, st_n = backend.node_forward(spec, deg_loc, x[lo:hi].contiguous(), agg[lo:hi].contiguous(), na_loc, pn)
-            hs.append(x); aggs.append(agg); st.append((st_l, st_r, st_n))
-            padded = out_loc.new_empty((plan.world * plan.per,) + tuple(out_loc.shape[1:]))
-            pending = _all_gather_rows_async(padded, plan.pad_slice(out_loc), group)
-            x_own = out_loc.new_zeros((plan.n_nodes,) + tuple(out_loc.shape[1:]))
-            x_own[lo:hi] = out_loc
-        pending.wait()
-        x = plan.from_padded(padded)
-        ctx.st = st
-        ctx.specs, ctx.plan, ctx.backend, ctx.group, ctx.counts = specs, plan, backend, group, counts
-        ctx.has_ea, ctx.has_na = edge_attr_local is not None, node_attr is not None
-        ctx.mask = [p is not None for p in params]
-        ctx.n_layers = len(specs)
-        saved = hs + aggs + ([ea_l, ea_r] if ctx.has_ea else []) + ([node_attr] if ctx.has_na else [])
-        ctx.save_for_backward(*saved, *[p for p in params if p is not None])
-        return x
-
-    @staticmethod
-    def backward(ctx, gout):
-        specs, plan, backend, group, counts = ctx.specs, ctx.plan, ctx.backend, ctx.group, ctx.counts
-        L = ctx.n_layers
-        saved = list(ctx.saved_tensors)
-        hs, aggs = saved[:L], saved[L:2 * L]
-        pos = 2 * L
-        ea_l = ea_r = node_attr = None
-        if ctx.has_ea:
-            ea_l, ea_r = saved[pos], saved[pos + 1]; pos += 2
-        if ctx.has_na:
-            node_attr = saved[pos]; pos += 1
-        it = iter(saved[pos:])
-        params = [next(it) if m else None for m in ctx.mask]
-        lo, hi = plan.lo, plan.hi
-        csr_l, csr_r = plan.split()
-        na_loc = None if node_attr is None else node_attr[lo:hi].contiguous()
-        deg_loc = plan.deg[lo:hi].contiguous()
-        offs = [0]
-        for cnt in counts:
-            offs.append(offs[-1] + cnt)
-        g_loc = gout[lo:hi].contiguous()
-        views_all = [None] * len(params)
-        g_ea_l_tot = g_ea_r_tot = g_na_loc_total = None
-
-        def acc(a, b):
-            return b if a is None else (a if b is None else a + b)
-
-        for k in range(L - 1, -1, -1):
-            spec = specs[k]
-            lp = params[offs[k]:offs[k + 1]]
-            ne = spec.edge.nblk * ops.NP
-            pe, pn = lp[:ne], lp[ne:]
-            h, agg = hs[k], aggs[k]
-            st_l, st_r, st_n = ctx.st[k]
-            gh_node, g_agg_loc, g_na_loc, views_n = backend.node_backward(
-                spec, deg_loc, h[lo:hi].contiguous(), agg[lo:hi].contiguous(), na_loc, pn, g_loc,
-                ctx.needs_input_grad[2], st_n)
-            g_agg = torch.zeros_like(agg)
-            g_agg[lo:hi] = g_agg_loc
-            gh_r = torch.zeros_like(h)             # +g -> owned targets, -g -> sources on OTHER ranks
-            g_ea_r, views_r = backend.edge_backward(spec, csr_r, h, ea_r, pe, g_agg, gh_r, ctx.needs_input_grad[1], st_r)
-            g_pad = gh_r.new_empty((plan.per,) + tuple(gh_r.shape[1:]))
-            pending = _reduce_scatter_rows_async(g_pad, plan.to_padded(gh_r), group)
-            gh_l = torch.zeros_like(h)             # both ends owned: rows of [lo, hi) only
-            g_ea_l, views_l = backend.edge_backward(spec, csr_l, h, ea_l, pe, g_agg, gh_l, ctx.needs_input_grad[1], st_l)
-            views_e = [acc(a, b) for a, b in zip(views_l, views_r)]
-            for i, v in enumerate(list(views_e) + list(views_n)):
-                views_all[offs[k] + i] = v
-            g_ea_l_tot, g_ea_r_tot = acc(g_ea_l_tot, g_ea_l), acc(g_ea_r_tot, g_ea_r)
-            g_na_loc_total = acc(g_na_loc_total, g_na_loc)
-            pending.wait()
-            g_loc = g_pad[:hi - lo] + gh_l[lo:hi] + gh_node
-        gh = None
-        if ctx.needs_input_grad[0]:
-            padded = g_loc.new_empty((plan.world * plan.per,) + tuple(g_loc.shape[1:]))
-            _all_gather_rows(padded, plan.pad_slice(g_loc), group)
-            gh = plan.from_padded(padded)
-        g_ea_total = None
-        if g_ea_l_tot is not None or g_ea_r_tot is not None:
-            ref = g_ea_l_tot if g_ea_l_tot is not None else g_ea_r_tot
-            g_ea_total = ref.new_zeros((plan.edge_ids.numel(),) + tuple(ref.shape[1:]))
-            if g_ea_l_tot is not None:
-                g_ea_total[plan.idx_loc] = g_ea_l_tot
-            if g_ea_r_tot is not None:
-                g_ea_total[plan.idx_rem] = g_ea_r_tot
-        live = [v for v in views_all if v is not None]
-        if live:
-            flat = torch.cat([v.reshape(-1) for v in live])
-            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
-            off, red = 0, []
-            for v in views_all:
-                if v is None:
-                    red.append(None)
-                else:
-                    red.append(flat[off:off + v.numel()].view(v.shape))
-                    off += v.numel()
-            views_all = red
-        g_na = None
-        if g_na_loc_total is not None:
-            g_na = torch.zeros_like(node_attr)
-            g_na[lo:hi] = g_na_loc_total
-            dist.all_reduce(g_na, op=dist.ReduceOp.SUM, group=group)
-        return (gh, g_ea_total, g_na, None, None, None, None, None, *views_all)
-
-
-class DstPartitionedEGCL(torch.nn.Module):
-    """Wraps an EGCL module (partitioning B). `plan(edge_index, n_nodes)` takes the WHOLE edge list
-    (replicated topology); forward takes the whole h / node_attr and this rank's rows of edge_attr
-    (`edge_attr[plan.edge_ids]`)."""
-
-    def __init__(self, layer, backend=ops.HipBackend, group=None, balance=True):
+    def __init__(self, backend, group, balance, overlap=False):
         super().__init__()
-        self.layer = layer
         self.backend = backend
         self.group = group
         self.balance = balance
+        self.overlap = overlap     # collectives in flight under the local-source edges
 
     def plan(self, edge_index, n_nodes, boundaries=None) -> DstPlan:
         """boundaries: allowed cut positions (the `ptr` of a collated batch): graphs stay whole, see balanced_node_cuts."""
         return DstPlan(edge_index, n_nodes, self.backend, self.group, balance=self.balance, boundaries=boundaries)
 
     def forward(self, h, plan: DstPlan, edge_attr_local=None, node_attr=None):
-        layer = self.layer
-        params = layer.edge_model.flat_params() + layer.node_model.flat_params()
-        return _DstPartStackFn.apply(h, edge_attr_local, node_attr, (layer.spec(),), plan, self.backend, self.group,
-                                     (len(params),), *params)
+        layers = self._chain()
+        lps = [_layer_params(layer) for layer in layers]
+        specs, counts = tuple(layer.spec() for layer in layers), tuple(len(lp) for lp in lps)
+        return _DstPartStackFn.apply(h, edge_attr_local, node_attr, specs, plan, self.backend, self.group, counts,
+                                     bool(self.overlap and plan.multi), *[p for lp in lps for p in lp])
 
 
-class DstPartitionedStack(torch.nn.Module):
+class DstPartitionedEGCL(_DstPartitioned):
+    """Wraps ONE EGCL module (partitioning B): the chain of one layer."""
+
+    def __init__(self, layer, backend=ops.HipBackend, group=None, balance=True):
+        super().__init__(backend, group, balance)
+        self.layer = layer
+
+    def _chain(self):
+        return [self.layer]
+
+
+class DstPartitionedStack(_DstPartitioned):
     """L chained EGCL layers on ONE destination partition of the complex: h stays resident, every
     layer costs one all-gather forward and one reduce-scatter backward, the parameter gradients of all layers one
     all-reduce. All layers share edge_attr / node_attr, as the reference's models do (hulls_cssmpnn.py:89-94).
     overlap=True: the collectives travel under the edges whose source is owned too (two edge launches per stage)."""
 
     def __init__(self, layers, backend=ops.HipBackend, group=None, balance=True, overlap=False):
-        super().__init__()
+        super().__init__(backend, group, balance, overlap)
         self.layers = torch.nn.ModuleList(layers)
-        self.backend = backend
-        self.group = group
-        self.balance = balance
-        self.overlap = overlap     # collectives in flight under the local-source edges (_DstPartStackOverlapFn)
 
-    def plan(self, edge_index, n_nodes, boundaries=None) -> DstPlan:
-        """boundaries: allowed cut positions (the `ptr` of a collated batch): graphs stay whole, see balanced_node_cuts."""
-        return DstPlan(edge_index, n_nodes, self.backend, self.group, balance=self.balance, boundaries=boundaries)
-
-    def forward(self, h, plan: DstPlan, edge_attr_local=None, node_attr=None):
-        params, counts, specs = [], [], []
-        for layer in self.layers:
-            lp = layer.edge_model.flat_params() + layer.node_model.flat_params()
-            params += lp
-            counts.append(len(lp))
-            specs.append(layer.spec())
-        fn = _DstPartStackOverlapFn if (self.overlap and plan.multi) else _DstPartStackFn
-        return fn.apply(h, edge_attr_local, node_attr, tuple(specs), plan, self.backend, self.group, tuple(counts), *params)
+    def _chain(self):
+        return list(self.layers)
 
 
 class GraphedDstStep:
@@ -816,47 +774,32 @@ class GraphedDstStep:
     [graph 1: edge forward on the owned targets, node forward on the owned nodes, slice padded] -> all-gather(out)
     -> [graph 2: rows back to the natural layout, node backward, edge backward, d/dh rows to the padded layout] ->
     reduce-scatter(d/dh) + all-reduce(parameter gradients). `compute_only=True` skips the collectives (the
-    compute-only rate of the bench)."""
+    compute-only rate of the bench). World size 1: no padded-layout copies at all."""
 
     def __init__(self, part: "DstPartitionedEGCL", plan: DstPlan, h, edge_attr_local, node_attr, gout):
         layer, be = part.layer, part.backend
         self.group, self.plan = part.group, plan
         self.spec = spec = layer.spec()
-        pe, pn = layer.edge_model.flat_params(), layer.node_model.flat_params()
+        lp = _layer_params(layer)
         self.h = h_ = h.detach()
-        lo, hi = plan.lo, plan.hi
         self._multi = plan.multi
-        na_loc = None if node_attr is None else node_attr[lo:hi].contiguous()
-        h_loc, deg_loc, gout_loc = h_[lo:hi], plan.deg[lo:hi].contiguous(), gout[lo:hi].contiguous()
+        own = _Own(plan, node_attr)
+        gout_loc = gout[plan.lo:plan.hi].contiguous()
         self.out_all = h_.new_empty((plan.world * plan.per,) + tuple(h_.shape[1:]))   # all-gather target (padded layout)
 
         def part1():
-            agg, st_e = be.edge_forward(spec, plan.csr, h_, edge_attr_local, pe)
-            out_loc, st_n = be.node_forward(spec, deg_loc, h_loc, agg[lo:hi], na_loc, pn)
-            return agg, st_e, plan.pad_slice(out_loc), st_n
+            agg, out_loc, st = _dst_forward(be, spec, own, h_, edge_attr_local, lp)
+            return agg, st, plan.pad_slice(out_loc)
 
-        def part2(agg, st_e, st_n):
+        def part2(agg, st):
             out = plan.from_padded(self.out_all) if self._multi else None   # the layer's replicated output
-            gh_node, g_agg_loc, _g, views_n = be.node_backward(spec, deg_loc, h_loc, agg[lo:hi], na_loc, pn, gout_loc, False, st_n)
-            g_agg = torch.zeros_like(agg)
-            g_agg[lo:hi] = g_agg_loc
-            gh_edge = torch.zeros_like(h_)
-            _g_ea, views_e = be.edge_backward(spec, plan.csr, h_, edge_attr_local, pe, g_agg, gh_edge, False, st_e)
-            flat = torch.cat([v.reshape(-1) for v in list(views_e) + list(views_n) if v is not None])
-            return gh_node, gh_edge, plan.to_padded(gh_edge) if self._multi else None, flat, out
+            gh_node, gh_edge, _g_ea, _g_na, views = _dst_backward(be, spec, own, h_, agg, edge_attr_local, lp, gout_loc,
+                                                                   (False, False), st)
+            return gh_node, gh_edge, plan.to_padded(gh_edge) if self._multi else None, _pack(views), out
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            a, se, ol, sn = part1()
-            part2(a, se, sn)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.g1, self.g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g1, capture_error_mode="thread_local"):
-            self.agg, self._st_e, self.out_pad, self._st_n = part1()
-        with torch.cuda.graph(self.g2, pool=self.g1.pool(), capture_error_mode="thread_local"):
-            self.gh_node, self.gh_edge, self.gh_pad, self.flat, self.out = part2(self.agg, self._st_e, self._st_n)
+        capture = _Capture(lambda: part2(*part1()[:2]))
+        self.g1, (self.agg, self._st, self.out_pad) = capture(part1)
+        self.g2, (self.gh_node, self.gh_edge, self.gh_pad, self.flat, self.out) = capture(lambda: part2(self.agg, self._st))
         self.gh_rs = h_.new_empty((plan.per,) + tuple(h_.shape[1:]))   # reduce-scatter target: this rank's padded slice
         self.gh_loc = torch.empty_like(self.gh_node)
         self.bytes_per_step = 0
@@ -895,35 +838,26 @@ class GraphedDstStackStep:
         layers = list(stack.layers)
         self.L = L = len(layers)
         specs = [l.spec() for l in layers]
-        pes = [l.edge_model.flat_params() for l in layers]
-        pns = [l.node_model.flat_params() for l in layers]
-        lo, hi = plan.lo, plan.hi
-        n = hi - lo
+        lps = [_layer_params(l) for l in layers]
+        n = plan.hi - plan.lo
         self._multi = plan.multi
         h0 = h.detach().contiguous()
-        na_loc = None if node_attr is None else node_attr[lo:hi].contiguous()
-        deg_loc = plan.deg[lo:hi].contiguous()
-        gout_loc = gout[lo:hi].contiguous()
+        own = _Own(plan, node_attr)
+        gout_loc = gout[plan.lo:plan.hi].contiguous()
         row = tuple(h0.shape[1:])
         self.out_all = [h0.new_empty((plan.world * plan.per,) + row) for _ in range(L)]   # all-gather targets
         self.gh_rs = [h0.new_empty((plan.per,) + row) for _ in range(L)]                  # reduce-scatter targets
 
-        def fwd(k):
+        def fwd(k):     # -> (x, agg, states, padded output slice)
             x = h0 if k == 0 else plan.from_padded(self.out_all[k - 1])
-            agg, st_e = be.edge_forward(specs[k], plan.csr, x, edge_attr_local, pes[k])
-            out_loc, st_n = be.node_forward(specs[k], deg_loc, x[lo:hi].contiguous(), agg[lo:hi].contiguous(), na_loc, pns[k])
-            return x, agg, st_e, st_n, plan.pad_slice(out_loc)
+            agg, out_loc, st = _dst_forward(be, specs[k], own, x, edge_attr_local, lps[k])
+            return x, agg, st, plan.pad_slice(out_loc)
 
-        def bwd(k, x, agg, st_e, st_n, gh_node_next):
+        def bwd(k, x, agg, st, gh_node_next):     # -> (d/dh of the node stage, padded d/dh of the edge stage, gradients)
             g_loc = gout_loc if k == L - 1 else self.gh_rs[k + 1][:n] + gh_node_next
-            gh_node, g_agg_loc, _g, views_n = be.node_backward(specs[k], deg_loc, x[lo:hi].contiguous(), agg[lo:hi].contiguous(),
-                                                               na_loc, pns[k], g_loc, False, st_n)
-            g_agg = torch.zeros_like(agg)
-            g_agg[lo:hi] = g_agg_loc
-            gh_edge = torch.zeros_like(x)
-            _g_ea, views_e = be.edge_backward(specs[k], plan.csr, x, edge_attr_local, pes[k], g_agg, gh_edge, False, st_e)
-            flat = torch.cat([v.reshape(-1) for v in list(views_e) + list(views_n) if v is not None])
-            return gh_node, plan.to_padded(gh_edge), flat
+            gh_node, gh_edge, _g_ea, _g_na, views = _dst_backward(be, specs[k], own, x, agg, edge_attr_local, lps[k], g_loc,
+                                                                   (False, False), st)
+            return gh_node, plan.to_padded(gh_edge), _pack(views)
 
         def gather(k, pad):
             if self._multi:
@@ -938,38 +872,22 @@ class GraphedDstStackStep:
                 self.gh_rs[k].copy_(pad)
         self._gather, self._scatter = gather, scatter
 
-        # warm-up on a side stream (allocations, lazy kernel loads), then one capture per segment
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            st = []
+        def chain(segment):
+            """The 2 L segments in step order, each through `segment` (which runs it plainly, or captures it) and
+            followed by its collective, so that the next segment reads a buffer of the right content."""
+            self.gf, self.gb = [None] * L, [None] * L
+            self._st, self._bw = [None] * L, [None] * L
             for k in range(L):
-                st.append(fwd(k))
-                gather(k, st[k][4])
+                self.gf[k], self._st[k] = segment(lambda: fwd(k))
+                gather(k, self._st[k][3])
             ghn = None
             for k in range(L - 1, -1, -1):
-                ghn, pad, _f = bwd(k, *st[k][:4], ghn)
-                scatter(k, pad)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.gf, self.gb = [], [None] * L
-        self._st, self._bw = [], [None] * L
-        pool = None
-        for k in range(L):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-                self._st.append(fwd(k))
-            pool = pool or g.pool()
-            self.gf.append(g)
-            gather(k, self._st[k][4])      # the next segment's capture reads a buffer of the right content
-        ghn = None
-        for k in range(L - 1, -1, -1):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-                self._bw[k] = bwd(k, *self._st[k][:4], ghn)
-            self.gb[k] = g
-            ghn = self._bw[k][0]
-            scatter(k, self._bw[k][1])
+                self.gb[k], self._bw[k] = segment(lambda: bwd(k, *self._st[k][:3], ghn))
+                ghn = self._bw[k][0]
+                scatter(k, self._bw[k][1])
+
+        capture = _Capture(lambda: chain(lambda fn: (None, fn())))     # warm-up: no graph
+        chain(capture)
         self.flat = torch.cat([self._bw[k][2] for k in range(L)])
         self.gh_loc = torch.empty_like(self._bw[0][0])
         self.out = None
@@ -982,7 +900,7 @@ class GraphedDstStackStep:
         L, n = self.L, self.plan.hi - self.plan.lo
         for k in range(L):
             self.gf[k].replay()
-            self._gather(k, self._st[k][4])
+            self._gather(k, self._st[k][3])
         for k in range(L - 1, -1, -1):
             self.gb[k].replay()
             self._scatter(k, self._bw[k][1])
