@@ -98,9 +98,11 @@ def _run_layer(pkg, C, seed, N=2000, E=20000, metric=(1.0, 1.0, 1.0)):
                                           # 8 channels of D = 32: the parity-lane kernels (cemlp_pl.hpp) in this mode too; the
                                           # one-group wide kernels take them only under CSMPN_PLW8=1
                                           (8, (1.0, 1.0, 1.0, 1.0, -1.0), 500, 5000),
-                                          # round 3: the general row-tile kernels in their deterministic form (one row tile per
-                                          # workgroup, mirror slices + fixed-order reduction): the md17 width (Cl(3,0), 32 channels),
-                                          # the NBA width (Cl(2,0), 40 channels), an odd narrow width
+                                          # the md17 width (Cl(3,0), 32 channels): the 16-row-tile kernels (cemlp_pq.hpp) both ways
+                                          # in their row-store form, as at 16 channels cemlp_cm.hpp / cemlp_cmb.hpp with the fixed
+                                          # tile assignment - the dispatch log of tests/test_lane_n3_gpu.py, group det. The general
+                                          # row-tile kernels in their deterministic form (one row tile per workgroup, mirror slices
+                                          # + fixed-order reduction): the NBA width (Cl(2,0), 40 channels), an odd narrow width
                                           (32, (1.0, 1.0, 1.0), 600, 6000), (40, (1.0, 1.0), 400, 4000), (5, (1.0, 1.0, 1.0), 700, 5000)])
 def test_bit_reproducible(pkg, det, C, metric, N, E):
     once = _run_layer(pkg, C, seed=11, N=N, E=E, metric=metric)
