@@ -134,11 +134,89 @@ def to_complex(n_vertices: int, x_dict, adj, max_dim: int = 2) -> SimplicialComp
     return SimplicialComplex(n_vertices, x_ind, node_types, edge_index, edge_types)
 
 
-def hull_complex(points: np.ndarray, max_dim: int = 2) -> SimplicialComplex:
-    """Faces of the convex hull of `points` [V, n] (utils.py:210-247)."""
-    from scipy.spatial import ConvexHull
-    hull = ConvexHull(np.asarray(points, dtype=np.float64))
-    x_dict, adj = lift(len(points), hull.simplices.tolist(), max_dim)
+def _hull_det(M, row: int, cols):
+    """Determinant of the rows row .. of M and the columns `cols` (as many as rows), M[i][j] float64 arrays: the Laplace
+    expansion along the first row over the columns ascending, ((M[c0] d0 - M[c1] d1) + M[c2] d2) - ..., every product
+    rounded before it is added - the expression minor_det / laplace of csrc/lift.hip state."""
+    if len(cols) == 1:
+        return M[row][cols[0]]
+    acc = None
+    for k, c in enumerate(cols):
+        term = M[row][c] * _hull_det(M, row + 1, [x for x in cols if x != c])
+        acc = term if k == 0 else (acc - term if k & 1 else acc + term)
+    return acc
+
+
+HULL_LANES = 256       # the candidates rank, rank + 256, ... are summed by one thread of lift_hull_kernel
+
+
+def hull_facets(points: np.ndarray) -> Tuple[np.ndarray, float]:
+    """(facets int64 [F, n] in lexicographic order, volume) of the convex hull of `points` [V, n], V > n >= 2, by the rule
+    csmpn_hull_lift applies on the device, in float64 with the very order of operations of lift_hull_kernel, so that both
+    give the same facets and the same volume to the bit.
+
+    A candidate is an n-subset F = (f_0 < ... < f_{n-1}). With the rows M_i = p_{f_{i+1}} - p_{f_0}, its normal is
+    N_j = (-1)^(n-1+j) det(M without column j) (_hull_det) and side(F, q) = sum_j N_j (q_j - p_{f_0, j}), j ascending. F is a
+    facet iff side(F, q) > 0 for every vertex q outside F, or < 0 for every one; a zero or a NaN makes F no facet. Coplanar
+    point sets, coincident points and NaN vertices therefore give fewer facets, or none: what qhull does with degenerate
+    input (merged or joggled facets) is not restated. On points in general position this is the facet set of the hull,
+    whatever the implementation.
+
+    volume = (sum over the facets of |side(F, p_0)|) / n!: vertex 0 lies in or on the hull, so every term is n! times the
+    volume of the simplex over a facet with apex p_0 (0 for the facets through p_0). Order of the sum: the candidates
+    rank, rank + 256, ... (rank = the lexicographic index) ascending into one of 256 partial sums; each run of 64 of those
+    halved by adding the upper half onto the lower (32, 16, ..., 1); the four results added left to right."""
+    pts = np.asarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] < 2 or pts.shape[0] <= pts.shape[1]:
+        raise ValueError(f"hull_facets: points must be [V, n] with V > n >= 2, got {tuple(pts.shape)}")
+    V, n = pts.shape
+    cand = np.array(list(itertools.combinations(range(V), n)), dtype=np.int64).reshape(-1, n)
+    origin = pts[cand[:, 0]]
+    with np.errstate(invalid="ignore", over="ignore"):
+        M = [[pts[cand[:, i + 1], j] - origin[:, j] for j in range(n)] for i in range(n - 1)]
+        normal = []
+        for j in range(n):
+            d = _hull_det(M, 0, [c for c in range(n) if c != j])
+            normal.append(-d if (n - 1 + j) & 1 else d)
+
+        def side(q):
+            s = normal[0] * (q[0] - origin[:, 0])
+            for j in range(1, n):
+                s = s + normal[j] * (q[j] - origin[:, j])
+            return s
+
+        pos, neg = np.ones(len(cand), dtype=bool), np.ones(len(cand), dtype=bool)
+        for q in range(V):
+            s, inside = side(pts[q]), (cand == q).any(axis=1)
+            pos &= inside | (s > 0)
+            neg &= inside | (s < 0)
+        facet = pos | neg
+        terms = np.where(facet, np.abs(side(pts[0])), 0.0)
+        terms = np.concatenate([terms, np.zeros(-len(terms) % HULL_LANES)]).reshape(-1, HULL_LANES)
+        partial = np.zeros(HULL_LANES)
+        for row in terms:
+            partial = partial + row
+        x = partial.reshape(-1, 64)
+        for d in (32, 16, 8, 4, 2, 1):
+            x = x[:, :d] + x[:, d:2 * d]
+        total = x[0, 0]
+        for w in range(1, x.shape[0]):
+            total = total + x[w, 0]
+    return cand[facet], float(total / math.factorial(n))
+
+
+def hull_complex(points: np.ndarray, max_dim: int = 2, method: str = "qhull") -> SimplicialComplex:
+    """Faces of the convex hull of `points` [V, n] (utils.py:210-247). method="qhull": the facets scipy's qhull reports (the
+    reference's); method="exact": those of hull_facets - the same set on points in general position, the rule of the device
+    lift (csmpn_hull_lift) on every input."""
+    if method == "qhull":
+        from scipy.spatial import ConvexHull
+        facets = ConvexHull(np.asarray(points, dtype=np.float64)).simplices.tolist()
+    elif method == "exact":
+        facets = hull_facets(points)[0].tolist()
+    else:
+        raise ValueError(f"hull_complex: method {method!r} (\"qhull\" or \"exact\")")
+    x_dict, adj = lift(len(points), facets, max_dim)
     return to_complex(len(points), x_dict, adj, max_dim)
 
 
@@ -319,13 +397,16 @@ class SimplicialBatch:
         return self
 
     def relift_(self, points: torch.Tensor, dis: Optional[float] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
-                knn: Optional[int] = None) -> "SimplicialBatch":
+                knn: Optional[int] = None, hull: bool = False) -> "SimplicialBatch":
         """Make this DEVICE batch hold the Vietoris-Rips complexes of `points` (device float32 [B * V, n], the V vertices of
         graph g contiguous; B and V are this batch's) at threshold `dis`, at the capacity the batch was built with: the
         structure tensors are written by ops.rips_lift (csmpn_rips_lift) as pad_batch(collate([rips_complex(...)]), capacity)
         would lay them out, then everything derived from them is rebuilt in place as in refresh_. With knn=k instead of
         dis (exactly one of the two, else ValueError) the complexes are the clique complexes of the k-nearest-neighbour
-        graphs, knn_clique_complex(points, k), written by ops.knn_lift (csmpn_knn_lift). vertex_features
+        graphs, knn_clique_complex(points, k), written by ops.knn_lift (csmpn_knn_lift); with hull=True (exactly one of the
+        three) the convex-hull complexes hull_complex(points, method="exact"), written by ops.hull_lift (csmpn_hull_lift), which
+        also writes the hulls' volumes into `target` where the batch has one, and - as hull_batch_device does - the points
+        count as the vertex feature `input` where the batch has that tensor and vertex_features does not name it. vertex_features
         {name: per-vertex tensor [B * V, ...]}: the per-simplex tensor `name` is zeroed and gets these rows at the vertex
         rows of the new batch. plan() and csr() must have been called. After the first call: no allocation, no host
         synchronisation. A complex that does not fit the capacity leaves the batch as it was (the features excepted, which
@@ -333,8 +414,9 @@ class SimplicialBatch:
         n_real_edges are dropped: the real counts live on the device, in plan()["lift_counts"] (rows per dimension,
         adjacencies)."""
         from csmpn_hip import ops
-        if (dis is None) == (knn is None):
-            raise ValueError("relift_: pass exactly one of dis=... (Rips) and knn=... (k-nearest-neighbour cliques)")
+        if (dis is not None) + (knn is not None) + bool(hull) != 1:
+            raise ValueError("relift_: pass exactly one of dis=... (Rips), knn=... (k-nearest-neighbour cliques) and hull=True "
+                             "(convex hulls)")
         plan = getattr(self, "_plan", None)
         if plan is None or self._csr is None:
             raise RuntimeError("relift_: call plan() and csr() on the batch first")
@@ -345,20 +427,25 @@ class SimplicialBatch:
         rows = [int(r.shape[0]) for r in plan["rows"]]
         if points.dim() != 2 or int(points.shape[0]) != rows[0]:
             raise ValueError(f"relift_: points must be [{rows[0]}, n] (one row per vertex of the batch), got {tuple(points.shape)}")
+        if hull and "input" in self._names and "input" not in (vertex_features or {}):
+            vertex_features = dict(vertex_features or {}, input=points)
         for name, value in (vertex_features or {}).items():
             t = getattr(self, name, None)
             if name not in self._names or name in _STRUCTURE or int(t.shape[0]) != int(self.node_types.shape[0]):
                 raise ValueError(f"relift_: {name!r} is not a per-simplex feature tensor of the batch")
             if tuple(value.shape) != (rows[0],) + tuple(t.shape[1:]):
                 raise ValueError(f"relift_: vertex feature {name!r} has shape {tuple(value.shape)}, expected {(rows[0],) + tuple(t.shape[1:])}")
-        if "lift_ws" not in plan:      # one workspace serves both lifts: the larger of the two queries (they are equal today)
-            sizes = [query(B, rows[0] // B, max_dim, dev) for query in (ops.rips_lift_workspace, ops.knn_lift_workspace)]
-            plan["lift_ws"] = max(sizes, key=lambda t: t.numel())
+        if "lift_ws" not in plan:
+            plan["lift_ws"] = _lift_workspace(B, rows[0] // B, max_dim, dev)
             plan["lift_status"] = torch.zeros(1, dtype=torch.int32, device=dev)
             plan["lift_counts"] = torch.zeros(max_dim + 2, dtype=torch.int64, device=dev)
-        run, param = (ops.rips_lift, dis) if knn is None else (ops.knn_lift, knn)
-        run(points, B, param, max_dim, rows, int(self.edge_index.shape[1]), self.x_ind, self.node_types, self.batch,
-            self.x_ind_batch, self.ptr, self.x_ind_ptr, self.edge_index, getattr(self, "edge_types", None),
+        if hull:
+            target = getattr(self, "target", None) if "target" in self._names else None
+            run = lambda p, b, _, *rest: ops.hull_lift(p, b, *rest, volume=target)
+        else:
+            run = ops.rips_lift if knn is None else ops.knn_lift
+        run(points, B, dis if knn is None else knn, max_dim, rows, int(self.edge_index.shape[1]), self.x_ind, self.node_types,
+            self.batch, self.x_ind_batch, self.ptr, self.x_ind_ptr, self.edge_index, getattr(self, "edge_types", None),
             plan["lift_counts"], plan["lift_status"], plan["lift_ws"])
         for k in ("n_real_rows", "n_real_edges"):
             if hasattr(self, k):
@@ -578,7 +665,16 @@ def pad_batch(batch: "SimplicialBatch", capacity: BatchCapacity, simplex_feature
 # structure tensors come out exactly as pad_batch(collate([rips_complex(...)])) lays them out, and relift_ rebuilds the
 # rest in place in front of a replayed step. The clique complex of the k-nearest-neighbour graph (knn_clique_complex, the
 # reference's aspirin configuration) is lifted the same way by csmpn_knn_lift: knn_capacity, knn_batch_device,
-# relift_(points, knn=k).
+# relift_(points, knn=k); the convex-hull complex (hull_complex(method="exact"), the hulls task) with its volume by
+# csmpn_hull_lift: hull_capacity, hull_batch_device, relift_(points, hull=True).
+
+
+def _lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, device) -> torch.Tensor:
+    """One workspace that serves all three device lifts of a batch: the largest of their queries."""
+    from csmpn_hip import ops
+    sizes = [query(n_graphs, verts_per_graph, max_dim, device)
+             for query in (ops.rips_lift_workspace, ops.knn_lift_workspace, ops.hull_lift_workspace)]
+    return max(sizes, key=lambda t: t.numel())
 
 
 def rips_adjacencies(n_graphs: int, verts_per_graph: int, n_edges: int, n_triangles: int) -> int:
@@ -625,6 +721,27 @@ def knn_capacity(n_graphs: int, verts_per_graph: int, k: int, max_triangles: int
     return BatchCapacity(rows, clique_adjacencies(max_edges, max_triangles))
 
 
+def hull_capacity(n_graphs: int, verts_per_graph: int, max_dim: int = 2, max_edges: Optional[int] = None,
+                  max_triangles: Optional[int] = None) -> BatchCapacity:
+    """The capacity that serves every batch of n_graphs convex-hull complexes on verts_per_graph vertices each with at most
+    max_edges 1-simplices and max_triangles 2-simplices in all (defaults: every pair and every triple, n_graphs C(V, 2) and
+    n_graphs C(V, 3)) - with the one spare 1-simplex of rips_capacity. The adjacencies are those of a Rips complex with
+    these counts (rips_adjacencies: the lift has the vertex block)."""
+    if max_dim not in (1, 2):
+        raise ValueError("hull_capacity: max_dim must be 1 or 2")
+    if n_graphs < 1 or verts_per_graph < max_dim + 1 or (max_edges is not None and max_edges < 0) or \
+            (max_triangles is not None and max_triangles < 0):
+        raise ValueError("hull_capacity: need n_graphs >= 1, verts_per_graph >= max_dim + 1 and counts >= 0")
+    if max_edges is None:
+        max_edges = n_graphs * math.comb(verts_per_graph, 2)
+    if max_triangles is None:
+        max_triangles = n_graphs * math.comb(verts_per_graph, 3)
+    if max_dim == 1:
+        max_triangles = 0
+    rows = (n_graphs * verts_per_graph, max_edges + 1) + ((max_triangles,) if max_dim == 2 else ())
+    return BatchCapacity(rows, rips_adjacencies(n_graphs, verts_per_graph, max_edges, max_triangles))
+
+
 def rips_batch_device(points: torch.Tensor, n_graphs: int, dis: float, capacity: BatchCapacity,
                       features: Optional[Dict[str, torch.Tensor]] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
                       x_ind_cols: Optional[int] = None) -> SimplicialBatch:
@@ -644,8 +761,21 @@ def knn_batch_device(points: torch.Tensor, n_graphs: int, k: int, capacity: Batc
     return _lifted_batch_device("knn_batch_device", "knn_lift", points, n_graphs, k, capacity, features, vertex_features, x_ind_cols)
 
 
+def hull_batch_device(points: torch.Tensor, n_graphs: int, capacity: BatchCapacity,
+                      features: Optional[Dict[str, torch.Tensor]] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
+                      x_ind_cols: Optional[int] = None) -> SimplicialBatch:
+    """rips_batch_device for the convex-hull complexes of the points (hull_complex(method="exact"); csmpn_hull_lift) - the
+    batch relift_(points, hull=True) is then called on, laid out as a hulls sample (hulls_example): `input` [rows, n] holds
+    the points at the vertex rows (unless vertex_features names it), `target` [n_graphs] float32 the hulls' volumes as the
+    device computed them (unless features names it)."""
+    vertex_features = dict(vertex_features or {})
+    vertex_features.setdefault("input", points)
+    return _lifted_batch_device("hull_batch_device", "hull_lift", points, n_graphs, None, capacity, features, vertex_features, x_ind_cols)
+
+
 def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, vertex_features, x_ind_cols) -> SimplicialBatch:
-    """The body of rips_batch_device (op = "rips_lift", param = dis) and knn_batch_device (op = "knn_lift", param = k)."""
+    """The body of rips_batch_device (op = "rips_lift", param = dis), knn_batch_device (op = "knn_lift", param = k) and
+    hull_batch_device (op = "hull_lift", no parameter; the volumes become `target`)."""
     from csmpn_hip import ops
     if not points.is_cuda:
         raise RuntimeError(f"{what} needs device points (no CPU fallback)")
@@ -655,10 +785,11 @@ def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, 
                    edge_types=i64(E, 2), batch=i64(S), ptr=i64(B + 1), x_ind_batch=i64(S), x_ind_ptr=i64(B + 1))
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     counts = i64(max_dim + 2)
-    ws = getattr(ops, op + "_workspace")(B, int(points.shape[0]) // max(B, 1), max_dim, dev)
-    getattr(ops, op)(points, B, param, max_dim, capacity.simplices, E, tensors["x_ind"], tensors["node_types"], tensors["batch"],
-                     tensors["x_ind_batch"], tensors["ptr"], tensors["x_ind_ptr"], tensors["edge_index"], tensors["edge_types"], counts,
-                     status, ws)
+    ws = _lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev)
+    volume = torch.zeros(B, dtype=torch.float32, device=dev) if op == "hull_lift" else None
+    run = getattr(ops, op) if volume is None else (lambda p, b, _, *rest: ops.hull_lift(p, b, *rest, volume=volume))
+    run(points, B, param, max_dim, capacity.simplices, E, tensors["x_ind"], tensors["node_types"], tensors["batch"],
+        tensors["x_ind_batch"], tensors["ptr"], tensors["x_ind_ptr"], tensors["edge_index"], tensors["edge_types"], counts, status, ws)
     word = int(status.item())
     if word:
         raise ValueError(f"{what}: the complex does not fit the capacity {capacity} (status {word:#x}: bit 1 / 2 = too "
@@ -668,6 +799,8 @@ def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, 
         t = torch.zeros((S,) + tuple(value.shape[1:]), dtype=value.dtype, device=dev)
         t.index_copy_(0, vertex_rows, value.to(dev))
         tensors[name] = t
+    if volume is not None:
+        tensors["target"] = volume
     for name, value in (features or {}).items():
         tensors[name] = value.to(dev)
     out = SimplicialBatch(**tensors)

@@ -17,7 +17,8 @@ and the tables derived from the topology - the target-sorted CSR, the index tabl
 are rebuilt in place on the device (SimplicialBatch.refresh_: csmpn_simplex_tables, csmpn_csr_build) in front of the replay.
 Where the complex is the Vietoris-Rips complex of the current positions, step(points=...) builds it on the device as well
 (SimplicialBatch.relift_: csmpn_rips_lift writes the structure tensors at the capacity), so a step takes no host lift at all;
-step(points=..., knn=k) does the same for the clique complex of the k-nearest-neighbour graph (csmpn_knn_lift).
+step(points=..., knn=k) does the same for the clique complex of the k-nearest-neighbour graph (csmpn_knn_lift), and
+step(points=..., hull=True) for the convex-hull complex with the hull's volume as the target (csmpn_hull_lift).
 
 The kernels launched inside are the same C-ABI calls as in eager mode (they take the current stream); the
 CSR and the embedding index tables are built before capture (their only host round trips).
@@ -111,16 +112,22 @@ class GraphedTrainStep:
     a complex over the capacity leaves the previous structure in place and sets bits in status(). With `knn` (the step's
     default, as `rips_dis` is for dis) or knn=... in the call, the complexes are the clique complexes of the
     k-nearest-neighbour graphs instead (csmpn.data.complexes.knn_clique_complex; csmpn_knn_lift). A threshold AND a k, as
-    defaults or in one call, are a ValueError; a call that names one of the two does not read the defaults."""
+    defaults or in one call, are a ValueError; a call that names one of the two does not read the defaults. `hull=True` (as a
+    default or in the call) is the third choice under the same rules: the convex-hull complexes of the points
+    (hull_complex(method="exact"); csmpn_hull_lift), with the points as the vertex feature `input` and the hulls' volumes
+    written into `target` where the batch has these tensors - a hulls step from nothing but device points."""
+
+    hull = False
 
     def __init__(self, model, optimizer, batch, feature_names: Iterable[str], warmup: int = 2, max_dim: Optional[int] = None,
                  capacity=None, simplex_features: Optional[Iterable[str]] = None, device=None, rips_dis: Optional[float] = None,
-                 knn: Optional[int] = None):
-        if rips_dis is not None and knn is not None:
-            raise ValueError("GraphedTrainStep: rips_dis (Rips) and knn (k-nearest-neighbour cliques) exclude each other")
+                 knn: Optional[int] = None, hull: bool = False):
+        if (rips_dis is not None) + (knn is not None) + bool(hull) > 1:
+            raise ValueError("GraphedTrainStep: rips_dis (Rips), knn (k-nearest-neighbour cliques) and hull (convex hulls) "
+                             "exclude each other")
         self.capacity = capacity
         self.simplex_features = None
-        self.rips_dis, self.knn = rips_dis, knn
+        self.rips_dis, self.knn, self.hull = rips_dis, knn, bool(hull)
         if capacity is not None:
             from csmpn.data.complexes import pad_batch
             if device is None:
@@ -202,23 +209,24 @@ class GraphedTrainStep:
         self.batch.refresh_(pad_batch(batch, self.capacity, self.simplex_features))
 
     def load_points(self, points: torch.Tensor, dis: Optional[float] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
-                    knn: Optional[int] = None):
+                    knn: Optional[int] = None, hull: Optional[bool] = None):
         """Make the captured batch hold the Vietoris-Rips complexes of the device points [B * V, n] at threshold `dis`
         (default: the step's `rips_dis`) - or, with knn (default: the step's `knn`), the clique complexes of their
-        k-nearest-neighbour graphs - lifted on the device (SimplicialBatch.relift_): no host work per batch. A complex
+        k-nearest-neighbour graphs, or with hull=True (default: the step's `hull`) their convex hulls - lifted on the device (SimplicialBatch.relift_): no host work per batch. A complex
         over the capacity leaves the structure of the captured batch as it was and shows in status()."""
         if self.capacity is None:
             raise RuntimeError("GraphedTrainStep was built without a capacity: it replays ONE topology (load(features))")
-        if dis is not None and knn is not None:
-            raise ValueError("step(points=...): dis=... (Rips) and knn=... (k-nearest-neighbour cliques) exclude each other")
-        if dis is None and knn is None:
-            dis, knn = self.rips_dis, self.knn
-        if dis is None and knn is None:
-            raise ValueError("step(points=...): pass dis=... or knn=..., or set the step's rips_dis or knn")
-        self.batch.relift_(points, dis, vertex_features, knn=knn)
+        if (dis is not None) + (knn is not None) + bool(hull) > 1:
+            raise ValueError("step(points=...): dis=... (Rips), knn=... (k-nearest-neighbour cliques) and hull=True (convex "
+                             "hulls) exclude each other")
+        if dis is None and knn is None and not hull:
+            dis, knn, hull = self.rips_dis, self.knn, self.hull
+        if dis is None and knn is None and not hull:
+            raise ValueError("step(points=...): pass dis=... or knn=... or hull=True, or set the step's rips_dis, knn or hull")
+        self.batch.relift_(points, dis, vertex_features, knn=knn, hull=bool(hull))
 
     def status(self) -> int:
-        """The status words of the table rebuilds (ops.simplex_tables) and of the device lifts (ops.rips_lift / knn_lift: its bits
+        """The status words of the table rebuilds (ops.simplex_tables) and of the device lifts (ops.rips_lift / knn_lift / hull_lift: its bits
         1..4 are reported as bits 9..12) so far; 0 = fine. Synchronises."""
         plan = self.batch._plan
         word, lift = plan.get("status"), plan.get("lift_status")
@@ -226,13 +234,13 @@ class GraphedTrainStep:
 
     def step(self, features: Optional[Dict[str, torch.Tensor]] = None, batch=None, points: Optional[torch.Tensor] = None,
              vertex_features: Optional[Dict[str, torch.Tensor]] = None, dis: Optional[float] = None,
-             knn: Optional[int] = None) -> torch.Tensor:
+             knn: Optional[int] = None, hull: Optional[bool] = None) -> torch.Tensor:
         if batch is not None and points is not None:
             raise ValueError("step: pass batch=... (lifted on the host) or points=... (lifted on the device), not both")
         if batch is not None:
             self.load_batch(batch)
         if points is not None:
-            self.load_points(points, dis, vertex_features, knn)
+            self.load_points(points, dis, vertex_features, knn, hull)
         if features:
             self.load(features)
         self.graph.replay()

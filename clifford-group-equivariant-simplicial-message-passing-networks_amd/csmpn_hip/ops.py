@@ -1417,7 +1417,7 @@ def simplex_tables(x_ind, node_types, x_ind_batch, x_ind_ptr, max_dim, rows, ver
 
 # --------------------------------------------------------------------------------- the Rips lift of a batch on the device
 
-# bits of the status word of rips_lift / knn_lift; bit d (d = 1, 2) = more d-simplices than the capacity
+# bits of the status word of rips_lift / knn_lift / hull_lift; bit d (d = 1, 2) = more d-simplices than the capacity
 LIFT_STATUS_EDGES, LIFT_STATUS_NO_FILLER_ROW = 8, 16
 
 
@@ -1429,7 +1429,7 @@ def rips_lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, devic
 
 def _lift_arguments(what, points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch, x_ind_batch, ptr,
                     x_ind_ptr, edge_index, edge_types, counts, status):
-    """The tensor validation rips_lift and knn_lift share; returns (B, V, E, the capacity rows as a C array)."""
+    """The tensor validation rips_lift, knn_lift and hull_lift share; returns (B, V, E, the capacity rows as a C array)."""
     if not points.is_cuda:
         raise RuntimeError(f"{what} needs device tensors (no CPU fallback)")
     if points.dtype != torch.float32 or points.dim() != 2 or not points.is_contiguous():
@@ -1492,3 +1492,29 @@ def knn_lift(points, n_graphs, k, max_dim, capacity_rows, capacity_edges, x_ind,
             x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), batch.data_ptr(), x_ind_batch.data_ptr(), ptr.data_ptr(),
             x_ind_ptr.data_ptr(), edge_index.data_ptr(), _ptr(edge_types), _ptr(counts), _ptr(status), workspace.data_ptr(),
             workspace.numel(), _stream(dev)))
+
+
+def hull_lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, device) -> torch.Tensor:
+    """Workspace of hull_lift (uninitialised device bytes)."""
+    return torch.empty(max(int(native.lib().csmpn_hull_lift_workspace_bytes(int(n_graphs), int(verts_per_graph), int(max_dim))), 16),
+                       dtype=torch.uint8, device=device)
+
+
+def hull_lift(points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch, x_ind_batch, ptr, x_ind_ptr,
+              edge_index, edge_types, counts, status, workspace, volume=None):
+    """csmpn_hull_lift: rips_lift for the convex-hull complex - the structure tensors of
+    pad_batch(collate([hull_complex(points of graph g, max_dim, method="exact")]), capacity), same buffers, same status bits -
+    and the hulls' volumes (csmpn.data.complexes.hull_facets) into `volume` (None or a contiguous float32 device tensor
+    [B]), which a batch that does not fit leaves as it was, too. Points in R^2 .. R^5, at most 16 per graph."""
+    B, V, E, cap = _lift_arguments("hull_lift", points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch,
+                                   x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status)
+    dev = points.device
+    if volume is not None and (volume.dtype != torch.float32 or not volume.is_contiguous() or volume.device != dev
+                               or tuple(volume.shape) != (B,)):
+        raise RuntimeError(f"hull_lift: volume must be a contiguous float32 tensor [{B}] on the device of points")
+    with torch.cuda.device(dev):
+        check(native.lib().csmpn_hull_lift(
+            points.data_ptr(), int(points.shape[1]), B, V, int(max_dim), C.addressof(cap), E,
+            x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), batch.data_ptr(), x_ind_batch.data_ptr(), ptr.data_ptr(),
+            x_ind_ptr.data_ptr(), edge_index.data_ptr(), _ptr(edge_types), _ptr(counts), _ptr(status), _ptr(volume),
+            workspace.data_ptr(), workspace.numel(), _stream(dev)))

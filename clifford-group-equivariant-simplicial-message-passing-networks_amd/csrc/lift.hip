@@ -7,6 +7,10 @@
 // csmpn_knn_lift is the same lift of the clique complex of the k-nearest-neighbour graph (knn_clique_complex): another
 // kernel produces the neighbour masks, and the adjacencies have no 0_0 block over the non-edges (kVertexBlock = false).
 //
+// csmpn_hull_lift is the same lift of the convex-hull complex (hull_complex(method="exact")) with the hull's volume: its
+// kernel finds the facets among the subsets of point_dim vertices and writes, beside the masks, a table T[a][b] of the w with
+// {a, b, w} in a facet - the triangles and cofaces of an edge come from T, not from the masks (kFacetTable = true).
+//
 // A graph has at most 64 vertices, so ONE 64-bit neighbour mask per vertex (a wave ballot over the other vertices) carries
 // it, and every index is a popcount of masks plus a scan: with upper[a] = mask[a] restricted to b > a,
 //   index of the edge (a, b), a < b      = sum_{a' < a} popc(upper[a']) + popc(upper[a] & below(b))
@@ -15,7 +19,8 @@
 // Both scans are kept per vertex a (64 entries in LDS); the part inside a's row of edges is a wave scan over the lanes b.
 //
 //   count    one workgroup per graph: the masks -> workspace, the graph's numbers of 1- and 2-simplices
-//            (lift_count_kernel: pairs within dis; lift_knn_kernel: the symmetrised k nearest neighbours)
+//            (lift_count_kernel: pairs within dis; lift_knn_kernel: the symmetrised k nearest neighbours;
+//            lift_hull_kernel<N>: the pairs and triples inside a facet, and the volume)
 //   offsets  ONE workgroup: the totals against the capacity -> fit flag, status word; where the batch fits, the scan of the
 //            graphs' row and adjacency counts (256 graphs per pass) -> ptr / x_ind_ptr, counts, the offsets of every graph
 //   scatter  one workgroup per graph + workgroups for the fillers; all of them return at once when the fit flag is clear,
@@ -186,6 +191,181 @@ __global__ __launch_bounds__(kBlock) void lift_knn_kernel(const float* points, i
     if (wave == 0) count_tail(m, g, V, max_dim, lane, masks, n1, n2);
 }
 
+// ------------------------------------------------------------------------------------------------ the convex-hull lift
+//
+// A graph has V <= 16 points in R^N, N = 2..5. A candidate is an N-subset F = (f_0 < ... < f_{N-1}); with the rows
+// M_i = p_{f_{i+1}} - p_{f_0} (i = 0..N-2), its normal is nrm_j = (-1)^(N-1+j) det(M without column j), and
+// side(F, q) = sum_j nrm_j (q_j - p_{f_0, j}). F is a facet iff side(F, q) > 0 for every vertex q outside F, or < 0 for
+// every one (a zero or a NaN: no facet). Everything in double, every product, sum and difference rounded once; the order of
+// operations below is the one csmpn.data.complexes.hull_facets states on the host:
+//   det of one entry = the entry; det of k rows = the Laplace expansion along the first of them over the columns c_0 < c_1 < ..:
+//     ((M[c_0] det_0 - M[c_1] det_1) + M[c_2] det_2) - ...   (left to right, each product rounded before it is added);
+//   side = ((nrm_0 d_0 + nrm_1 d_1) + nrm_2 d_2) + ..., d_j = q_j - p_{f_0, j}.
+// Volume = (sum over the facets of |side(F, p_0)|) / N!: a thread sums the candidates rank = tid, tid + 256, ... ascending
+// (rank = the lexicographic index of F), a wave adds lane + 32, + 16, ... + 1 into lane 0, wave 0's sum takes those of waves
+// 1, 2, 3 in that order.
+
+constexpr int kHullMaxVerts = 16;                             // C(16, 5) = 4368 candidates; the T table is 16 x 16 masks
+
+// Rounded once, never contracted into an fma. The unit is built with -ffp-contract=fast, under which the backend fuses any
+// product into the sum that takes it, whatever a pragma or __dmul_rn says; so the product is an instruction of its own that
+// the optimiser cannot look into (pure: equal products are still computed once), and with it no sum has a product to fuse.
+__device__ __forceinline__ double mul_rn(double x, double y) {
+    double r;
+    asm("v_mul_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+    return r;
+}
+__device__ __forceinline__ double add_rn(double x, double y) { return x + y; }
+__device__ __forceinline__ double sub_rn(double x, double y) { return x - y; }
+
+constexpr int low_bit(unsigned m) { return (m & 1u) ? 0 : 1 + low_bit(m >> 1); }
+constexpr int bits_of(unsigned m) { return m ? 1 + bits_of(m & (m - 1)) : 0; }
+
+template <int N, int Row, unsigned Cols>
+__device__ __forceinline__ double minor_det(const double (&M)[N - 1][N]);
+
+// the terms of the expansion along row Row that are still to come (the columns in Rest), K of them taken
+template <int N, int Row, unsigned Cols, unsigned Rest, int K>
+__device__ __forceinline__ double laplace(const double (&M)[N - 1][N], double acc) {
+    if constexpr (Rest == 0u) {
+        return acc;
+    } else {
+        constexpr int c = low_bit(Rest);
+        const double term = mul_rn(M[Row][c], minor_det<N, Row + 1, (Cols & ~(1u << c))>(M));
+        const double next = K == 0 ? term : (K & 1) ? sub_rn(acc, term) : add_rn(acc, term);
+        return laplace<N, Row, Cols, (Rest & (Rest - 1u)), K + 1>(M, next);
+    }
+}
+
+// determinant of the rows Row .. N-2 and the columns in Cols (as many as rows)
+template <int N, int Row, unsigned Cols>
+__device__ __forceinline__ double minor_det(const double (&M)[N - 1][N]) {
+    static_assert(bits_of(Cols) == N - 1 - Row, "as many columns as rows");
+    if constexpr (bits_of(Cols) == 1)
+        return M[Row][low_bit(Cols)];
+    else
+        return laplace<N, Row, Cols, Cols, 0>(M, 0.0);
+}
+
+template <int N, int J>
+__device__ __forceinline__ void normal_of(const double (&M)[N - 1][N], double (&nrm)[N]) {
+    if constexpr (J < N) {
+        const double d = minor_det<N, 0, (((1u << N) - 1u) & ~(1u << J))>(M);
+        nrm[J] = ((N - 1 + J) & 1) ? -d : d;
+        normal_of<N, J + 1>(M, nrm);
+    }
+}
+
+template <int N>
+__device__ __forceinline__ double side_of(const double (&nrm)[N], const double* q, const double* origin) {
+    double s = mul_rn(nrm[0], sub_rn(q[0], origin[0]));
+#pragma unroll
+    for (int j = 1; j < N; ++j) s = add_rn(s, mul_rn(nrm[j], sub_rn(q[j], origin[j])));
+    return s;
+}
+
+// C(m, K) for 0 <= m <= 16 (0 for m < K); every intermediate is an integer
+template <int K>
+__device__ __forceinline__ int choose(int m) {
+    int r = 1;
+#pragma unroll
+    for (int t = 0; t < K; ++t) r = r * (m - t) / (t + 1);
+    return r;
+}
+
+// f = the rank-th N-subset of 0 .. V-1 in lexicographic order, rank < C(V, N)
+template <int N, int I>
+__device__ __forceinline__ void unrank(int V, int r, int x, int (&f)[N]) {
+    if constexpr (I < N) {
+        for (; x < V - (N - I); ++x) {                        // at the bound x is the only choice left
+            const int c = choose<N - 1 - I>(V - 1 - x);       // subsets whose I-th element is x
+            if (r < c) break;
+            r -= c;
+        }
+        f[I] = x;
+        unrank<N, I + 1>(V, r, x + 1, f);
+    }
+}
+
+// one workgroup per graph: the facets among the C(V, N) candidates -> mask[a] bit b = {a, b} lies in a facet, T[a][b] bit w =
+// {a, b, w} lies in a facet (both ORed together in LDS: the result does not depend on the order), the counts n1 and n2 and
+// the volume -> workspace. No output is touched: the scatter kernel copies the volume once the batch is known to fit.
+template <int N>
+__global__ __launch_bounds__(kBlock) void lift_hull_kernel(const float* points, int V, int n_cand, int max_dim, u64* masks, u64* tables,
+                                                            int* n1, int* n2, float* vols) {
+    __shared__ double p[kHullMaxVerts * N];
+    __shared__ u64 m[kHullMaxVerts], T[kHullMaxVerts * kHullMaxVerts];
+    __shared__ double part[kWaves];
+    const long g = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* pg = points + g * V * (long)N;
+    if (tid < V * N) p[tid] = (double)pg[tid];                // V N <= 80
+    if (tid < kHullMaxVerts) m[tid] = 0ull;
+    T[tid] = 0ull;                                            // kBlock == 16 x 16
+    __syncthreads();
+    double vol = 0.0;
+    for (int rank = tid; rank < n_cand; rank += kBlock) {
+        int f[N];
+        unrank<N, 0>(V, rank, 0, f);
+        const double* origin = p + f[0] * N;
+        double M[N - 1][N], nrm[N];
+        u64 fb = 1ull << f[0];
+#pragma unroll
+        for (int i = 1; i < N; ++i) {
+            fb |= 1ull << f[i];
+#pragma unroll
+            for (int j = 0; j < N; ++j) M[i - 1][j] = sub_rn(p[f[i] * N + j], origin[j]);
+        }
+        normal_of<N, 0>(M, nrm);
+        bool pos = true, neg = true;
+        for (int q = 0; q < V; ++q) {
+            if ((fb >> q) & 1ull) continue;
+            const double s = side_of<N>(nrm, p + q * N, origin);
+            pos = pos && s > 0.0;
+            neg = neg && s < 0.0;
+        }
+        if (!(pos || neg)) continue;
+        vol = add_rn(vol, fabs(side_of<N>(nrm, p, origin)));
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const u64 others = fb & ~(1ull << f[i]);
+            atomicOr(&m[f[i]], others);
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+                if (j != i) atomicOr(&T[f[i] * kHullMaxVerts + f[j]], others & ~(1ull << f[j]));
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) vol = add_rn(vol, __shfl_down(vol, d, 64));
+    if (lane == 0) part[wave] = vol;
+    __syncthreads();
+    if (wave != 0) return;
+    int c1 = 0, c2 = 0;
+    if (lane < V) {
+        const u64 ma = m[lane], up = ma & above(lane);
+        masks[g * V + lane] = ma;
+        c1 = __popcll(up);
+        if (max_dim >= 2)
+            for (u64 r = up; r; r &= r - 1) {
+                const int b = first_bit(r);
+                c2 += __popcll(T[lane * kHullMaxVerts + b] & above(b));
+            }
+    }
+    for (int i = lane; i < V * V; i += 64) tables[g * V * V + i] = T[(i / V) * kHullMaxVerts + i % V];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        c1 += __shfl_down(c1, d, 64);
+        c2 += __shfl_down(c2, d, 64);
+    }
+    if (lane == 0) {
+        n1[g] = c1;
+        n2[g] = c2;
+        double fact = 1.0;
+        for (int i = 2; i <= N; ++i) fact *= i;
+        vols[g] = (float)(add_rn(add_rn(add_rn(part[0], part[1]), part[2]), part[3]) / fact);
+    }
+}
+
 // one workgroup: totals against the capacity; if the batch fits, the offsets of every graph and ptr / x_ind_ptr / counts.
 // kVertexBlock: a graph's adjacencies hold the 0_0 block over the non-edges (Rips), V (V - 1) + 5 n1 + 12 n2 of them; without
 // it (kNN cliques) 6 n1 + 12 n2. A template parameter, here and in the scatter kernel: the Rips instantiations are the
@@ -268,10 +448,20 @@ __global__ __launch_bounds__(kBlock) void lift_offsets_kernel(const int* n1, con
 //   6  1_2  for every triangle t = (a, b, c): ((a, b), t), ((a, c), t), ((b, c), t)                         3 n2
 //   7  2_1  the flips of block 6                                                                            3 n2
 // A wave takes the vertices a = wave, wave + 4, ...; its lane b holds the pair (a, b).
-template <bool kVertexBlock>
-__device__ void scatter_graph(long g, int V, int max_dim, const u64* masks, const int* n1s, const int* n2s,
+// kFacetTable (the hull lift, V <= 16): a triple is a 2-simplex iff it lies in a facet, not iff its pairs are edges, so the
+// triangles of the edge (a, b) are T[a][b] & above(b) and its cofaces T[a][b], T = `tables` [V, V] of graph g loaded into
+// LDS, instead of the intersections of the neighbour masks. A template parameter for the reason kVertexBlock is one: the
+// Rips and kNN instantiations carry neither the table nor a branch on it.
+template <bool kVertexBlock, bool kFacetTable>
+__device__ void scatter_graph(long g, int V, int max_dim, const u64* masks, const u64* tables, const int* n1s, const int* n2s,
                               const long long* row_off, const long long* adj_off, const Outputs& o) {
     __shared__ u64 m[kMaxVerts];
+    const u64* T = nullptr;
+    if constexpr (kFacetTable) {
+        __shared__ u64 table_s[kHullMaxVerts * kHullMaxVerts];
+        if ((int)threadIdx.x < V * V) table_s[(threadIdx.x / V) * kHullMaxVerts + threadIdx.x % V] = tables[g * V * V + threadIdx.x];
+        T = table_s;
+    }
     __shared__ int deg_s[kMaxVerts], up_s[kMaxVerts], tri_s[kMaxVerts], cof_s[kMaxVerts];   // sums over the vertices in front
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < kMaxVerts) m[tid] = tid < V ? masks[g * V + tid] : 0ull;
@@ -283,8 +473,9 @@ __device__ void scatter_graph(long g, int V, int max_dim, const u64* masks, cons
             for (u64 r = up; r; r &= r - 1) {
                 const int b = first_bit(r);
                 const u64 mb = m[b];
-                t += __popcll(up & mb & above(b));
-                c += __popcll(ma & mb);
+                const u64 cof = kFacetTable ? T[lane * kHullMaxVerts + b] : ma & mb;
+                t += __popcll(kFacetTable ? cof & above(b) : up & mb & above(b));
+                c += __popcll(cof);
             }
         deg_s[lane] = wave_scan(__popcll(ma), lane, nullptr);
         up_s[lane] = wave_scan(__popcll(up), lane, nullptr);
@@ -305,8 +496,9 @@ __device__ void scatter_graph(long g, int V, int max_dim, const u64* masks, cons
             put_adj(o, o2 + (long long)a * (V - 1) - up_s[a] + lane - (lane > a ? 1 : 0) - __popcll(up & below(lane)), row0 + a,
                     row0 + lane, 0, 0);
         const bool edge = (up >> lane) & 1ull;                // the pair (a, lane), a < lane, is an edge
-        const u64 tri = edge && max_dim >= 2 ? up & mb & above(lane) : 0ull;     // its triangles (a, lane, c)
-        const u64 cof = edge && max_dim >= 2 ? ma & mb : 0ull;                   // its cofaces {a, lane, w}
+        const u64 both = kFacetTable ? (edge ? T[a * kHullMaxVerts + lane] : 0ull) : ma & mb;
+        const u64 tri = edge && max_dim >= 2 ? (kFacetTable ? both : up & mb) & above(lane) : 0ull;   // its triangles (a, lane, c)
+        const u64 cof = edge && max_dim >= 2 ? both : 0ull;                      // its cofaces {a, lane, w}
         const long long tb = tri_s[a] + wave_scan(__popcll(tri), lane, nullptr);
         const long long cb = cof_s[a] + wave_scan(__popcll(cof), lane, nullptr);
         if (!edge) continue;
@@ -368,9 +560,23 @@ __global__ __launch_bounds__(kBlock) void lift_scatter_kernel(long B, int V, int
                                                                const long long* adj_off, Outputs o) {
     if (!hdr->fit) return;
     if ((long)blockIdx.x < B)
-        scatter_graph<kVertexBlock>((long)blockIdx.x, V, max_dim, masks, n1, n2, row_off, adj_off, o);
+        scatter_graph<kVertexBlock, false>((long)blockIdx.x, V, max_dim, masks, nullptr, n1, n2, row_off, adj_off, o);
     else
         scatter_fillers((long)blockIdx.x - B, (long)gridDim.x - B, B, max_dim, cap, hdr, o);
+}
+
+// the scatter of the hull lift: the vertex block, the facet table, and the volumes from the workspace to their output
+__global__ __launch_bounds__(kBlock) void lift_hull_scatter_kernel(long B, int V, int max_dim, Capacity cap, const Header* hdr,
+                                                                    const u64* masks, const u64* tables, const int* n1, const int* n2,
+                                                                    const long long* row_off, const long long* adj_off,
+                                                                    const float* vols, float* volume, Outputs o) {
+    if (!hdr->fit) return;
+    if ((long)blockIdx.x < B) {
+        if (volume && threadIdx.x == 0) volume[blockIdx.x] = vols[blockIdx.x];
+        scatter_graph<true, true>((long)blockIdx.x, V, max_dim, masks, tables, n1, n2, row_off, adj_off, o);
+    } else {
+        scatter_fillers((long)blockIdx.x - B, (long)gridDim.x - B, B, max_dim, cap, hdr, o);
+    }
 }
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -379,11 +585,14 @@ inline bool sizes_ok(int64_t n_graphs, int32_t V, int32_t max_dim) {
     return (max_dim == 1 || max_dim == 2) && V > max_dim && V <= kMaxVerts && n_graphs > 0 && n_graphs < (1ll << 31) / V;
 }
 
-inline size_t workspace_bytes_of(int64_t n_graphs, int32_t V, int32_t max_dim) {
-    if (!sizes_ok(n_graphs, V, max_dim)) return 0;
+enum class Lift { rips, knn, hull };
+
+inline size_t workspace_bytes_of(int64_t n_graphs, int32_t V, int32_t max_dim, Lift kind = Lift::rips) {
+    if (!sizes_ok(n_graphs, V, max_dim) || (kind == Lift::hull && V > kHullMaxVerts)) return 0;
     const size_t B = (size_t)n_graphs;
-    // alignment slack + header | masks | n1 | n2 | row offsets | adjacency offsets
-    return 256 + 256 + align256(sizeof(u64) * B * (size_t)V) + 2 * align256(sizeof(int) * B) + 2 * align256(sizeof(long long) * B);
+    // alignment slack + header | masks | n1 | n2 | row offsets | adjacency offsets; the hull lift: | T tables | volumes
+    const size_t hull = kind == Lift::hull ? align256(sizeof(u64) * B * (size_t)V * (size_t)V) + align256(sizeof(float) * B) : 0;
+    return 256 + 256 + align256(sizeof(u64) * B * (size_t)V) + 2 * align256(sizeof(int) * B) + 2 * align256(sizeof(long long) * B) + hull;
 }
 
 struct LiftArgs {                // what csmpn_rips_lift and csmpn_knn_lift share
@@ -402,17 +611,22 @@ struct LiftArgs {                // what csmpn_rips_lift and csmpn_knn_lift shar
     void* stream;
 };
 
-// the checks both entries share, before the first HIP call; `what` names the entry in the messages. dis >= 0: the Rips
-// threshold, knn_k: the k of the kNN entry (0 for the Rips entry) - each checked where csmpn_rips_lift has always checked dis.
-int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, bool knn, Capacity* cap) {
+// the checks the entries share, before the first HIP call; `what` names the entry in the messages. dis >= 0: the Rips
+// threshold, knn_k: the k of the kNN entry (0 for the others) - each checked where csmpn_rips_lift has always checked dis; the
+// hull entry checks its point dimension there, and its 16 vertices where the others check their 64.
+int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, Lift kind, Capacity* cap) {
     const int V = a.verts_per_graph, max_dim = a.max_dim;
+    const bool knn = kind == Lift::knn, hull = kind == Lift::hull;
     if (max_dim < 0) return csmpn_fail(CSMPN_ERR_INVALID, "max_dim %d is negative", max_dim);
     if (max_dim != 1 && max_dim != 2) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: max_dim %d (1 or 2)", what, max_dim);
+    if (hull && V > kHullMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > %d (every subset of point_dim vertices is tried)", what, V, kHullMaxVerts);
     if (V > kMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > %d (one 64-bit mask per vertex)", what, V, kMaxVerts);
     if (V <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "%s: %d vertices per graph, max_dim %d needs %d", what, V, max_dim, max_dim + 1);
     if (a.n_graphs <= 0 || a.n_graphs >= (1ll << 31) / V) return csmpn_fail(CSMPN_ERR_INVALID, "bad sizes n_graphs=%lld verts_per_graph=%d", (long long)a.n_graphs, V);
     if (a.point_dim <= 0) return csmpn_fail(CSMPN_ERR_INVALID, "point_dim %d", (int)a.point_dim);
-    if (!knn && !(dis >= 0.0)) return csmpn_fail(CSMPN_ERR_INVALID, "dis %g is negative or not a number", dis);
+    if (hull && (a.point_dim < 2 || a.point_dim > 5)) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: points in R^%d (2 .. 5)", what, (int)a.point_dim);
+    if (hull && V <= a.point_dim) return csmpn_fail(CSMPN_ERR_INVALID, "%s: %d vertices per graph in R^%d (a hull needs %d)", what, V, (int)a.point_dim, (int)a.point_dim + 1);
+    if (!knn && !hull && !(dis >= 0.0)) return csmpn_fail(CSMPN_ERR_INVALID, "dis %g is negative or not a number", dis);
     if (knn && knn_k < 1) return csmpn_fail(CSMPN_ERR_INVALID, "%s: k = %d (at least 1)", what, knn_k);
     if (a.x_ind_cols <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "x_ind has %d columns, max_dim %d needs %d", (int)a.x_ind_cols, max_dim, max_dim + 1);
     if (!a.points || !a.capacity_rows || !a.x_ind || !a.node_types || !a.batch || !a.x_ind_batch || !a.ptr || !a.x_ind_ptr || !a.edge_index)
@@ -428,14 +642,16 @@ int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, 
         return csmpn_fail(CSMPN_ERR_INVALID, "capacity_rows[0] = %lld, the batch has %lld vertices (vertex rows are never padded)", cap->rows[0], (long long)(a.n_graphs * V));
     if (total >= (1ll << 31) || cap->edges < 0 || cap->edges >= (1ll << 31))
         return csmpn_fail(CSMPN_ERR_INVALID, "bad capacity: %lld rows, %lld adjacencies", total, cap->edges);
-    const size_t need = workspace_bytes_of(a.n_graphs, V, max_dim);
+    const size_t need = workspace_bytes_of(a.n_graphs, V, max_dim, kind);
     if (!a.workspace || a.workspace_bytes < need) return csmpn_fail(CSMPN_ERR_INVALID, "%s workspace too small: %zu < %zu", what, a.workspace_bytes, need);
     return CSMPN_OK;
 }
 
 // Behind the argument checks: the workspace carved up, then the three launches. knn_k = 0: the masks of the pairs within
-// `dis` and the adjacencies with the vertex block (Rips); knn_k >= 1: the masks of the k nearest neighbours, no vertex block.
-int launch_lift(const char* what, const LiftArgs& a, const Capacity& cap, double dis, int knn_k) {
+// `dis` and the adjacencies with the vertex block (Rips); knn_k >= 1: the masks of the k nearest neighbours, no vertex block;
+// kind == Lift::hull: the masks and the T tables of the facets, the vertex block, the volumes -> `volume` (may be null).
+int launch_lift(const char* what, const LiftArgs& a, const Capacity& cap, double dis, int knn_k, Lift kind = Lift::rips,
+                float* volume = nullptr) {
     hipStream_t st = (hipStream_t)a.stream;
     const int V = a.verts_per_graph, max_dim = a.max_dim, P = a.point_dim;
     const size_t B = (size_t)a.n_graphs;
@@ -451,11 +667,32 @@ int launch_lift(const char* what, const LiftArgs& a, const Capacity& cap, double
     long long* row_off = reinterpret_cast<long long*>(ws);
     ws += align256(sizeof(long long) * B);
     long long* adj_off = reinterpret_cast<long long*>(ws);
+    ws += align256(sizeof(long long) * B);
+    const bool hull = kind == Lift::hull;                                                  // its workspace alone has these bytes
+    u64* tables = hull ? reinterpret_cast<u64*>(ws) : nullptr;
+    float* vols = hull ? reinterpret_cast<float*>(ws + align256(sizeof(u64) * B * (size_t)V * (size_t)V)) : nullptr;
     Outputs out{a.x_ind, a.node_types, a.batch, a.x_ind_batch, a.edge_index, a.edge_types, (int)a.x_ind_cols, cap.edges};
     const long long fill_items = std::max(cap.rows[1] + cap.rows[2], cap.edges);
     const long fill_blocks = (long)std::min<long long>(std::max<long long>((fill_items + kBlock - 1) / kBlock, 1), kMaxFillBlocks);
     const dim3 per_graph((unsigned)B), one(1), scatter((unsigned)(B + fill_blocks)), block(kBlock);
-    if (knn_k > 0) {
+    if (hull) {
+        int n_cand = 1;                                                                    // C(V, P) <= C(16, 5)
+        for (int t = 0; t < P; ++t) n_cand = n_cand * (V - t) / (t + 1);
+#define CSMPN_HULL_COUNT(N)                                                                                                       \
+    hipLaunchKernelGGL(lift_hull_kernel<N>, per_graph, block, 0, st, a.points, V, n_cand, max_dim, masks, tables, n1, n2, vols)
+        switch (P) {
+            case 2: CSMPN_HULL_COUNT(2); break;
+            case 3: CSMPN_HULL_COUNT(3); break;
+            case 4: CSMPN_HULL_COUNT(4); break;
+            default: CSMPN_HULL_COUNT(5); break;
+        }
+#undef CSMPN_HULL_COUNT
+        hipLaunchKernelGGL(lift_offsets_kernel<true>, one, block, 0, st, (const int*)n1, (const int*)n2, (long)B, V, max_dim, cap, hdr,
+                           row_off, adj_off, a.ptr, a.x_ind_ptr, a.counts, (unsigned*)a.status);
+        hipLaunchKernelGGL(lift_hull_scatter_kernel, scatter, block, 0, st, (long)B, V, max_dim, cap, (const Header*)hdr, (const u64*)masks,
+                           (const u64*)tables, (const int*)n1, (const int*)n2, (const long long*)row_off, (const long long*)adj_off,
+                           (const float*)vols, volume, out);
+    } else if (knn_k > 0) {
         hipLaunchKernelGGL(lift_knn_kernel, per_graph, block, 0, st, a.points, P, V, knn_k, max_dim, masks, n1, n2);
         hipLaunchKernelGGL(lift_offsets_kernel<false>, one, block, 0, st, (const int*)n1, (const int*)n2, (long)B, V, max_dim, cap, hdr,
                            row_off, adj_off, a.ptr, a.x_ind_ptr, a.counts, (unsigned*)a.status);
@@ -492,7 +729,7 @@ int csmpn_rips_lift(const float* points, int32_t point_dim, int64_t n_graphs, in
     const LiftArgs a{points, point_dim, n_graphs, verts_per_graph, max_dim, capacity_rows, capacity_edges, x_ind, x_ind_cols, node_types,
                      batch, x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status, workspace, workspace_bytes, stream};
     Capacity cap{};
-    if (const int rc = check_lift_args("rips lift", a, dis, 0, false, &cap)) return rc;
+    if (const int rc = check_lift_args("rips lift", a, dis, 0, Lift::rips, &cap)) return rc;
     return launch_lift("rips lift", a, cap, dis, 0);
 }
 
@@ -503,8 +740,23 @@ int csmpn_knn_lift(const float* points, int32_t point_dim, int64_t n_graphs, int
     const LiftArgs a{points, point_dim, n_graphs, verts_per_graph, max_dim, capacity_rows, capacity_edges, x_ind, x_ind_cols, node_types,
                      batch, x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status, workspace, workspace_bytes, stream};
     Capacity cap{};
-    if (const int rc = check_lift_args("knn lift", a, 0.0, (int)k, true, &cap)) return rc;
+    if (const int rc = check_lift_args("knn lift", a, 0.0, (int)k, Lift::knn, &cap)) return rc;
     return launch_lift("knn lift", a, cap, 0.0, (int)k);
+}
+
+size_t csmpn_hull_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim) {
+    return workspace_bytes_of(n_graphs, verts_per_graph, max_dim, Lift::hull);
+}
+
+int csmpn_hull_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim,
+                    const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                    int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                    int64_t* counts, uint32_t* status, float* volume, void* workspace, size_t workspace_bytes, void* stream) {
+    const LiftArgs a{points, point_dim, n_graphs, verts_per_graph, max_dim, capacity_rows, capacity_edges, x_ind, x_ind_cols, node_types,
+                     batch, x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status, workspace, workspace_bytes, stream};
+    Capacity cap{};
+    if (const int rc = check_lift_args("hull lift", a, 0.0, 0, Lift::hull, &cap)) return rc;
+    return launch_lift("hull lift", a, cap, 0.0, 0, Lift::hull, volume);
 }
 
 }  // extern "C"

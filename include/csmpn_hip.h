@@ -484,6 +484,33 @@ int csmpn_knn_lift(const float* points, int32_t point_dim, int64_t n_graphs, int
                    int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
                    int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same lift of the convex-hull complex of verts_per_graph points in R^point_dim, and the hull's volume: the structure
+ * tensors of exactly the batch that
+ *   pad_batch(collate([hull_complex(points_g, max_dim, method="exact") for g]), BatchCapacity(capacity_rows, capacity_edges))
+ * builds on the host. Every argument of csmpn_rips_lift but `dis`, every contract (three launches on `stream`, no allocation,
+ * no host round trip, no atomic on an output), the status bits 1..4 of a batch that does not fit (every output, `volume`
+ * included, is left as it was) and the adjacency order with the 0_0 block over the non-edges are those of csmpn_rips_lift.
+ *   With n = point_dim, a candidate is an n-subset F = (f_0 < ... < f_{n-1}) of a graph's vertices. Its rows are
+ *   M_i = p_{f_{i+1}} - p_{f_0}, i = 0..n-2; its normal is N_j = (-1)^(n-1+j) det(M without column j), a determinant being
+ *   the Laplace expansion along its first row over the columns ascending, ((M[c0] d0 - M[c1] d1) + M[c2] d2) - ...; and
+ *   side(F, q) = sum_j N_j (q_j - p_{f_0, j}), j ascending. All of it in double on the float points, every product, sum and
+ *   difference rounded once, none contracted. F is a facet iff side(F, q) > 0 for every vertex q of the graph outside F, or
+ *   < 0 for every one; a zero or a NaN makes F no facet. Coplanar point sets, coincident points and NaN vertices therefore
+ *   give fewer facets, or none: what qhull does with degenerate input (merged or joggled facets) is NOT restated. On points
+ *   in general position this is the facet set of the hull. The 1-simplices are the pairs and, for max_dim = 2, the
+ *   2-simplices the triples that lie in a facet (a triple whose three pairs are edges need not be one).
+ *   volume (device, float [n_graphs], may be NULL): (sum over the facets of |side(F, p_0)|) / n!, summed in double in the
+ *   fixed order csmpn.data.complexes.hull_facets states: the same bits in every call.
+ * Limits: point_dim in 2..5 and verts_per_graph <= 16, else CSMPN_ERR_UNSUPPORTED; verts_per_graph > point_dim, else
+ * CSMPN_ERR_INVALID; otherwise those of csmpn_rips_lift.
+ * workspace: csmpn_hull_lift_workspace_bytes(...) bytes (larger than the other two lifts': the facet tables; 0 for sizes the
+ * entry point rejects); needs no initialisation. */
+size_t csmpn_hull_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim);
+int csmpn_hull_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim,
+                    const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                    int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                    int64_t* counts, uint32_t* status, float* volume, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fused simplex feature embedding (round 3; hulls_cssmpnn.py:96-125: vertex features of every d-simplex in all (d+1)!
  * vertex orders -> CEMLP -> sum over the orders), for the shapes the wide parity-lane kernels serve as standalone CEMLPs
  * (Cl(5,0) / Cl(4,1), 16 / 24 / 28 / 32 output channels, at most 8 input channels = verts_per_row * channels_per_vertex);

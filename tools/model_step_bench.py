@@ -21,6 +21,9 @@ JSON line with the step times and the simplices / adjacencies of the batch.
 --knn K (with --device-lift, md17): the batches are the clique complexes of the K-nearest-neighbour graphs
   (knn_clique_complex: the reference's aspirin configuration has K = 3) instead of Rips complexes, lifted on the device by
   step(points=..., knn=K) (csmpn_knn_lift); the same four figures, and the capacity's rows / adjacencies
+--model hulls --varying K --device-lift: the K batches of convex hulls through step(points=..., hull=True) (csmpn_hull_lift:
+  the complex, `input` and the volume target all from the device points); the host figure is qhull + lift + collate +
+  pad_batch of one batch
 --pkg-root: import the package from another tree (a build of another commit) with this same tool file; a tree without
   the capacity interface reports the eager figure only.
 """
@@ -100,8 +103,8 @@ def make_batch(args, rng, cx):
     points they were lifted from and the threshold (lift_points float32 [B * V, n], lift_dis) for --device-lift."""
     points, dis = [], None
     if args.model == "hulls":
-        batch = cx.collate([cx.hulls_example(rng.standard_normal((args.points, 5)).astype(np.float32))
-                            for _ in range(args.batch)])
+        points = [rng.standard_normal((args.points, 5)).astype(np.float32) for _ in range(args.batch)]
+        batch = cx.collate([cx.hulls_example(p) for p in points])
         features = ["input", "target"]
     elif args.model == "motion":
         # motion-capture-shaped batch (motion_cssmpnn.py: Cl(3,0), 16 channels, 4 layers, aggr = mean): 31 joints per
@@ -164,6 +167,8 @@ def make_batch(args, rng, cx):
         batch.lift_points, batch.lift_dis = np.concatenate(points, axis=0), dis
         if args.knn:
             batch.lift_knn = args.knn
+        if args.model == "hulls":
+            batch.lift_hull = True
     return batch, features
 
 
@@ -223,19 +228,24 @@ def device_lift(args, out, cx, gs, batches, features, cap, dev):
     """--device-lift: the same K point sets through step(points=...) - the complexes lifted on the device in front of the
     replay - beside step(batch=pre-lifted host batch) of the same run, and what the host lift of such a batch costs."""
     if not hasattr(gs, "load_points") or not hasattr(batches[0], "lift_points"):
-        raise SystemExit("--device-lift needs a Rips model (md17, motion, nba) and a tree with the device lift")
+        raise SystemExit("--device-lift needs a tree with the device lift")
     K, dis, knn = len(batches), batches[0].lift_dis, getattr(batches[0], "lift_knn", None)
-    how = dict(dis=dis) if knn is None else dict(knn=knn)
-    host = (lambda g: cx.rips_complex(g, dis=dis, max_dim=2)) if knn is None else (lambda g: cx.knn_clique_complex(g, knn, max_dim=2))
-    names = [k for k in features if k != "y"]
+    hull = getattr(batches[0], "lift_hull", False)
+    if hull and not hasattr(cx, "hull_batch_device"):
+        raise SystemExit("--model hulls --device-lift needs a tree with the hull lift")
+    how = dict(hull=True) if hull else dict(dis=dis) if knn is None else dict(knn=knn)
+    host = (lambda g: cx.hull_complex(g, max_dim=2)) if hull else (lambda g: cx.rips_complex(g, dis=dis, max_dim=2)) if knn is None \
+        else (lambda g: cx.knn_clique_complex(g, knn, max_dim=2))
+    names = [] if hull else [k for k in features if k != "y"]      # the hull lift fills `input` and `target` itself
     on_dev = []
     for b in batches:
         vertex = b.node_types == 0
-        on_dev.append((torch.from_numpy(b.lift_points).to(dev), {k: getattr(b, k)[vertex].to(dev) for k in names}, b.y.to(dev)))
+        on_dev.append((torch.from_numpy(b.lift_points).to(dev), {k: getattr(b, k)[vertex].to(dev) for k in names},
+                       None if hull else b.y.to(dev)))
 
     def lifted(i):
         pts, vf, y = on_dev[i % K]
-        return gs.step(features={"y": y}, points=pts, vertex_features=vf, **how)
+        return gs.step(features=None if hull else {"y": y}, points=pts, vertex_features=vf, **how)
 
     out["graphed_device_lift_ms_per_step"] = round(timed(lifted, args.steps), 3)
     out["graphed_host_lifted_ms_per_step"] = round(timed(lambda i: gs.step(batch=batches[i % K]), args.steps), 3)
