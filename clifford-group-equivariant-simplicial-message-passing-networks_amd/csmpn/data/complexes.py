@@ -22,7 +22,11 @@ then lets PyG collate graphs into a batch with `follow_batch=["node_types", "x_i
                                              simplicial_lift) with the adjacencies of
                                              utils.py:322-375 generate_adjacencies, which has NO
                                              fully connected 0-0 block: lift(..., vertex_block=False)
-  collate(complexes)                          the batch the task models read: x_ind (vertex ids
+  clique_complex(points, edge_index,         the same lift of ANY edge list with the reference's finite
+                 edge_th, tri_th)            thresholds (utils.py:183-200): edges longer than edge_th and
+                                             triangles of area above tri_th are dropped, a kept triangle
+                                             brings its pairs back
+  collate(complexes)                        the batch the task models read: x_ind (vertex ids
                                              LOCAL to each graph, as in the reference: x_ind has no
                                              `__inc__`), node_types, edge_index (offset per graph),
                                              batch / ptr / x_ind_batch / x_ind_ptr
@@ -289,6 +293,66 @@ def knn_clique_complex(points: np.ndarray, k: int, max_dim: int = 2) -> Simplici
     return to_complex(V, x_dict, adjs, max_dim)
 
 
+def _gram_dets(points: np.ndarray, triples: np.ndarray) -> np.ndarray:
+    """g = uu vv - uv uv of every triple (a, b, c) [T, 3] in float64: u = p_b - p_a, v = p_c - p_a, uu / vv / uv summed over j
+    ascending, one rounding per difference, product and sum (what csrc/lift.hip takes); 4 area^2 of the triangle, in any
+    dimension. A NaN counts as +infinity."""
+    pts = np.asarray(points, dtype=np.float64)
+    t = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+    uu, vv, uv = np.zeros(len(t)), np.zeros(len(t)), np.zeros(len(t))
+    for j in range(pts.shape[1]):
+        u = pts[t[:, 1], j] - pts[t[:, 0], j]
+        v = pts[t[:, 2], j] - pts[t[:, 0], j]
+        uu, vv, uv = uu + u * u, vv + v * v, uv + u * v
+    g = uu * vv - uv * uv
+    g[np.isnan(g)] = np.inf
+    return g
+
+
+def _thresholds_squared(what: str, edge_th: float, tri_th: float) -> Tuple[float, float]:
+    """(edge_th^2, 4 tri_th^2) in float64 - what s and g are compared against; ValueError for a negative one or a NaN."""
+    edge_th, tri_th = float(edge_th), float(tri_th)
+    if not (edge_th >= 0.0 and tri_th >= 0.0):
+        raise ValueError(f"{what}: edge_th and tri_th must be >= 0 or +infinity, got {edge_th} and {tri_th}")
+    return edge_th * edge_th, 4.0 * tri_th * tri_th
+
+
+def clique_complex(points: np.ndarray, edge_index, edge_th: float = math.inf, tri_th: float = math.inf,
+                   max_dim: int = 2) -> SimplicialComplex:
+    """The thresholded clique lift of ANY graph G on `points` [V, n] (utils.py:151-207 simplicial_lift with finite
+    edge_th / tri_th). edge_index [2, E]: {a, b} is an edge of G iff (a, b) or (b, a) is listed; duplicates and both
+    directions are harmless, self-loops are ignored.
+
+      E_keep = the edges of G with s(a, b) <= edge_th^2 (s of _pair_sums);
+      T_keep = the triples a < b < c whose three pairs are edges of G - not of E_keep - with g <= 4 tri_th^2 (g of _gram_dets:
+               4 area^2, in R^3 the reference's |u x v|^2, and defined in R^2 as well);
+      1-simplices = E_keep and the three pairs of every triple of T_keep (gudhi's insert of a triangle inserts its faces: a kept
+               triangle brings back an edge that edge_th removed), 2-simplices = T_keep.
+
+    The result is NOT a clique complex: three surviving edges need not bound a surviving triangle. Adjacencies: those of
+    lift(..., vertex_block=False). With both thresholds +infinity every comparison holds (a NaN counts as +infinity) and the
+    result on knn_edges(points, k) is knn_clique_complex(points, k)."""
+    pts = np.asarray(points, dtype=np.float64)
+    V = len(pts)
+    ei = np.asarray(edge_index.cpu() if torch.is_tensor(edge_index) else edge_index, dtype=np.int64).reshape(2, -1)
+    if ei.size and (int(ei.min()) < 0 or int(ei.max()) >= V):
+        raise ValueError(f"clique_complex: edge_index names vertices outside 0..{V - 1}")
+    edge_th2, tri_th4 = _thresholds_squared("clique_complex", edge_th, tri_th)
+    adj = np.zeros((V, V), dtype=bool)
+    adj[ei[0], ei[1]] = True
+    adj |= adj.T
+    np.fill_diagonal(adj, False)
+    s = _pair_sums(pts)
+    tops = [(a, b) for a in range(V) for b in range(a + 1, V) if adj[a, b] and s[a, b] <= edge_th2]
+    triples = [(a, b, c) for a in range(V) for b in range(a + 1, V) if adj[a, b]
+               for c in range(b + 1, V) if adj[a, c] and adj[b, c]]
+    if triples:
+        keep = _gram_dets(pts, np.asarray(triples)) <= tri_th4
+        tops += [t for t, k in zip(triples, keep) if k]
+    x_dict, adjs = lift(V, tops, max_dim, vertex_block=False)
+    return to_complex(V, x_dict, adjs, max_dim)
+
+
 class SimplicialBatch:
     """What the task models read from a collated batch (hulls.py:109-122 with
     follow_batch=["node_types", "x_ind"]). Per-simplex feature tensors and per-graph labels are
@@ -397,7 +461,8 @@ class SimplicialBatch:
         return self
 
     def relift_(self, points: torch.Tensor, dis: Optional[float] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
-                knn: Optional[int] = None, hull: bool = False) -> "SimplicialBatch":
+                knn: Optional[int] = None, hull: bool = False, edges: Optional[torch.Tensor] = None,
+                edge_th: Optional[float] = None, tri_th: Optional[float] = None) -> "SimplicialBatch":
         """Make this DEVICE batch hold the Vietoris-Rips complexes of `points` (device float32 [B * V, n], the V vertices of
         graph g contiguous; B and V are this batch's) at threshold `dis`, at the capacity the batch was built with: the
         structure tensors are written by ops.rips_lift (csmpn_rips_lift) as pad_batch(collate([rips_complex(...)]), capacity)
@@ -412,11 +477,21 @@ class SimplicialBatch:
         synchronisation. A complex that does not fit the capacity leaves the batch as it was (the features excepted, which
         land on the old vertex rows) and sets bits in plan()["lift_status"] (ops.rips_lift). The host-side n_real_rows /
         n_real_edges are dropped: the real counts live on the device, in plan()["lift_counts"] (rows per dimension,
-        adjacencies)."""
+        adjacencies).
+
+        edges=... (a device int64 [2, n] list of GLOBAL vertex ids g V + a; (-1, -1) entries are padding) is the fourth choice
+        under the same rule: the thresholded clique complexes clique_complex(points, edges of the graph, edge_th, tri_th) of
+        the listed graph, written by ops.clique_lift (csmpn_clique_lift). edge_th / tri_th (default +infinity each) go with
+        edges=... or knn=...: knn=k with a threshold lifts clique_complex(points, knn_edges(points, k), edge_th, tri_th) through
+        the same entry; knn=k without one is csmpn_knn_lift as before. A threshold with dis or hull is a ValueError. A list
+        with an end outside the batch or across two graphs leaves the batch as it was and sets bit 5 of plan()["lift_status"]."""
         from csmpn_hip import ops
-        if (dis is not None) + (knn is not None) + bool(hull) != 1:
-            raise ValueError("relift_: pass exactly one of dis=... (Rips), knn=... (k-nearest-neighbour cliques) and hull=True "
-                             "(convex hulls)")
+        if (dis is not None) + (knn is not None) + bool(hull) + (edges is not None) != 1:
+            raise ValueError("relift_: pass exactly one of dis=... (Rips), knn=... (k-nearest-neighbour cliques), hull=True "
+                             "(convex hulls) and edges=... (the thresholded cliques of a listed graph)")
+        thresholded = edge_th is not None or tri_th is not None
+        if thresholded and (dis is not None or hull):
+            raise ValueError("relift_: edge_th / tri_th go with edges=... or knn=..., not with dis or hull")
         plan = getattr(self, "_plan", None)
         if plan is None or self._csr is None:
             raise RuntimeError("relift_: call plan() and csr() on the batch first")
@@ -439,7 +514,12 @@ class SimplicialBatch:
             plan["lift_ws"] = _lift_workspace(B, rows[0] // B, max_dim, dev)
             plan["lift_status"] = torch.zeros(1, dtype=torch.int32, device=dev)
             plan["lift_counts"] = torch.zeros(max_dim + 2, dtype=torch.int64, device=dev)
-        if hull:
+        if edges is not None or thresholded:
+            if "clique_lift_ws" not in plan:
+                plan["clique_lift_ws"] = ops.clique_lift_workspace(B, rows[0] // B, max_dim, dev)
+            ths = dict(edge_th=math.inf if edge_th is None else edge_th, tri_th=math.inf if tri_th is None else tri_th)
+            run = lambda p, b, _, *rest: ops.clique_lift(p, b, knn if edges is None else edges, *rest[:-1], plan["clique_lift_ws"], **ths)
+        elif hull:
             target = getattr(self, "target", None) if "target" in self._names else None
             run = lambda p, b, _, *rest: ops.hull_lift(p, b, *rest, volume=target)
         else:
@@ -666,7 +746,9 @@ def pad_batch(batch: "SimplicialBatch", capacity: BatchCapacity, simplex_feature
 # rest in place in front of a replayed step. The clique complex of the k-nearest-neighbour graph (knn_clique_complex, the
 # reference's aspirin configuration) is lifted the same way by csmpn_knn_lift: knn_capacity, knn_batch_device,
 # relift_(points, knn=k); the convex-hull complex (hull_complex(method="exact"), the hulls task) with its volume by
-# csmpn_hull_lift: hull_capacity, hull_batch_device, relift_(points, hull=True).
+# csmpn_hull_lift: hull_capacity, hull_batch_device, relift_(points, hull=True); the thresholded clique complex of any graph
+# (clique_complex: a caller's edge list or the kNN graph, edge_th / tri_th) by csmpn_clique_lift: clique_capacity,
+# clique_batch_device, relift_(points, edges=... | knn=k, edge_th=..., tri_th=...).
 
 
 def _lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, device) -> torch.Tensor:
@@ -715,6 +797,27 @@ def knn_capacity(n_graphs: int, verts_per_graph: int, k: int, max_triangles: int
         raise ValueError("knn_capacity: need n_graphs >= 1, verts_per_graph >= max_dim + 1, k >= 1 and counts >= 0")
     if max_edges is None:
         max_edges = n_graphs * min(k * verts_per_graph, verts_per_graph * (verts_per_graph - 1) // 2)
+    if max_dim == 1:
+        max_triangles = 0
+    rows = (n_graphs * verts_per_graph, max_edges + 1) + ((max_triangles,) if max_dim == 2 else ())
+    return BatchCapacity(rows, clique_adjacencies(max_edges, max_triangles))
+
+
+def clique_capacity(n_graphs: int, verts_per_graph: int, max_edges: Optional[int] = None, max_triangles: Optional[int] = None,
+                    max_dim: int = 2) -> BatchCapacity:
+    """The capacity that serves every batch of n_graphs thresholded clique complexes (clique_complex) on verts_per_graph vertices
+    each with at most max_edges 1-simplices and max_triangles 2-simplices in all (defaults: every pair and every triple,
+    n_graphs C(V, 2) and n_graphs C(V, 3) - a caller's graph has no bound of its own) - with the one spare 1-simplex of
+    rips_capacity. The adjacencies are clique_adjacencies of these counts (no vertex block)."""
+    if max_dim not in (1, 2):
+        raise ValueError("clique_capacity: max_dim must be 1 or 2")
+    if n_graphs < 1 or verts_per_graph < max_dim + 1 or (max_edges is not None and max_edges < 0) or \
+            (max_triangles is not None and max_triangles < 0):
+        raise ValueError("clique_capacity: need n_graphs >= 1, verts_per_graph >= max_dim + 1 and counts >= 0")
+    if max_edges is None:
+        max_edges = n_graphs * math.comb(verts_per_graph, 2)
+    if max_triangles is None:
+        max_triangles = n_graphs * math.comb(verts_per_graph, 3)
     if max_dim == 1:
         max_triangles = 0
     rows = (n_graphs * verts_per_graph, max_edges + 1) + ((max_triangles,) if max_dim == 2 else ())
@@ -773,9 +876,26 @@ def hull_batch_device(points: torch.Tensor, n_graphs: int, capacity: BatchCapaci
     return _lifted_batch_device("hull_batch_device", "hull_lift", points, n_graphs, None, capacity, features, vertex_features, x_ind_cols)
 
 
+def clique_batch_device(points: torch.Tensor, n_graphs: int, capacity: BatchCapacity, edges: Optional[torch.Tensor] = None,
+                        knn: Optional[int] = None, edge_th: float = math.inf, tri_th: float = math.inf,
+                        features: Optional[Dict[str, torch.Tensor]] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
+                        x_ind_cols: Optional[int] = None) -> SimplicialBatch:
+    """rips_batch_device for the thresholded clique complexes of the points (clique_complex; csmpn_clique_lift) over exactly
+    one of edges=... (int64 [2, n] of GLOBAL vertex ids g V + a, moved to the device of the points; (-1, -1) is padding) and
+    knn=k (the k-nearest-neighbour graphs) - the batch relift_(points, edges=... | knn=k, edge_th=..., tri_th=...) is then called
+    on. ValueError as well for a list with an end outside the batch or across two graphs (status bit 5)."""
+    if (edges is None) == (knn is None):
+        raise ValueError("clique_batch_device: pass exactly one of edges=... and knn=...")
+    _thresholds_squared("clique_batch_device", edge_th, tri_th)
+    source = int(knn) if edges is None else edges.to(points.device)
+    return _lifted_batch_device("clique_batch_device", "clique_lift", points, n_graphs, (source, float(edge_th), float(tri_th)), capacity,
+                                features, vertex_features, x_ind_cols)
+
+
 def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, vertex_features, x_ind_cols) -> SimplicialBatch:
-    """The body of rips_batch_device (op = "rips_lift", param = dis), knn_batch_device (op = "knn_lift", param = k) and
-    hull_batch_device (op = "hull_lift", no parameter; the volumes become `target`)."""
+    """The body of rips_batch_device (op = "rips_lift", param = dis), knn_batch_device (op = "knn_lift", param = k),
+    hull_batch_device (op = "hull_lift", no parameter; the volumes become `target`) and clique_batch_device (op =
+    "clique_lift", param = (the list or k, edge_th, tri_th); its larger workspace serves the other lifts as well)."""
     from csmpn_hip import ops
     if not points.is_cuda:
         raise RuntimeError(f"{what} needs device points (no CPU fallback)")
@@ -785,15 +905,20 @@ def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, 
                    edge_types=i64(E, 2), batch=i64(S), ptr=i64(B + 1), x_ind_batch=i64(S), x_ind_ptr=i64(B + 1))
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     counts = i64(max_dim + 2)
-    ws = _lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev)
+    clique = op == "clique_lift"
+    ws = ops.clique_lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev) if clique else \
+        _lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev)
     volume = torch.zeros(B, dtype=torch.float32, device=dev) if op == "hull_lift" else None
     run = getattr(ops, op) if volume is None else (lambda p, b, _, *rest: ops.hull_lift(p, b, *rest, volume=volume))
+    if clique:
+        run = lambda p, b, src, *rest: ops.clique_lift(p, b, src[0], *rest, edge_th=src[1], tri_th=src[2])
     run(points, B, param, max_dim, capacity.simplices, E, tensors["x_ind"], tensors["node_types"], tensors["batch"],
         tensors["x_ind_batch"], tensors["ptr"], tensors["x_ind_ptr"], tensors["edge_index"], tensors["edge_types"], counts, status, ws)
     word = int(status.item())
     if word:
         raise ValueError(f"{what}: the complex does not fit the capacity {capacity} (status {word:#x}: bit 1 / 2 = too "
-                         "many 1- / 2-simplices, bit 3 = too many adjacencies, bit 4 = filler adjacencies without a filler row)")
+                         "many 1- / 2-simplices, bit 3 = too many adjacencies, bit 4 = filler adjacencies without a filler row"
+                         + (", bit 5 = an edge list with an end outside the batch or across two graphs)" if clique else ")"))
     vertex_rows = torch.nonzero(tensors["node_types"] == 0, as_tuple=False).flatten()
     for name, value in (vertex_features or {}).items():
         t = torch.zeros((S,) + tuple(value.shape[1:]), dtype=value.dtype, device=dev)
@@ -808,4 +933,6 @@ def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, 
     out.csr()
     plan = out._plan
     plan["lift_ws"], plan["lift_status"], plan["lift_counts"] = ws, status, counts
+    if clique:
+        plan["clique_lift_ws"] = ws
     return out

@@ -18,7 +18,9 @@ are rebuilt in place on the device (SimplicialBatch.refresh_: csmpn_simplex_tabl
 Where the complex is the Vietoris-Rips complex of the current positions, step(points=...) builds it on the device as well
 (SimplicialBatch.relift_: csmpn_rips_lift writes the structure tensors at the capacity), so a step takes no host lift at all;
 step(points=..., knn=k) does the same for the clique complex of the k-nearest-neighbour graph (csmpn_knn_lift), and
-step(points=..., hull=True) for the convex-hull complex with the hull's volume as the target (csmpn_hull_lift).
+step(points=..., hull=True) for the convex-hull complex with the hull's volume as the target (csmpn_hull_lift), and
+step(points=..., edges=list | knn=k, edge_th=..., tri_th=...) for the thresholded clique complex of a listed graph or of the
+k-nearest-neighbour graph (csmpn_clique_lift).
 
 The kernels launched inside are the same C-ABI calls as in eager mode (they take the current stream); the
 CSR and the embedding index tables are built before capture (their only host round trips).
@@ -115,19 +117,34 @@ class GraphedTrainStep:
     defaults or in one call, are a ValueError; a call that names one of the two does not read the defaults. `hull=True` (as a
     default or in the call) is the third choice under the same rules: the convex-hull complexes of the points
     (hull_complex(method="exact"); csmpn_hull_lift), with the points as the vertex feature `input` and the hulls' volumes
-    written into `target` where the batch has these tensors - a hulls step from nothing but device points."""
+    written into `target` where the batch has these tensors - a hulls step from nothing but device points.
+
+    `edges=True` (or an int: the columns of the list buffer; True = every ordered pair of every graph) is the fourth choice:
+    step(points=..., edges=int64 [2, n] of GLOBAL vertex ids) lifts the thresholded clique complexes of the listed graph
+    (csmpn.data.complexes.clique_complex; csmpn_clique_lift). The list is copied into ONE static device buffer behind a fill of
+    (-1, -1) padding, so lists of changing length replay through the same addresses. `edge_th` / `tri_th` (defaults of the step,
+    or in the call; +infinity where neither names one) go with edges or knn: a k with a threshold lifts the thresholded
+    cliques of the k-nearest-neighbour graph through the same entry; with dis or hull they are a ValueError. A list with an end
+    outside the batch or across two graphs leaves the batch as it was and shows as bit 5 of the lift's word in status()."""
 
     hull = False
+    edges = False
+    edge_th = tri_th = None
+    _edge_buffer = None
 
     def __init__(self, model, optimizer, batch, feature_names: Iterable[str], warmup: int = 2, max_dim: Optional[int] = None,
                  capacity=None, simplex_features: Optional[Iterable[str]] = None, device=None, rips_dis: Optional[float] = None,
-                 knn: Optional[int] = None, hull: bool = False):
-        if (rips_dis is not None) + (knn is not None) + bool(hull) > 1:
-            raise ValueError("GraphedTrainStep: rips_dis (Rips), knn (k-nearest-neighbour cliques) and hull (convex hulls) "
-                             "exclude each other")
+                 knn: Optional[int] = None, hull: bool = False, edges=False, edge_th: Optional[float] = None,
+                 tri_th: Optional[float] = None):
+        if (rips_dis is not None) + (knn is not None) + bool(hull) + bool(edges) > 1:
+            raise ValueError("GraphedTrainStep: rips_dis (Rips), knn (k-nearest-neighbour cliques), hull (convex hulls) and edges "
+                             "(the thresholded cliques of a listed graph) exclude each other")
+        if (edge_th is not None or tri_th is not None) and (rips_dis is not None or hull):
+            raise ValueError("GraphedTrainStep: edge_th / tri_th go with edges or knn, not with rips_dis or hull")
         self.capacity = capacity
         self.simplex_features = None
         self.rips_dis, self.knn, self.hull = rips_dis, knn, bool(hull)
+        self.edges, self.edge_th, self.tri_th = edges, edge_th, tri_th
         if capacity is not None:
             from csmpn.data.complexes import pad_batch
             if device is None:
@@ -184,6 +201,8 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss, self.aux = self._eager_step()
+        if edges:
+            self._edge_list_buffer(None)
         # the capture itself executes nothing: parameters and optimizer state are still those of step 0
 
     def _eager_step(self):
@@ -208,39 +227,69 @@ class GraphedTrainStep:
         from csmpn.data.complexes import pad_batch
         self.batch.refresh_(pad_batch(batch, self.capacity, self.simplex_features))
 
+    def _edge_list_buffer(self, edges: Optional[torch.Tensor]) -> torch.Tensor:
+        """The static list buffer [2, columns] (allocated on first use: `edges` of the constructor as an int, else every ordered
+        pair of every graph), filled with (-1, -1) and then with `edges` (None: the buffer as it is)."""
+        plan = self.batch._plan
+        if self._edge_buffer is None:
+            B, V = self.batch.num_graphs, int(plan["rows"][0].shape[0]) // self.batch.num_graphs
+            columns = B * V * (V - 1) if self.edges is True or not self.edges else int(self.edges)
+            self._edge_buffer = torch.full((2, max(columns, 1)), -1, dtype=torch.int64, device=self.batch.x_ind.device)
+        if edges is None:
+            return self._edge_buffer
+        if edges.dtype != torch.int64 or edges.dim() != 2 or int(edges.shape[0]) != 2:
+            raise ValueError(f"step(points=..., edges=...): the list must be an int64 tensor [2, n], got {edges.dtype} {tuple(edges.shape)}")
+        if int(edges.shape[1]) > int(self._edge_buffer.shape[1]):
+            raise ValueError(f"step(points=..., edges=...): {int(edges.shape[1])} entries, the list buffer holds "
+                             f"{int(self._edge_buffer.shape[1])} (GraphedTrainStep(edges=columns))")
+        self._edge_buffer.fill_(-1)
+        self._edge_buffer[:, :int(edges.shape[1])].copy_(edges, non_blocking=True)
+        return self._edge_buffer
+
     def load_points(self, points: torch.Tensor, dis: Optional[float] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
-                    knn: Optional[int] = None, hull: Optional[bool] = None):
+                    knn: Optional[int] = None, hull: Optional[bool] = None, edges: Optional[torch.Tensor] = None,
+                    edge_th: Optional[float] = None, tri_th: Optional[float] = None):
         """Make the captured batch hold the Vietoris-Rips complexes of the device points [B * V, n] at threshold `dis`
         (default: the step's `rips_dis`) - or, with knn (default: the step's `knn`), the clique complexes of their
         k-nearest-neighbour graphs, or with hull=True (default: the step's `hull`) their convex hulls - lifted on the device (SimplicialBatch.relift_): no host work per batch. A complex
-        over the capacity leaves the structure of the captured batch as it was and shows in status()."""
+        over the capacity leaves the structure of the captured batch as it was and shows in status(). With edges=list
+        (int64 [2, n] of global vertex ids, copied into the step's static list buffer) the thresholded clique complexes of the
+        listed graph; edge_th / tri_th (defaults: the step's) go with edges or knn."""
         if self.capacity is None:
             raise RuntimeError("GraphedTrainStep was built without a capacity: it replays ONE topology (load(features))")
-        if (dis is not None) + (knn is not None) + bool(hull) > 1:
-            raise ValueError("step(points=...): dis=... (Rips), knn=... (k-nearest-neighbour cliques) and hull=True (convex "
-                             "hulls) exclude each other")
-        if dis is None and knn is None and not hull:
+        if (dis is not None) + (knn is not None) + bool(hull) + (edges is not None) > 1:
+            raise ValueError("step(points=...): dis=... (Rips), knn=... (k-nearest-neighbour cliques), hull=True (convex "
+                             "hulls) and edges=... (a listed graph) exclude each other")
+        if dis is None and knn is None and not hull and edges is None:
             dis, knn, hull = self.rips_dis, self.knn, self.hull
-        if dis is None and knn is None and not hull:
-            raise ValueError("step(points=...): pass dis=... or knn=... or hull=True, or set the step's rips_dis, knn or hull")
-        self.batch.relift_(points, dis, vertex_features, knn=knn, hull=bool(hull))
+            if self.edges and dis is None and knn is None and not hull:
+                raise ValueError("step(points=...): pass edges=... (the step was built with edges: every call names its list)")
+        if dis is None and knn is None and not hull and edges is None:
+            raise ValueError("step(points=...): pass dis=... or knn=... or hull=True or edges=..., or set the step's rips_dis, knn or hull")
+        if edges is not None or knn is not None:
+            edge_th = self.edge_th if edge_th is None else edge_th
+            tri_th = self.tri_th if tri_th is None else tri_th
+        if edges is not None:
+            edges = self._edge_list_buffer(edges)
+        self.batch.relift_(points, dis, vertex_features, knn=knn, hull=bool(hull), edges=edges, edge_th=edge_th, tri_th=tri_th)
 
     def status(self) -> int:
         """The status words of the table rebuilds (ops.simplex_tables) and of the device lifts (ops.rips_lift / knn_lift / hull_lift: its bits
-        1..4 are reported as bits 9..12) so far; 0 = fine. Synchronises."""
+        1..4 are reported as bits 9..12, bit 5 of clique_lift - a refused edge list - as bit 13) so far; 0 = fine. Synchronises."""
         plan = self.batch._plan
         word, lift = plan.get("status"), plan.get("lift_status")
         return (0 if word is None else int(word.item())) | (0 if lift is None else int(lift.item()) << LIFT_STATUS_SHIFT)
 
     def step(self, features: Optional[Dict[str, torch.Tensor]] = None, batch=None, points: Optional[torch.Tensor] = None,
              vertex_features: Optional[Dict[str, torch.Tensor]] = None, dis: Optional[float] = None,
-             knn: Optional[int] = None, hull: Optional[bool] = None) -> torch.Tensor:
+             knn: Optional[int] = None, hull: Optional[bool] = None, edges: Optional[torch.Tensor] = None,
+             edge_th: Optional[float] = None, tri_th: Optional[float] = None) -> torch.Tensor:
         if batch is not None and points is not None:
             raise ValueError("step: pass batch=... (lifted on the host) or points=... (lifted on the device), not both")
         if batch is not None:
             self.load_batch(batch)
         if points is not None:
-            self.load_points(points, dis, vertex_features, knn, hull)
+            self.load_points(points, dis, vertex_features, knn, hull, edges, edge_th, tri_th)
         if features:
             self.load(features)
         self.graph.replay()

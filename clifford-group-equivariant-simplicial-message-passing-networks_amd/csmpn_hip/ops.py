@@ -1518,3 +1518,37 @@ def hull_lift(points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, n
             x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), batch.data_ptr(), x_ind_batch.data_ptr(), ptr.data_ptr(),
             x_ind_ptr.data_ptr(), edge_index.data_ptr(), _ptr(edge_types), _ptr(counts), _ptr(status), _ptr(volume),
             workspace.data_ptr(), workspace.numel(), _stream(dev)))
+
+
+def clique_lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, device) -> torch.Tensor:
+    """Workspace of clique_lift (uninitialised device bytes); at least as large as those of the other three lifts."""
+    return torch.empty(max(int(native.lib().csmpn_clique_lift_workspace_bytes(int(n_graphs), int(verts_per_graph), int(max_dim))), 16),
+                       dtype=torch.uint8, device=device)
+
+
+LIFT_STATUS_BAD_LIST = 32          # bit 5 of the status word of clique_lift: an end outside the batch or across two graphs
+
+
+def clique_lift(points, n_graphs, source, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch, x_ind_batch, ptr,
+                x_ind_ptr, edge_index, edge_types, counts, status, workspace, edge_th=float("inf"), tri_th=float("inf")):
+    """csmpn_clique_lift: rips_lift for the thresholded clique complex of any graph - the structure tensors of
+    pad_batch(collate([clique_complex(points of graph g, its edges, edge_th, tri_th, max_dim)]), capacity), same buffers, same
+    status bits. `source` names the graph: an int k >= 1 (the k-nearest-neighbour graph of knn_lift) or a contiguous int64
+    device tensor [2, n] of GLOBAL vertex ids g V + a ((-1, -1) entries are padding; an end outside the batch or two ends in
+    different graphs set LIFT_STATUS_BAD_LIST and leave the buffers as they were)."""
+    B, V, E, cap = _lift_arguments("clique_lift", points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch,
+                                   x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status)
+    dev = points.device
+    if torch.is_tensor(source):
+        if source.dtype != torch.int64 or source.dim() != 2 or int(source.shape[0]) != 2 or not source.is_contiguous() or source.device != dev:
+            raise RuntimeError("clique_lift: the edge list must be a contiguous int64 tensor [2, n] on the device of points")
+        # an empty list is a list all the same: any non-null address stands for it (n_list = 0: never read)
+        k, list_ptr, n_list = 0, source.data_ptr() if source.numel() else workspace.data_ptr(), int(source.shape[1])
+    else:
+        k, list_ptr, n_list = int(source), None, 0
+    with torch.cuda.device(dev):
+        check(native.lib().csmpn_clique_lift(
+            points.data_ptr(), int(points.shape[1]), B, V, k, list_ptr, n_list, float(edge_th), float(tri_th), int(max_dim),
+            C.addressof(cap), E, x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), batch.data_ptr(),
+            x_ind_batch.data_ptr(), ptr.data_ptr(), x_ind_ptr.data_ptr(), edge_index.data_ptr(), _ptr(edge_types), _ptr(counts),
+            _ptr(status), workspace.data_ptr(), workspace.numel(), _stream(dev)))

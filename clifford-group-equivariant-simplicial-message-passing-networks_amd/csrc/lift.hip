@@ -11,6 +11,12 @@
 // kernel finds the facets among the subsets of point_dim vertices and writes, beside the masks, a table T[a][b] of the w with
 // {a, b, w} in a facet - the triangles and cofaces of an edge come from T, not from the masks (kFacetTable = true).
 //
+// csmpn_clique_lift is the thresholded clique lift of any graph G (clique_complex): G's masks come from a caller's edge list
+// (lift_list_kernel: 64-bit atomic ORs into zeroed masks) or from lift_knn_kernel; lift_filter_kernel keeps the edges of G
+// with s <= edge_th^2 and the triangles of G with Gram determinant <= 4 tri_th^2, brings back the pairs of every kept
+// triangle, and writes the final masks and a 64-wide table T - three surviving edges need not bound a surviving triangle,
+// so the scatter reads T as the hull's does (kFacetTable = true, kTableStride = 64, no vertex block).
+//
 // A graph has at most 64 vertices, so ONE 64-bit neighbour mask per vertex (a wave ballot over the other vertices) carries
 // it, and every index is a popcount of masks plus a scan: with upper[a] = mask[a] restricted to b > a,
 //   index of the edge (a, b), a < b      = sum_{a' < a} popc(upper[a']) + popc(upper[a] & below(b))
@@ -55,6 +61,7 @@ struct Header {                  // first 256 bytes of the workspace, written by
     int fit;                     // 1: the batch fits its capacity, the scatter kernel writes
     long long n[3];              // real rows per dimension
     long long adj;               // real adjacencies
+    int bad_list;                // csmpn_clique_lift: zeroed on the stream, set by lift_list_kernel for an end it refuses
 };
 
 struct Outputs {
@@ -366,17 +373,140 @@ __global__ __launch_bounds__(kBlock) void lift_hull_kernel(const float* points, 
     }
 }
 
+// -------------------------------------------------------------------------------------- the thresholded clique lift
+//
+// G is any graph on the V vertices of a graph of the batch, as masks gm[a] bit b. With s(a, b) the sum of lift_count_kernel
+// and, for a < b < c, g(a, b, c) = uu vv - uv uv (u = p_b - p_a, v = p_c - p_a, uu / vv / uv summed over j ascending; a NaN s
+// or g counts as +infinity), all in double, every product, sum and difference rounded once (mul_rn above):
+//   E_keep = the edges of G with s <= edge_th^2;   T_keep = the triples whose pairs are edges of G with g <= 4 tri_th^2;
+//   1-simplices = E_keep and the three pairs of every triple of T_keep;   2-simplices = T_keep.
+
+constexpr int kCliqueStride = kMaxVerts;                      // the T table of a graph in LDS: 64 x 64 masks, 32 KB
+
+// G from a caller's list [2, n_list] of global vertex ids (graph g holds g V .. g V + V - 1): both directions ORed into
+// the zeroed masks - an OR does not depend on the order. (-1, -1) is padding, a self-loop is skipped; an end outside the
+// batch or two ends in different graphs set *bad_list and write nothing.
+__global__ __launch_bounds__(kBlock) void lift_list_kernel(const int64_t* list, long long n_list, long long n_verts, int V, u64* gmasks,
+                                                            int* bad_list) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_list) return;
+    const long long a = list[i], b = list[n_list + i];
+    if (a == -1 && b == -1) return;
+    if (a < 0 || a >= n_verts || b < 0 || b >= n_verts || a / V != b / V) {
+        atomicOr(bad_list, 1);
+        return;
+    }
+    if (a == b) return;
+    atomicOr(&gmasks[a], 1ull << (int)(b % V));
+    atomicOr(&gmasks[b], 1ull << (int)(a % V));
+}
+
+__device__ __forceinline__ double not_nan(double x) { return x == x ? x : __longlong_as_double(0x7ff0000000000000ll); }
+
+// one workgroup per graph: G's masks -> the final masks, the table T[a][b] (bit c = {a, b, c} in T_keep; [V, V] per graph in
+// the workspace) and the counts. G's masks and the final ones live side by side in LDS; the pairs a kept triangle brings back
+// and the table entries are ORed there (the result does not depend on the order). A thread takes the pairs (a, b) of G,
+// a < b, and walks their common neighbours c > b: every triple is tried once.
+__global__ __launch_bounds__(kBlock) void lift_filter_kernel(const float* points, int P, int V, double edge_th2, double tri_th4,
+                                                              int max_dim, const u64* gmasks, u64* masks, u64* tables, int* n1, int* n2) {
+    __shared__ u64 gm[kMaxVerts], fm[kMaxVerts], T[kCliqueStride * kCliqueStride];
+    const long g = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* pg = points + g * V * (long)P;
+    if (tid < kMaxVerts) gm[tid] = tid < V ? gmasks[g * V + tid] : 0ull;        // neither source sets a bit at or above V
+    for (int i = tid; i < kCliqueStride * kCliqueStride; i += kBlock) T[i] = 0ull;
+    __syncthreads();
+    for (int a = wave; a < V; a += kWaves) {                  // E_keep
+        bool keep = false;
+        if (lane < V && lane != a && ((gm[a] >> lane) & 1ull)) {
+            double s = 0.0;
+            for (int j = 0; j < P; ++j) {
+                const double d = sub_rn((double)pg[a * P + j], (double)pg[lane * P + j]);
+                s = add_rn(s, mul_rn(d, d));
+            }
+            keep = not_nan(s) <= edge_th2;
+        }
+        const u64 mk = __ballot(keep);
+        if (lane == 0) fm[a] = mk;
+    }
+    __syncthreads();
+    for (int i = tid; i < V * V; i += kBlock) {               // T_keep
+        const int a = i / V, b = i % V;
+        if (a >= b || !((gm[a] >> b) & 1ull)) continue;
+        u64 kept = 0ull;
+        for (u64 r = gm[a] & gm[b] & above(b); r; r &= r - 1) {
+            const int c = first_bit(r);
+            double uu = 0.0, vv = 0.0, uv = 0.0;
+            for (int j = 0; j < P; ++j) {
+                const double pa = (double)pg[a * P + j];
+                const double u = sub_rn((double)pg[b * P + j], pa), v = sub_rn((double)pg[c * P + j], pa);
+                uu = add_rn(uu, mul_rn(u, u));
+                vv = add_rn(vv, mul_rn(v, v));
+                uv = add_rn(uv, mul_rn(u, v));
+            }
+            const double gram = sub_rn(mul_rn(uu, vv), mul_rn(uv, uv));
+            if (!(not_nan(gram) <= tri_th4)) continue;
+            kept |= 1ull << c;
+            atomicOr(&T[a * kCliqueStride + c], 1ull << b);
+            atomicOr(&T[c * kCliqueStride + a], 1ull << b);
+            atomicOr(&T[b * kCliqueStride + c], 1ull << a);
+            atomicOr(&T[c * kCliqueStride + b], 1ull << a);
+            atomicOr(&fm[c], (1ull << a) | (1ull << b));
+        }
+        if (!kept) continue;
+        atomicOr(&T[a * kCliqueStride + b], kept);
+        atomicOr(&T[b * kCliqueStride + a], kept);
+        atomicOr(&fm[a], kept | (1ull << b));
+        atomicOr(&fm[b], kept | (1ull << a));
+    }
+    __syncthreads();
+    for (int i = tid; i < V * V; i += kBlock) tables[g * V * V + i] = T[(i / V) * kCliqueStride + i % V];
+    if (wave != 0) return;
+    int c1 = 0, c2 = 0;
+    if (lane < V) {
+        const u64 ma = fm[lane], up = ma & above(lane);
+        masks[g * V + lane] = ma;
+        c1 = __popcll(up);
+        if (max_dim >= 2)
+            for (u64 r = up; r; r &= r - 1) {
+                const int b = first_bit(r);
+                c2 += __popcll(T[lane * kCliqueStride + b] & above(b));
+            }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        c1 += __shfl_down(c1, d, 64);
+        c2 += __shfl_down(c2, d, 64);
+    }
+    if (lane == 0) {
+        n1[g] = c1;
+        n2[g] = c2;
+    }
+}
+
 // one workgroup: totals against the capacity; if the batch fits, the offsets of every graph and ptr / x_ind_ptr / counts.
-// kVertexBlock: a graph's adjacencies hold the 0_0 block over the non-edges (Rips), V (V - 1) + 5 n1 + 12 n2 of them; without
+// kVertexBlock:a graph's adjacencies hold the 0_0 block over the non-edges (Rips), V (V - 1) + 5 n1 + 12 n2 of them; without
 // it (kNN cliques) 6 n1 + 12 n2. A template parameter, here and in the scatter kernel: the Rips instantiations are the
 // kernels without the switch, and the kNN instantiation of the scatter carries neither the block-2 store nor its index
 // arithmetic - no wave-uniform branch in the pair loop and no register for it.
-template <bool kVertexBlock>
+// kListFlag (csmpn_clique_lift): a list that lift_list_kernel has refused (hdr->bad_list) makes the batch invalid - bit 5 of
+// the status word alone, whatever the counts of the rest of the list are, and no output is written. The instantiations without
+// it never read the field.
+template <bool kVertexBlock, bool kListFlag = false>
 __global__ __launch_bounds__(kBlock) void lift_offsets_kernel(const int* n1, const int* n2, long B, int V, int max_dim, Capacity cap,
                                                                Header* hdr, long long* row_off, long long* adj_off, int64_t* ptr,
                                                                int64_t* x_ind_ptr, int64_t* counts, unsigned* status) {
     using Scan = hipcub::BlockScan<long long, kBlock>;
     __shared__ typename Scan::TempStorage temp;
+    if constexpr (kListFlag) {
+        if (hdr->bad_list) {                                  // uniform
+            if (threadIdx.x == 0) {
+                hdr->fit = 0;
+                if (status) atomicOr(status, 1u << 5);
+            }
+            return;
+        }
+    }
     const long long VV = kVertexBlock ? (long long)V * (V - 1) : 0ll;     // adjacencies of a graph = VV + per_edge n1 + 12 n2
     const long long per_edge = kVertexBlock ? 5 : 6;
     long long N1 = 0, N2 = 0;
@@ -451,15 +581,21 @@ __global__ __launch_bounds__(kBlock) void lift_offsets_kernel(const int* n1, con
 // kFacetTable (the hull lift, V <= 16): a triple is a 2-simplex iff it lies in a facet, not iff its pairs are edges, so the
 // triangles of the edge (a, b) are T[a][b] & above(b) and its cofaces T[a][b], T = `tables` [V, V] of graph g loaded into
 // LDS, instead of the intersections of the neighbour masks. A template parameter for the reason kVertexBlock is one: the
-// Rips and kNN instantiations carry neither the table nor a branch on it.
-template <bool kVertexBlock, bool kFacetTable>
+// Rips and kNN instantiations carry neither the table nor a branch on it. kTableStride: the row length of T in LDS - 16 for
+// the hull lift, 64 for the thresholded clique lift (32 KB, loaded by a loop); a template parameter again, so that the hull
+// instantiation keeps its one-statement load and its index arithmetic.
+template <bool kVertexBlock, bool kFacetTable, int kTableStride = kHullMaxVerts>
 __device__ void scatter_graph(long g, int V, int max_dim, const u64* masks, const u64* tables, const int* n1s, const int* n2s,
                               const long long* row_off, const long long* adj_off, const Outputs& o) {
     __shared__ u64 m[kMaxVerts];
     const u64* T = nullptr;
     if constexpr (kFacetTable) {
-        __shared__ u64 table_s[kHullMaxVerts * kHullMaxVerts];
-        if ((int)threadIdx.x < V * V) table_s[(threadIdx.x / V) * kHullMaxVerts + threadIdx.x % V] = tables[g * V * V + threadIdx.x];
+        __shared__ u64 table_s[kTableStride * kTableStride];
+        if constexpr (kTableStride == kHullMaxVerts) {
+            if ((int)threadIdx.x < V * V) table_s[(threadIdx.x / V) * kHullMaxVerts + threadIdx.x % V] = tables[g * V * V + threadIdx.x];
+        } else {
+            for (int i = threadIdx.x; i < V * V; i += kBlock) table_s[(i / V) * kTableStride + i % V] = tables[g * V * V + i];
+        }
         T = table_s;
     }
     __shared__ int deg_s[kMaxVerts], up_s[kMaxVerts], tri_s[kMaxVerts], cof_s[kMaxVerts];   // sums over the vertices in front
@@ -473,7 +609,7 @@ __device__ void scatter_graph(long g, int V, int max_dim, const u64* masks, cons
             for (u64 r = up; r; r &= r - 1) {
                 const int b = first_bit(r);
                 const u64 mb = m[b];
-                const u64 cof = kFacetTable ? T[lane * kHullMaxVerts + b] : ma & mb;
+                const u64 cof = kFacetTable ? T[lane * kTableStride + b] : ma & mb;
                 t += __popcll(kFacetTable ? cof & above(b) : up & mb & above(b));
                 c += __popcll(cof);
             }
@@ -496,7 +632,7 @@ __device__ void scatter_graph(long g, int V, int max_dim, const u64* masks, cons
             put_adj(o, o2 + (long long)a * (V - 1) - up_s[a] + lane - (lane > a ? 1 : 0) - __popcll(up & below(lane)), row0 + a,
                     row0 + lane, 0, 0);
         const bool edge = (up >> lane) & 1ull;                // the pair (a, lane), a < lane, is an edge
-        const u64 both = kFacetTable ? (edge ? T[a * kHullMaxVerts + lane] : 0ull) : ma & mb;
+        const u64 both = kFacetTable ? (edge ? T[a * kTableStride + lane] : 0ull) : ma & mb;
         const u64 tri = edge && max_dim >= 2 ? (kFacetTable ? both : up & mb) & above(lane) : 0ull;   // its triangles (a, lane, c)
         const u64 cof = edge && max_dim >= 2 ? both : 0ull;                      // its cofaces {a, lane, w}
         const long long tb = tri_s[a] + wave_scan(__popcll(tri), lane, nullptr);
@@ -579,20 +715,33 @@ __global__ __launch_bounds__(kBlock) void lift_hull_scatter_kernel(long B, int V
     }
 }
 
+// the scatter of the thresholded clique lift: no vertex block, the 64-wide table of lift_filter_kernel
+__global__ __launch_bounds__(kBlock) void lift_clique_scatter_kernel(long B, int V, int max_dim, Capacity cap, const Header* hdr,
+                                                                      const u64* masks, const u64* tables, const int* n1, const int* n2,
+                                                                      const long long* row_off, const long long* adj_off, Outputs o) {
+    if (!hdr->fit) return;
+    if ((long)blockIdx.x < B)
+        scatter_graph<false, true, kCliqueStride>((long)blockIdx.x, V, max_dim, masks, tables, n1, n2, row_off, adj_off, o);
+    else
+        scatter_fillers((long)blockIdx.x - B, (long)gridDim.x - B, B, max_dim, cap, hdr, o);
+}
+
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 inline bool sizes_ok(int64_t n_graphs, int32_t V, int32_t max_dim) {
     return (max_dim == 1 || max_dim == 2) && V > max_dim && V <= kMaxVerts && n_graphs > 0 && n_graphs < (1ll << 31) / V;
 }
 
-enum class Lift { rips, knn, hull };
+enum class Lift { rips, knn, hull, clique };
 
 inline size_t workspace_bytes_of(int64_t n_graphs, int32_t V, int32_t max_dim, Lift kind = Lift::rips) {
     if (!sizes_ok(n_graphs, V, max_dim) || (kind == Lift::hull && V > kHullMaxVerts)) return 0;
     const size_t B = (size_t)n_graphs;
-    // alignment slack + header | masks | n1 | n2 | row offsets | adjacency offsets; the hull lift: | T tables | volumes
+    // alignment slack + header | masks | n1 | n2 | row offsets | adjacency offsets; the hull lift: | T tables | volumes;
+    // the thresholded clique lift: | T tables | the masks of G
     const size_t hull = kind == Lift::hull ? align256(sizeof(u64) * B * (size_t)V * (size_t)V) + align256(sizeof(float) * B) : 0;
-    return 256 + 256 + align256(sizeof(u64) * B * (size_t)V) + 2 * align256(sizeof(int) * B) + 2 * align256(sizeof(long long) * B) + hull;
+    const size_t clique = kind == Lift::clique ? align256(sizeof(u64) * B * (size_t)V * (size_t)V) + align256(sizeof(u64) * B * (size_t)V) : 0;
+    return 256 + 256 + align256(sizeof(u64) * B * (size_t)V) + 2 * align256(sizeof(int) * B) + 2 * align256(sizeof(long long) * B) + hull + clique;
 }
 
 struct LiftArgs {                // what csmpn_rips_lift and csmpn_knn_lift share
@@ -611,10 +760,17 @@ struct LiftArgs {                // what csmpn_rips_lift and csmpn_knn_lift shar
     void* stream;
 };
 
+struct CliqueSource {            // what csmpn_clique_lift adds: the graph (a list, or k >= 1 in the knn_k of the others) and the thresholds
+    const int64_t* edge_list;
+    int64_t n_list;
+    double edge_th, tri_th;
+};
+
 // the checks the entries share, before the first HIP call; `what` names the entry in the messages. dis >= 0: the Rips
 // threshold, knn_k: the k of the kNN entry (0 for the others) - each checked where csmpn_rips_lift has always checked dis; the
-// hull entry checks its point dimension there, and its 16 vertices where the others check their 64.
-int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, Lift kind, Capacity* cap) {
+// hull entry checks its point dimension there, and its 16 vertices where the others check their 64; the clique entry checks
+// its graph source and its thresholds there.
+int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, Lift kind, Capacity* cap, const CliqueSource* src = nullptr) {
     const int V = a.verts_per_graph, max_dim = a.max_dim;
     const bool knn = kind == Lift::knn, hull = kind == Lift::hull;
     if (max_dim < 0) return csmpn_fail(CSMPN_ERR_INVALID, "max_dim %d is negative", max_dim);
@@ -628,6 +784,13 @@ int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, 
     if (hull && V <= a.point_dim) return csmpn_fail(CSMPN_ERR_INVALID, "%s: %d vertices per graph in R^%d (a hull needs %d)", what, V, (int)a.point_dim, (int)a.point_dim + 1);
     if (!knn && !hull && !(dis >= 0.0)) return csmpn_fail(CSMPN_ERR_INVALID, "dis %g is negative or not a number", dis);
     if (knn && knn_k < 1) return csmpn_fail(CSMPN_ERR_INVALID, "%s: k = %d (at least 1)", what, knn_k);
+    if (kind == Lift::clique) {
+        if ((src->edge_list != nullptr) == (knn_k >= 1))
+            return csmpn_fail(CSMPN_ERR_INVALID, "%s: exactly one of an edge list and k >= 1 names the graph (edge_list %s, k = %d)", what, src->edge_list ? "given" : "NULL", knn_k);
+        if (src->edge_list && (src->n_list < 0 || src->n_list >= (1ll << 31))) return csmpn_fail(CSMPN_ERR_INVALID, "%s: n_list = %lld", what, (long long)src->n_list);
+        if (!(src->edge_th >= 0.0)) return csmpn_fail(CSMPN_ERR_INVALID, "%s: edge_th %g is negative or not a number", what, src->edge_th);
+        if (!(src->tri_th >= 0.0)) return csmpn_fail(CSMPN_ERR_INVALID, "%s: tri_th %g is negative or not a number", what, src->tri_th);
+    }
     if (a.x_ind_cols <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "x_ind has %d columns, max_dim %d needs %d", (int)a.x_ind_cols, max_dim, max_dim + 1);
     if (!a.points || !a.capacity_rows || !a.x_ind || !a.node_types || !a.batch || !a.x_ind_batch || !a.ptr || !a.x_ind_ptr || !a.edge_index)
         return csmpn_fail(CSMPN_ERR_INVALID, "null pointer");
@@ -649,9 +812,11 @@ int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, 
 
 // Behind the argument checks: the workspace carved up, then the three launches. knn_k = 0: the masks of the pairs within
 // `dis` and the adjacencies with the vertex block (Rips); knn_k >= 1: the masks of the k nearest neighbours, no vertex block;
-// kind == Lift::hull: the masks and the T tables of the facets, the vertex block, the volumes -> `volume` (may be null).
+// kind == Lift::hull: the masks and the T tables of the facets, the vertex block, the volumes -> `volume` (may be null);
+// kind == Lift::clique: the masks of G from src's list (zeroed on the stream first) or from the knn_k nearest neighbours, the
+// filter, no vertex block - two memsets at the most and four launches.
 int launch_lift(const char* what, const LiftArgs& a, const Capacity& cap, double dis, int knn_k, Lift kind = Lift::rips,
-                float* volume = nullptr) {
+                float* volume = nullptr, const CliqueSource* src = nullptr) {
     hipStream_t st = (hipStream_t)a.stream;
     const int V = a.verts_per_graph, max_dim = a.max_dim, P = a.point_dim;
     const size_t B = (size_t)a.n_graphs;
@@ -668,8 +833,9 @@ int launch_lift(const char* what, const LiftArgs& a, const Capacity& cap, double
     ws += align256(sizeof(long long) * B);
     long long* adj_off = reinterpret_cast<long long*>(ws);
     ws += align256(sizeof(long long) * B);
-    const bool hull = kind == Lift::hull;                                                  // its workspace alone has these bytes
-    u64* tables = hull ? reinterpret_cast<u64*>(ws) : nullptr;
+    const bool hull = kind == Lift::hull, clique = kind == Lift::clique;                   // their workspaces alone have these bytes
+    u64* tables = hull || clique ? reinterpret_cast<u64*>(ws) : nullptr;
+    u64* gmasks = clique ? reinterpret_cast<u64*>(ws + align256(sizeof(u64) * B * (size_t)V * (size_t)V)) : nullptr;
     float* vols = hull ? reinterpret_cast<float*>(ws + align256(sizeof(u64) * B * (size_t)V * (size_t)V)) : nullptr;
     Outputs out{a.x_ind, a.node_types, a.batch, a.x_ind_batch, a.edge_index, a.edge_types, (int)a.x_ind_cols, cap.edges};
     const long long fill_items = std::max(cap.rows[1] + cap.rows[2], cap.edges);
@@ -692,6 +858,21 @@ int launch_lift(const char* what, const LiftArgs& a, const Capacity& cap, double
         hipLaunchKernelGGL(lift_hull_scatter_kernel, scatter, block, 0, st, (long)B, V, max_dim, cap, (const Header*)hdr, (const u64*)masks,
                            (const u64*)tables, (const int*)n1, (const int*)n2, (const long long*)row_off, (const long long*)adj_off,
                            (const float*)vols, volume, out);
+    } else if (clique) {
+        hipError_t e = hipMemsetAsync(hdr, 0, 256, st);                                    // bad_list = 0
+        if (e == hipSuccess && src->edge_list) e = hipMemsetAsync(gmasks, 0, sizeof(u64) * B * (size_t)V, st);
+        if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "%s memset: %s", what, hipGetErrorString(e));
+        if (!src->edge_list)                                                               // its counts are overwritten by the filter
+            hipLaunchKernelGGL(lift_knn_kernel, per_graph, block, 0, st, a.points, P, V, knn_k, max_dim, gmasks, n1, n2);
+        else if (src->n_list > 0)
+            hipLaunchKernelGGL(lift_list_kernel, dim3((unsigned)((src->n_list + kBlock - 1) / kBlock)), block, 0, st, src->edge_list,
+                               (long long)src->n_list, (long long)(B * (size_t)V), V, gmasks, &hdr->bad_list);
+        hipLaunchKernelGGL(lift_filter_kernel, per_graph, block, 0, st, a.points, P, V, src->edge_th * src->edge_th,
+                           4.0 * src->tri_th * src->tri_th, max_dim, (const u64*)gmasks, masks, tables, n1, n2);
+        hipLaunchKernelGGL((lift_offsets_kernel<false, true>), one, block, 0, st, (const int*)n1, (const int*)n2, (long)B, V, max_dim, cap,
+                           hdr, row_off, adj_off, a.ptr, a.x_ind_ptr, a.counts, (unsigned*)a.status);
+        hipLaunchKernelGGL(lift_clique_scatter_kernel, scatter, block, 0, st, (long)B, V, max_dim, cap, (const Header*)hdr, (const u64*)masks,
+                           (const u64*)tables, (const int*)n1, (const int*)n2, (const long long*)row_off, (const long long*)adj_off, out);
     } else if (knn_k > 0) {
         hipLaunchKernelGGL(lift_knn_kernel, per_graph, block, 0, st, a.points, P, V, knn_k, max_dim, masks, n1, n2);
         hipLaunchKernelGGL(lift_offsets_kernel<false>, one, block, 0, st, (const int*)n1, (const int*)n2, (long)B, V, max_dim, cap, hdr,
@@ -757,6 +938,23 @@ int csmpn_hull_lift(const float* points, int32_t point_dim, int64_t n_graphs, in
     Capacity cap{};
     if (const int rc = check_lift_args("hull lift", a, 0.0, 0, Lift::hull, &cap)) return rc;
     return launch_lift("hull lift", a, cap, 0.0, 0, Lift::hull, volume);
+}
+
+size_t csmpn_clique_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim) {
+    return workspace_bytes_of(n_graphs, verts_per_graph, max_dim, Lift::clique);
+}
+
+int csmpn_clique_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, int32_t k,
+                      const int64_t* edge_list, int64_t n_list, double edge_th, double tri_th, int32_t max_dim,
+                      const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                      int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                      int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const LiftArgs a{points, point_dim, n_graphs, verts_per_graph, max_dim, capacity_rows, capacity_edges, x_ind, x_ind_cols, node_types,
+                     batch, x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status, workspace, workspace_bytes, stream};
+    const CliqueSource src{edge_list, n_list, edge_th, tri_th};
+    Capacity cap{};
+    if (const int rc = check_lift_args("clique lift", a, 0.0, (int)k, Lift::clique, &cap, &src)) return rc;
+    return launch_lift("clique lift", a, cap, 0.0, (int)k, Lift::clique, nullptr, &src);
 }
 
 }  // extern "C"

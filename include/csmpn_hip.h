@@ -511,6 +511,38 @@ int csmpn_hull_lift(const float* points, int32_t point_dim, int64_t n_graphs, in
                     int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
                     int64_t* counts, uint32_t* status, float* volume, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same lift of the thresholded clique complex of ANY graph G on the verts_per_graph points of a graph of the batch: the
+ * structure tensors of exactly the batch that
+ *   pad_batch(collate([clique_complex(points_g, edges_g, edge_th, tri_th, max_dim) for g]), BatchCapacity(capacity_rows, capacity_edges))
+ * builds on the host. Every argument of csmpn_knn_lift, every contract (every launch and memset on `stream`, no allocation, no
+ * host round trip, no atomic on an output - capturable in a HIP graph), the status bits 1..4 of a batch that does not fit (every
+ * output is left as it was), the limits and the adjacency order without the 0_0 block over the non-edges are those of
+ * csmpn_knn_lift.
+ *   The graph: exactly one of edge_list != NULL and k >= 1 (both or neither: CSMPN_ERR_INVALID). k >= 1: G is the symmetrised
+ *   k-nearest-neighbour graph of csmpn_knn_lift. edge_list (device, int64 [2, n_list], n_list in [0, 2^31)): {a, b} is an
+ *   edge of G iff (a, b) or (b, a) is listed, the ends being GLOBAL vertex ids g * verts_per_graph + a; duplicates and both
+ *   directions are harmless, a self-loop is ignored, an entry (-1, -1) is padding and is skipped (one buffer serves lists of
+ *   changing length). An end outside [0, n_graphs * verts_per_graph) or two ends in different graphs make the batch invalid:
+ *   bit 5 of *status alone is ORed in and every output is left as it was.
+ *   The rule, all of it in double on the float points, every product, sum and difference rounded once, none contracted,
+ *   every sum over j ascending; a NaN s or g counts as +infinity:
+ *     E_keep = the edges {a, b} of G with s(a, b) = sum_j (p_a[j] - p_b[j])^2 <= edge_th^2;
+ *     T_keep = the triples a < b < c whose three pairs are edges of G (not of E_keep) with g = uu vv - uv uv <= 4 tri_th^2,
+ *       u = p_b - p_a, v = p_c - p_a, uu = sum_j u_j^2, vv = sum_j v_j^2, uv = sum_j u_j v_j (g = 4 area^2; any point_dim);
+ *     1-simplices = E_keep and the three pairs of every triple of T_keep (a kept triangle brings back an edge that edge_th
+ *       removed, for max_dim = 1 too); 2-simplices (max_dim = 2) = T_keep. Three 1-simplices need not bound a 2-simplex: the
+ *       triangles and cofaces of an edge come from T_keep.
+ *   edge_th and tri_th are >= 0 or +infinity (NaN or negative: CSMPN_ERR_INVALID); with both +infinity every comparison
+ *   holds, a NaN included, and the k source gives the very bits of csmpn_knn_lift.
+ * workspace: csmpn_clique_lift_workspace_bytes(...) bytes (the largest of the four lifts': a table of verts_per_graph^2 masks
+ * per graph and G's masks; 0 for sizes the entry point rejects); needs no initialisation. */
+size_t csmpn_clique_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim);
+int csmpn_clique_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, int32_t k,
+                      const int64_t* edge_list, int64_t n_list, double edge_th, double tri_th, int32_t max_dim,
+                      const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                      int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                      int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fused simplex feature embedding (round 3; hulls_cssmpnn.py:96-125: vertex features of every d-simplex in all (d+1)!
  * vertex orders -> CEMLP -> sum over the orders), for the shapes the wide parity-lane kernels serve as standalone CEMLPs
  * (Cl(5,0) / Cl(4,1), 16 / 24 / 28 / 32 output channels, at most 8 input channels = verts_per_row * channels_per_vertex);

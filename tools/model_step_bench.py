@@ -21,6 +21,10 @@ JSON line with the step times and the simplices / adjacencies of the batch.
 --knn K (with --device-lift, md17): the batches are the clique complexes of the K-nearest-neighbour graphs
   (knn_clique_complex: the reference's aspirin configuration has K = 3) instead of Rips complexes, lifted on the device by
   step(points=..., knn=K) (csmpn_knn_lift); the same four figures, and the capacity's rows / adjacencies
+--edge-th X / --tri-th Y (with --knn K): the batches are the THRESHOLDED clique complexes of the K-nearest-neighbour graphs
+  (clique_complex(points, knn_edges(points, K), X, Y)), lifted on the device by step(points=..., knn=K, edge_th=X, tri_th=Y)
+  (csmpn_clique_lift: the kNN masks, the filter, the table scatter); `inf` for both gives the very complexes of --knn K
+  through the new entry - the kNN device-lift step plus the filter launch
 --model hulls --varying K --device-lift: the K batches of convex hulls through step(points=..., hull=True) (csmpn_hull_lift:
   the complex, `input` and the volume target all from the device points); the host figure is qhull + lift + collate +
   pad_batch of one batch
@@ -98,6 +102,13 @@ def op_sites(eager, steps=2):
         print(f"{us / steps:8.1f} us {n / steps:5.1f}x  {k[0]:70s} {k[1]:40s} {k[2]}")
 
 
+def thresholds(args):
+    """None, or (edge_th, tri_th) where --edge-th or --tri-th is given (the other one: +infinity)."""
+    if args.edge_th is None and args.tri_th is None:
+        return None
+    return (float("inf") if args.edge_th is None else args.edge_th, float("inf") if args.tri_th is None else args.tri_th)
+
+
 def make_batch(args, rng, cx):
     """One collated CPU batch of the chosen model and the names of its changing tensors. The Rips models' batches carry the
     points they were lifted from and the threshold (lift_points float32 [B * V, n], lift_dis) for --device-lift."""
@@ -151,7 +162,10 @@ def make_batch(args, rng, cx):
         for _ in range(args.batch):
             base = (1.6 * rng.standard_normal((V, 3))).astype(np.float32)
             points.append(base)
-            c = cx.knn_clique_complex(base, args.knn, max_dim=2) if args.knn else cx.rips_complex(base, dis=dis, max_dim=2)
+            if args.knn and thresholds(args):
+                c = cx.clique_complex(base, cx.knn_edges(base, args.knn), *thresholds(args), max_dim=2)
+            else:
+                c = cx.knn_clique_complex(base, args.knn, max_dim=2) if args.knn else cx.rips_complex(base, dis=dis, max_dim=2)
             S = c.n_simplices
             loc = torch.zeros(S, F, 3); vel = torch.zeros(S, F, 3); ch = torch.zeros(S, F, 1)
             loc[:V] = torch.from_numpy(base)[:, None, :] + 0.05 * torch.from_numpy(rng.standard_normal((V, F, 3)).astype(np.float32))
@@ -166,7 +180,7 @@ def make_batch(args, rng, cx):
     if points:
         batch.lift_points, batch.lift_dis = np.concatenate(points, axis=0), dis
         if args.knn:
-            batch.lift_knn = args.knn
+            batch.lift_knn, batch.lift_thresholds = args.knn, thresholds(args)
         if args.model == "hulls":
             batch.lift_hull = True
     return batch, features
@@ -233,9 +247,16 @@ def device_lift(args, out, cx, gs, batches, features, cap, dev):
     hull = getattr(batches[0], "lift_hull", False)
     if hull and not hasattr(cx, "hull_batch_device"):
         raise SystemExit("--model hulls --device-lift needs a tree with the hull lift")
+    ths = getattr(batches[0], "lift_thresholds", None)
+    if ths and not hasattr(cx, "clique_complex"):
+        raise SystemExit("--edge-th / --tri-th need a tree with the thresholded clique lift")
     how = dict(hull=True) if hull else dict(dis=dis) if knn is None else dict(knn=knn)
     host = (lambda g: cx.hull_complex(g, max_dim=2)) if hull else (lambda g: cx.rips_complex(g, dis=dis, max_dim=2)) if knn is None \
         else (lambda g: cx.knn_clique_complex(g, knn, max_dim=2))
+    if ths:
+        how.update(edge_th=ths[0], tri_th=ths[1])
+        host = lambda g: cx.clique_complex(g, cx.knn_edges(g, knn), ths[0], ths[1], max_dim=2)
+        out["thresholds"] = [str(t) for t in ths]
     names = [] if hull else [k for k in features if k != "y"]      # the hull lift fills `input` and `target` itself
     on_dev = []
     for b in batches:
@@ -272,10 +293,14 @@ def main():
     ap.add_argument("--slack", type=float, default=0.0, help="--varying: capacity_of(batches, slack)")
     ap.add_argument("--device-lift", action="store_true", help="--varying: also step(points=...), the complexes lifted on the device, and the host time of the lift")
     ap.add_argument("--knn", type=int, default=0, metavar="K", help="--device-lift, md17: clique complexes of the K-nearest-neighbour graphs instead of Rips complexes")
+    ap.add_argument("--edge-th", type=float, default=None, metavar="X", help="--knn K: drop the edges longer than X (thresholded clique lift; inf keeps all)")
+    ap.add_argument("--tri-th", type=float, default=None, metavar="Y", help="--knn K: drop the triangles of area above Y (thresholded clique lift; inf keeps all)")
     ap.add_argument("--pkg-root", default=None, help="import the package from this tree instead of the tool's own")
     args = ap.parse_args()
     if args.knn and (args.model != "md17" or not args.device_lift or args.knn < 1):
         raise SystemExit("--knn K (K >= 1) goes with --model md17 --varying ... --device-lift")
+    if (args.edge_th is not None or args.tri_th is not None) and not args.knn:
+        raise SystemExit("--edge-th / --tri-th go with --knn K")
     if args.pkg_root:
         sys.path.insert(0, os.path.abspath(args.pkg_root))
     importlib.import_module(PKG)
