@@ -224,9 +224,10 @@ def hull_complex(points: np.ndarray, max_dim: int = 2, method: str = "qhull") ->
     return to_complex(len(points), x_dict, adj, max_dim)
 
 
-def rips_complex(points: np.ndarray, dis: float, max_dim: int = 2) -> SimplicialComplex:
+def rips_complex(points: np.ndarray, dis: float, max_dim: int = 2, vertex_block: bool = True) -> SimplicialComplex:
     """Vietoris-Rips complex: an edge for every pair closer than `dis`, higher simplices = cliques
-    (utils.py:106-137)."""
+    (utils.py:106-137). vertex_block=False: without the fully connected 0-0 block over the non-edges (lift), the
+    adjacencies of clique_complex - V (V - 1) - n1 entries that a cloud of thousands of points does not want."""
     pts = np.asarray(points, dtype=np.float64)
     V = len(pts)
     close = np.linalg.norm(pts[:, None] - pts[None], axis=-1) <= dis
@@ -235,7 +236,7 @@ def rips_complex(points: np.ndarray, dis: float, max_dim: int = 2) -> Simplicial
         for sub in itertools.combinations(range(V), k + 1):
             if all(close[a, b] for a, b in itertools.combinations(sub, 2)):
                 tops.append(sub)
-    x_dict, adj = lift(V, tops, max_dim)
+    x_dict, adj = lift(V, tops, max_dim, vertex_block=vertex_block)
     return to_complex(V, x_dict, adj, max_dim)
 
 
@@ -484,15 +485,23 @@ class SimplicialBatch:
         the listed graph, written by ops.clique_lift (csmpn_clique_lift). edge_th / tri_th (default +infinity each) go with
         edges=... or knn=...: knn=k with a threshold lifts clique_complex(points, knn_edges(points, k), edge_th, tri_th) through
         the same entry; knn=k without one is csmpn_knn_lift as before. A threshold with dis or hull is a ValueError. A list
-        with an end outside the batch or across two graphs leaves the batch as it was and sets bit 5 of plan()["lift_status"]."""
+        with an end outside the batch or across two graphs leaves the batch as it was and sets bit 5 of plan()["lift_status"].
+
+        A batch of cloud_batch_device (up to 4096 vertices per graph) takes dis=... alone: it is re-lifted by ops.cloud_lift
+        (csmpn_cloud_lift) with the vertex_block it was built with and its own workspace; knn, hull, edges and the thresholds
+        are a ValueError there - those lifts hold at most 64 vertices per graph."""
         from csmpn_hip import ops
         if (dis is not None) + (knn is not None) + bool(hull) + (edges is not None) != 1:
             raise ValueError("relift_: pass exactly one of dis=... (Rips), knn=... (k-nearest-neighbour cliques), hull=True "
                              "(convex hulls) and edges=... (the thresholded cliques of a listed graph)")
         thresholded = edge_th is not None or tri_th is not None
+        plan = getattr(self, "_plan", None)
+        cloud = None if plan is None else plan.get("cloud")
+        if cloud is not None and (dis is None or thresholded):
+            raise ValueError("relift_: a cloud batch (cloud_batch_device) is re-lifted with dis=... alone - the kNN, hull and "
+                             "thresholded clique lifts (knn, hull, edges, edge_th, tri_th) hold at most 64 vertices per graph")
         if thresholded and (dis is not None or hull):
             raise ValueError("relift_: edge_th / tri_th go with edges=... or knn=..., not with dis or hull")
-        plan = getattr(self, "_plan", None)
         if plan is None or self._csr is None:
             raise RuntimeError("relift_: call plan() and csr() on the batch first")
         dev = self.x_ind.device
@@ -514,7 +523,9 @@ class SimplicialBatch:
             plan["lift_ws"] = _lift_workspace(B, rows[0] // B, max_dim, dev)
             plan["lift_status"] = torch.zeros(1, dtype=torch.int32, device=dev)
             plan["lift_counts"] = torch.zeros(max_dim + 2, dtype=torch.int64, device=dev)
-        if edges is not None or thresholded:
+        if cloud is not None:
+            run = lambda *args: ops.cloud_lift(*args, vertex_block=cloud["vertex_block"])
+        elif edges is not None or thresholded:
             if "clique_lift_ws" not in plan:
                 plan["clique_lift_ws"] = ops.clique_lift_workspace(B, rows[0] // B, max_dim, dev)
             ths = dict(edge_th=math.inf if edge_th is None else edge_th, tri_th=math.inf if tri_th is None else tri_th)
@@ -749,6 +760,9 @@ def pad_batch(batch: "SimplicialBatch", capacity: BatchCapacity, simplex_feature
 # csmpn_hull_lift: hull_capacity, hull_batch_device, relift_(points, hull=True); the thresholded clique complex of any graph
 # (clique_complex: a caller's edge list or the kNN graph, edge_th / tri_th) by csmpn_clique_lift: clique_capacity,
 # clique_batch_device, relift_(points, edges=... | knn=k, edge_th=..., tri_th=...).
+# Those four hold at most 64 vertices per graph (hulls: 16). The Rips complex of a point cloud of up to 4096 vertices per graph -
+# one cloud of a few thousand points is a batch of one graph - is lifted by csmpn_cloud_lift, with or without the 0-0 block
+# over the non-edges: cloud_capacity, cloud_batch_device, relift_(points, dis=...) on such a batch.
 
 
 def _lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, device) -> torch.Tensor:
@@ -778,6 +792,15 @@ def rips_capacity(n_graphs: int, verts_per_graph: int, max_edges: int, max_trian
         max_triangles = 0
     rows = (n_graphs * verts_per_graph, max_edges + 1) + ((max_triangles,) if max_dim == 2 else ())
     return BatchCapacity(rows, rips_adjacencies(n_graphs, verts_per_graph, max_edges, max_triangles))
+
+
+def cloud_capacity(n_graphs: int, verts_per_graph: int, max_edges: int, max_triangles: int, max_dim: int = 2,
+                   vertex_block: bool = False) -> BatchCapacity:
+    """rips_capacity for the batches of cloud_batch_device (up to 4096 vertices per graph): the same rows; the adjacencies are
+    rips_adjacencies with the vertex block and clique_adjacencies (6 n1 + 12 n2) without it, the default - the block has
+    V (V - 1) - n1 entries per graph."""
+    cap = rips_capacity(n_graphs, verts_per_graph, max_edges, max_triangles, max_dim)
+    return cap if vertex_block else BatchCapacity(cap.simplices, clique_adjacencies(max_edges, cap.simplices[2] if max_dim == 2 else 0))
 
 
 def clique_adjacencies(n_edges: int, n_triangles: int) -> int:
@@ -892,10 +915,21 @@ def clique_batch_device(points: torch.Tensor, n_graphs: int, capacity: BatchCapa
                                 features, vertex_features, x_ind_cols)
 
 
+def cloud_batch_device(points: torch.Tensor, n_graphs: int, dis: float, capacity: BatchCapacity, vertex_block: bool = False,
+                       features: Optional[Dict[str, torch.Tensor]] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
+                       x_ind_cols: Optional[int] = None) -> SimplicialBatch:
+    """rips_batch_device for point clouds of up to 4096 vertices per graph (rips_complex(points, dis, max_dim, vertex_block);
+    csmpn_cloud_lift) - one cloud of a few thousand points is a batch of one graph. The batch's plan records that it is a
+    cloud batch and its vertex_block: relift_(points, dis=...) then goes to ops.cloud_lift, and nothing else re-lifts it."""
+    return _lifted_batch_device("cloud_batch_device", "cloud_lift", points, n_graphs, (float(dis), bool(vertex_block)), capacity, features,
+                                vertex_features, x_ind_cols)
+
+
 def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, vertex_features, x_ind_cols) -> SimplicialBatch:
     """The body of rips_batch_device (op = "rips_lift", param = dis), knn_batch_device (op = "knn_lift", param = k),
-    hull_batch_device (op = "hull_lift", no parameter; the volumes become `target`) and clique_batch_device (op =
-    "clique_lift", param = (the list or k, edge_th, tri_th); its larger workspace serves the other lifts as well)."""
+    hull_batch_device (op = "hull_lift", no parameter; the volumes become `target`), clique_batch_device (op =
+    "clique_lift", param = (the list or k, edge_th, tri_th); its larger workspace serves the other lifts as well) and
+    cloud_batch_device (op = "cloud_lift", param = (dis, vertex_block); its workspace serves that lift alone)."""
     from csmpn_hip import ops
     if not points.is_cuda:
         raise RuntimeError(f"{what} needs device points (no CPU fallback)")
@@ -905,13 +939,16 @@ def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, 
                    edge_types=i64(E, 2), batch=i64(S), ptr=i64(B + 1), x_ind_batch=i64(S), x_ind_ptr=i64(B + 1))
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     counts = i64(max_dim + 2)
-    clique = op == "clique_lift"
+    clique, cloud = op == "clique_lift", op == "cloud_lift"
     ws = ops.clique_lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev) if clique else \
+        ops.cloud_lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev) if cloud else \
         _lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev)
     volume = torch.zeros(B, dtype=torch.float32, device=dev) if op == "hull_lift" else None
     run = getattr(ops, op) if volume is None else (lambda p, b, _, *rest: ops.hull_lift(p, b, *rest, volume=volume))
     if clique:
         run = lambda p, b, src, *rest: ops.clique_lift(p, b, src[0], *rest, edge_th=src[1], tri_th=src[2])
+    if cloud:
+        run = lambda p, b, prm, *rest: ops.cloud_lift(p, b, prm[0], *rest, vertex_block=prm[1])
     run(points, B, param, max_dim, capacity.simplices, E, tensors["x_ind"], tensors["node_types"], tensors["batch"],
         tensors["x_ind_batch"], tensors["ptr"], tensors["x_ind_ptr"], tensors["edge_index"], tensors["edge_types"], counts, status, ws)
     word = int(status.item())
@@ -935,4 +972,6 @@ def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, 
     plan["lift_ws"], plan["lift_status"], plan["lift_counts"] = ws, status, counts
     if clique:
         plan["clique_lift_ws"] = ws
+    if cloud:
+        plan["cloud"] = {"vertex_block": param[1]}
     return out

@@ -125,7 +125,12 @@ class GraphedTrainStep:
     (-1, -1) padding, so lists of changing length replay through the same addresses. `edge_th` / `tri_th` (defaults of the step,
     or in the call; +infinity where neither names one) go with edges or knn: a k with a threshold lifts the thresholded
     cliques of the k-nearest-neighbour graph through the same entry; with dis or hull they are a ValueError. A list with an end
-    outside the batch or across two graphs leaves the batch as it was and shows as bit 5 of the lift's word in status()."""
+    outside the batch or across two graphs leaves the batch as it was and shows as bit 5 of the lift's word in status().
+
+    A `batch` built by csmpn.data.complexes.cloud_batch_device (the Rips complexes of point clouds of up to 4096 vertices per
+    graph; csmpn_cloud_lift) is taken as it is - it lives on the device at `capacity` already, and its plan says which lift
+    re-lifts it: step(points=..., dis=...) is the only device lift of such a step; knn, hull, edges and the thresholds are a
+    ValueError there."""
 
     hull = False
     edges = False
@@ -154,7 +159,13 @@ class GraphedTrainStep:
                 simplex_features = [k for k in feature_names if hasattr(batch, k) and getattr(batch, k).dim() >= 1
                                     and int(getattr(batch, k).shape[0]) == rows]
             self.simplex_features = tuple(simplex_features)
-            batch = pad_batch(batch, capacity, self.simplex_features).to(device)
+            if (getattr(batch, "_plan", None) or {}).get("cloud") is not None:
+                # a batch of cloud_batch_device is on the device at its capacity already, and its plan says which lift
+                # re-lifts it (csmpn_cloud_lift: more than 64 vertices per graph) - padding would make a plain batch of it
+                if int(batch.node_types.shape[0]) != capacity.rows or int(batch.edge_index.shape[1]) != capacity.edges:
+                    raise ValueError("GraphedTrainStep: the cloud batch was not built at `capacity`")
+            else:
+                batch = pad_batch(batch, capacity, self.simplex_features).to(device)
         dev = batch.edge_index.device
         if dev.type != "cuda":
             raise RuntimeError("GraphedTrainStep needs a device batch (no CPU fallback)")

@@ -1552,3 +1552,27 @@ def clique_lift(points, n_graphs, source, max_dim, capacity_rows, capacity_edges
             C.addressof(cap), E, x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), batch.data_ptr(),
             x_ind_batch.data_ptr(), ptr.data_ptr(), x_ind_ptr.data_ptr(), edge_index.data_ptr(), _ptr(edge_types), _ptr(counts),
             _ptr(status), workspace.data_ptr(), workspace.numel(), _stream(dev)))
+
+
+def cloud_lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, device) -> torch.Tensor:
+    """Workspace of cloud_lift (uninitialised device bytes): the mask words and ranks of every vertex, V^2 (1 / 8 + 1 / 16) bytes
+    per graph."""
+    return torch.empty(max(int(native.lib().csmpn_cloud_lift_workspace_bytes(int(n_graphs), int(verts_per_graph), int(max_dim))), 16),
+                       dtype=torch.uint8, device=device)
+
+
+def cloud_lift(points, n_graphs, dis, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch, x_ind_batch, ptr,
+               x_ind_ptr, edge_index, edge_types, counts, status, workspace, vertex_block=False):
+    """csmpn_cloud_lift: rips_lift for point clouds of up to 4096 vertices per graph - the structure tensors of
+    pad_batch(collate([rips_complex(points of graph g, dis, max_dim, vertex_block)]), capacity), same buffers, same status
+    bits. vertex_block=True: the adjacencies of rips_lift (the 0_0 block over the non-edges included); False: those of
+    knn_lift, 6 n1 + 12 n2."""
+    B, V, E, cap = _lift_arguments("cloud_lift", points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch,
+                                   x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status)
+    dev = points.device
+    with torch.cuda.device(dev):
+        check(native.lib().csmpn_cloud_lift(
+            points.data_ptr(), int(points.shape[1]), B, V, float(dis), int(vertex_block), int(max_dim), C.addressof(cap), E,
+            x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), batch.data_ptr(), x_ind_batch.data_ptr(), ptr.data_ptr(),
+            x_ind_ptr.data_ptr(), edge_index.data_ptr(), _ptr(edge_types), _ptr(counts), _ptr(status), workspace.data_ptr(),
+            workspace.numel(), _stream(dev)))

@@ -17,6 +17,10 @@
 // triangle, and writes the final masks and a 64-wide table T - three surviving edges need not bound a surviving triangle,
 // so the scatter reads T as the hull's does (kFacetTable = true, kTableStride = 64, no vertex block).
 //
+// csmpn_cloud_lift is the Rips lift of graphs of up to 4096 vertices, with or without the vertex block: several mask words per
+// vertex, one wave per vertex and kernels of its own - the section "the Rips lift of point clouds" below. Everything up to
+// there is the four lifts of small graphs:
+//
 // A graph has at most 64 vertices, so ONE 64-bit neighbour mask per vertex (a wave ballot over the other vertices) carries
 // it, and every index is a popcount of masks plus a scan: with upper[a] = mask[a] restricted to b > a,
 //   index of the edge (a, b), a < b      = sum_{a' < a} popc(upper[a']) + popc(upper[a] & below(b))
@@ -726,15 +730,252 @@ __global__ __launch_bounds__(kBlock) void lift_clique_scatter_kernel(long B, int
         scatter_fillers((long)blockIdx.x - B, (long)gridDim.x - B, B, max_dim, cap, hdr, o);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// ------------------------------------------------------------------------------- the Rips lift of point clouds, V > 64
+//
+// csmpn_cloud_lift: the Rips rule of lift_count_kernel on graphs of up to kCloudMaxVerts vertices. A vertex has
+// W = ceil(V / 64) mask words, masks[g][a][w] bit i = vertex 64 w + i is close to a (bits at or above V are never set), and
+// the closed forms above hold with sums over the words. One workgroup per graph no longer fills the chip (B = 1 is the case
+// the entry is for) and a graph's masks no longer fit LDS, so the grid is (graph, tile of kWaves vertices), one wave per
+// vertex, and the per-vertex prefix sums are read from the workspace:
+//   mask     a wave per vertex a: for every word, lane = the vertex inside it, a ballot = the word; beside it
+//            rank[g][a][w] = the upper neighbours of a in the words in front of w (the index of the edge (a, c) is then
+//            up_s[a] + rank[a][c / 64] + one popcount), and the vertex's degree deg[a] and upper degree up[a]
+//   count    (max_dim = 2) a wave per vertex a, lane = a WORD: for every upper neighbour b ascending the lanes load the row of
+//            b and add popc(up_a & m_b & above b) and popc(m_a & m_b) -> tri[a], cof[a] (triangles / cofaces of a's edges)
+//   scan     a workgroup per graph: deg / up / tri / cof -> their exclusive prefixes over the vertices, in place; n1, n2
+//   offsets  lift_offsets_kernel, unchanged
+//   scatter  a wave per vertex a + the filler workgroups: the rows and adjacencies of scatter_graph at the same positions;
+//            the prefix of tri / cof inside a's edges is a wave scan per word plus a carry over the words
+// No atomic, no LDS array sized by V. A graph's triangles can pass 2^31 long before the capacity is read (C(4096, 3)): the
+// scan sums in 64 bits and n2 saturates at INT_MAX, which no capacity admits, so such a batch is refused (bit 2) and the
+// truncated prefixes are never read.
 
-inline bool sizes_ok(int64_t n_graphs, int32_t V, int32_t max_dim) {
-    return (max_dim == 1 || max_dim == 2) && V > max_dim && V <= kMaxVerts && n_graphs > 0 && n_graphs < (1ll << 31) / V;
+constexpr int kCloudMaxVerts = 4096;                          // W <= 64: a lane per word in the count kernel
+
+constexpr int cloud_words(int V) { return (V + 63) / 64; }
+
+// the bits of word `word` that belong to vertices above v
+__device__ __forceinline__ u64 above_in(int word, int v) {
+    const int wv = v >> 6;
+    return word < wv ? 0ull : word == wv ? above(v & 63) : ~0ull;
 }
 
-enum class Lift { rips, knn, hull, clique };
+// one wave per vertex a of graph g = blockIdx.x / tiles: its mask words, ranks, degree and upper degree -> workspace
+__global__ __launch_bounds__(kBlock) void cloud_mask_kernel(const float* points, int P, int V, int W, int tiles, double dis2, u64* masks,
+                                                             int* rank, int* deg, int* up) {
+    const long g = blockIdx.x / (unsigned)tiles;
+    const int lane = threadIdx.x & 63, a = (int)(blockIdx.x % (unsigned)tiles) * kWaves + (threadIdx.x >> 6);
+    if (a >= V) return;                                       // the whole wave
+    const float* pg = points + g * V * (long)P;
+    const long long va = (long long)g * V + a;
+    u64* ma = masks + va * W;
+    int* ra = rank + va * W;
+    int nd = 0, nu = 0;
+    for (int w = 0; w < W; ++w) {
+        const int b = w * 64 + lane;
+        bool close = false;
+        if (b < V && b != a) {                                // a lane past V reads no point and sets no bit
+            double s = 0.0;
+            for (int k = 0; k < P; ++k) {
+                const double d = sub_rn((double)pg[a * P + k], (double)pg[b * P + k]);
+                s = add_rn(s, mul_rn(d, d));                  // no contraction: the sum the host takes
+            }
+            close = s <= dis2;                                // false for a NaN
+        }
+        const u64 word = __ballot(close);
+        if (lane == 0) {
+            ma[w] = word;
+            ra[w] = nu;
+        }
+        nd += __popcll(word);
+        nu += __popcll(word & above_in(w, a));
+    }
+    if (lane == 0) {
+        deg[va] = nd;
+        up[va] = nu;
+    }
+}
+
+// one wave per vertex a; lane = word: tri[a] = the triangles (a, b, c), a < b < c, cof[a] = the cofaces of the edges (a, b), a < b
+__global__ __launch_bounds__(kBlock) void cloud_count_kernel(int V, int W, int tiles, const u64* masks, int* tri, int* cof) {
+    const long g = blockIdx.x / (unsigned)tiles;
+    const int lane = threadIdx.x & 63, a = (int)(blockIdx.x % (unsigned)tiles) * kWaves + (threadIdx.x >> 6);
+    if (a >= V) return;
+    const u64* mg = masks + (long long)g * V * W;
+    const u64 ma = lane < W ? mg[(long long)a * W + lane] : 0ull;
+    const u64 ua = ma & above_in(lane, a);
+    int t = 0, c = 0;
+    for (int w = a >> 6; w < W; ++w)
+        for (u64 r = __shfl(ua, w, 64); r; r &= r - 1) {      // wave-uniform: the upper neighbours b of a, ascending
+            const int b = w * 64 + first_bit(r);
+            const u64 mb = lane < W ? mg[(long long)b * W + lane] : 0ull;
+            t += __popcll(ua & mb & above_in(lane, b));
+            c += __popcll(ma & mb);
+        }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        t += __shfl_down(t, d, 64);
+        c += __shfl_down(c, d, 64);
+    }
+    if (lane == 0) {
+        tri[(long long)g * V + a] = t;
+        cof[(long long)g * V + a] = c;
+    }
+}
+
+using CloudScan = hipcub::BlockScan<long long, kBlock>;
+
+// x[0 .. V) -> its exclusive prefix sums, in place (kBlock vertices per pass); returns the total
+__device__ __forceinline__ long long cloud_scan_in_place(int* x, int V, typename CloudScan::TempStorage& temp) {
+    long long carry = 0;
+    for (int v0 = 0; v0 < V; v0 += kBlock) {
+        const int v = v0 + threadIdx.x;
+        long long excl, sum;
+        CloudScan(temp).ExclusiveSum(v < V ? (long long)x[v] : 0ll, excl, sum);
+        __syncthreads();
+        if (v < V) x[v] = (int)(carry + excl);
+        carry += sum;
+    }
+    return carry;
+}
+
+// one workgroup per graph
+__global__ __launch_bounds__(kBlock) void cloud_scan_kernel(int V, int max_dim, int* deg, int* up, int* tri, int* cof, int* n1, int* n2) {
+    __shared__ typename CloudScan::TempStorage temp;
+    const long long v0 = (long long)blockIdx.x * V;
+    cloud_scan_in_place(deg + v0, V, temp);
+    const long long e = cloud_scan_in_place(up + v0, V, temp);    // <= V (V - 1) / 2
+    long long t = 0;
+    if (max_dim >= 2) {
+        t = cloud_scan_in_place(tri + v0, V, temp);
+        cloud_scan_in_place(cof + v0, V, temp);
+    }
+    if (threadIdx.x == 0) {
+        n1[blockIdx.x] = (int)e;
+        n2[blockIdx.x] = t > 0x7fffffffll ? 0x7fffffff : (int)t;
+    }
+}
+
+// index, among its graph's edges, of the edge (lo, hi), lo < hi; mg / rg / up_s are the graph's masks, ranks and scanned `up`
+__device__ __forceinline__ long long cloud_edge(const u64* mg, const int* rg, const int* up_s, int W, int lo, int hi) {
+    const int w = hi >> 6;
+    const long long i = (long long)lo * W + w;
+    return (long long)up_s[lo] + rg[i] + __popcll(mg[i] & above_in(w, lo) & below(hi & 63));
+}
+
+// The part of vertex a in the real part of graph g, run by one wave: scatter_graph's rows and adjacencies at scatter_graph's
+// positions. The wave walks a's words; in word w its lane holds the pair (a, b = 64 w + lane).
+template <bool kVertexBlock>
+__device__ void cloud_scatter_vertex(long g, int a, int lane, int V, int W, int max_dim, const u64* masks, const int* rank, const int* deg,
+                                     const int* up, const int* tri, const int* cof, const int* n1s, const int* n2s,
+                                     const long long* row_off, const long long* adj_off, const Outputs& o) {
+    const long long v0 = (long long)g * V;
+    const u64* mg = masks + v0 * W;
+    const int* rg = rank + v0 * W;
+    const int *deg_s = deg + v0, *up_s = up + v0;
+    const long long n1 = n1s[g], n2 = n2s[g], row0 = row_off[g], adj0 = adj_off[g];
+    const long long VV = kVertexBlock ? (long long)V * (V - 1) : 0ll;
+    const long long o1 = adj0, o2 = o1 + 2 * n1, o3 = kVertexBlock ? adj0 + VV + n1 : o2, o4 = o3 + 2 * n1, o5 = o4 + 2 * n1, o6 = o5 + 6 * n2,
+                    o7 = o6 + 3 * n2;
+    const long long e0 = row0 + V, t0 = e0 + n1;              // first edge row, first triangle row
+    const u64* ma = mg + (long long)a * W;
+    if (lane == 0) put_row(o, row0 + a, 0, g, a, 0, 0);
+    // in front of word w: the block-1 entries of a and of the vertices before it, the edges, the triangles and the cofaces
+    long long nd = deg_s[a], nu = up_s[a], tb = max_dim >= 2 ? tri[v0 + a] : 0, cb = max_dim >= 2 ? cof[v0 + a] : 0;
+    for (int w = 0; w < W; ++w) {
+        const int b = w * 64 + lane;
+        const u64 maw = ma[w], uaw = maw & above_in(w, a);
+        if ((maw >> lane) & 1ull) put_adj(o, o1 + nd + __popcll(maw & below(lane)), row0 + b, row0 + a, 0, 0);
+        if (kVertexBlock && b < V && b != a && !((uaw >> lane) & 1ull))
+            put_adj(o, o2 + (long long)a * (V - 1) + b - (b > a ? 1 : 0) - nu - __popcll(uaw & below(lane)), row0 + a, row0 + b, 0, 0);
+        nd += __popcll(maw);
+        if (uaw == 0ull) continue;                            // the whole wave: no edge (a, b) in this word
+        const bool edge = (uaw >> lane) & 1ull;               // the pair (a, b), a < b, is an edge
+        const u64* mb = mg + (long long)b * W;                // read by the edge lanes alone (b < V there)
+        int nt = 0, nc = 0;                                   // its triangles (a, b, c) and its cofaces {a, b, x}
+        if (edge && max_dim >= 2)
+            for (int x = 0; x < W; ++x) {
+                const u64 both = ma[x] & mb[x];
+                nc += __popcll(both);
+                nt += __popcll(both & above_in(x, b));
+            }
+        int sum_t, sum_c;
+        long long t = tb + wave_scan(nt, lane, &sum_t), k = cb + wave_scan(nc, lane, &sum_c);
+        tb += sum_t;
+        cb += sum_c;
+        const long long e = nu + __popcll(uaw & below(lane)), erow = e0 + e;
+        nu += __popcll(uaw);
+        if (!edge) continue;
+        put_row(o, erow, 1, g, a, b, 0);
+        put_adj(o, o3 + 2 * e, row0 + a, erow, 0, 1);
+        put_adj(o, o3 + 2 * e + 1, row0 + b, erow, 0, 1);
+        put_adj(o, o4 + 2 * e, erow, row0 + a, 1, 0);
+        put_adj(o, o4 + 2 * e + 1, erow, row0 + b, 1, 0);
+        if (max_dim < 2) continue;
+        for (int x = w; x < W; ++x) {                         // c > b: from b's word on
+            const u64 ubx = mb[x] & above_in(x, b);
+            for (u64 r = ma[x] & ubx; r; r &= r - 1, ++t) {
+                const int ci = first_bit(r), c = x * 64 + ci;
+                const long long trow = t0 + t;
+                const long long eac = e0 + cloud_edge(mg, rg, up_s, W, a, c);
+                const long long ebc = e0 + up_s[b] + rg[(long long)b * W + x] + __popcll(ubx & below(ci));
+                put_row(o, trow, 2, g, a, b, c);
+                put_adj(o, o6 + 3 * t, erow, trow, 1, 2);
+                put_adj(o, o6 + 3 * t + 1, eac, trow, 1, 2);
+                put_adj(o, o6 + 3 * t + 2, ebc, trow, 1, 2);
+                put_adj(o, o7 + 3 * t, trow, erow, 2, 1);
+                put_adj(o, o7 + 3 * t + 1, trow, eac, 2, 1);
+                put_adj(o, o7 + 3 * t + 2, trow, ebc, 2, 1);
+            }
+        }
+        for (int x = 0; x < W; ++x)
+            for (u64 r = ma[x] & mb[x]; r; r &= r - 1, ++k) {
+                const int y = x * 64 + first_bit(r);
+                // in the sorted triple of {a, b, y} the edge {a, y} always comes before {b, y}
+                const long long eay = e0 + cloud_edge(mg, rg, up_s, W, a < y ? a : y, a < y ? y : a);
+                const long long eby = e0 + cloud_edge(mg, rg, up_s, W, b < y ? b : y, b < y ? y : b);
+                put_adj(o, o5 + 2 * k, eay, erow, 1, 1);
+                put_adj(o, o5 + 2 * k + 1, eby, erow, 1, 1);
+            }
+    }
+}
+
+template <bool kVertexBlock>
+__global__ __launch_bounds__(kBlock) void cloud_scatter_kernel(long B, int V, int W, int tiles, int max_dim, Capacity cap, const Header* hdr,
+                                                                const u64* masks, const int* rank, const int* deg, const int* up,
+                                                                const int* tri, const int* cof, const int* n1, const int* n2,
+                                                                const long long* row_off, const long long* adj_off, Outputs o) {
+    if (!hdr->fit) return;
+    const long n_real = B * tiles;                            // workgroups of the real part
+    if ((long)blockIdx.x < n_real) {
+        const int a = (int)(blockIdx.x % (unsigned)tiles) * kWaves + (threadIdx.x >> 6);
+        if (a < V)
+            cloud_scatter_vertex<kVertexBlock>((long)(blockIdx.x / (unsigned)tiles), a, threadIdx.x & 63, V, W, max_dim, masks, rank, deg, up,
+                                               tri, cof, n1, n2, row_off, adj_off, o);
+    } else {
+        scatter_fillers((long)blockIdx.x - n_real, (long)gridDim.x - n_real, B, max_dim, cap, hdr, o);
+    }
+}
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+inline bool sizes_ok(int64_t n_graphs, int32_t V, int32_t max_dim, int32_t max_verts = kMaxVerts) {
+    return (max_dim == 1 || max_dim == 2) && V > max_dim && V <= max_verts && n_graphs > 0 && n_graphs < (1ll << 31) / V;
+}
+
+enum class Lift { rips, knn, hull, clique, cloud };
+
+// csmpn_cloud_lift: alignment slack + header | masks [B, V, W] | rank [B, V, W] | deg, up, tri, cof [B, V] | n1 | n2 |
+// row offsets | adjacency offsets, W = ceil(V / 64) - V^2 / 8 bytes of masks and V^2 / 16 of ranks per graph
+inline size_t cloud_workspace_bytes_of(int64_t n_graphs, int32_t V, int32_t max_dim) {
+    if (!sizes_ok(n_graphs, V, max_dim, kCloudMaxVerts)) return 0;
+    const size_t B = (size_t)n_graphs, BV = B * (size_t)V, BVW = BV * (size_t)cloud_words(V);
+    return 256 + 256 + align256(sizeof(u64) * BVW) + align256(sizeof(int) * BVW) + 4 * align256(sizeof(int) * BV) +
+           2 * align256(sizeof(int) * B) + 2 * align256(sizeof(long long) * B);
+}
 
 inline size_t workspace_bytes_of(int64_t n_graphs, int32_t V, int32_t max_dim, Lift kind = Lift::rips) {
+    if (kind == Lift::cloud) return cloud_workspace_bytes_of(n_graphs, V, max_dim);
     if (!sizes_ok(n_graphs, V, max_dim) || (kind == Lift::hull && V > kHullMaxVerts)) return 0;
     const size_t B = (size_t)n_graphs;
     // alignment slack + header | masks | n1 | n2 | row offsets | adjacency offsets; the hull lift: | T tables | volumes;
@@ -769,20 +1010,25 @@ struct CliqueSource {            // what csmpn_clique_lift adds: the graph (a li
 // the checks the entries share, before the first HIP call; `what` names the entry in the messages. dis >= 0: the Rips
 // threshold, knn_k: the k of the kNN entry (0 for the others) - each checked where csmpn_rips_lift has always checked dis; the
 // hull entry checks its point dimension there, and its 16 vertices where the others check their 64; the clique entry checks
-// its graph source and its thresholds there.
-int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, Lift kind, Capacity* cap, const CliqueSource* src = nullptr) {
+// its graph source and its thresholds there; the cloud entry checks its kCloudMaxVerts vertices where the others check their
+// 64, and its vertex_block behind dis.
+int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, Lift kind, Capacity* cap, const CliqueSource* src = nullptr,
+                    int vertex_block = 0) {
     const int V = a.verts_per_graph, max_dim = a.max_dim;
     const bool knn = kind == Lift::knn, hull = kind == Lift::hull;
     if (max_dim < 0) return csmpn_fail(CSMPN_ERR_INVALID, "max_dim %d is negative", max_dim);
     if (max_dim != 1 && max_dim != 2) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: max_dim %d (1 or 2)", what, max_dim);
     if (hull && V > kHullMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > %d (every subset of point_dim vertices is tried)", what, V, kHullMaxVerts);
-    if (V > kMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > %d (one 64-bit mask per vertex)", what, V, kMaxVerts);
+    if (kind == Lift::cloud && V > kCloudMaxVerts)
+        return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > kCloudMaxVerts = %d (V^2 / 8 bytes of masks and V^2 pair tests per graph)", what, V, kCloudMaxVerts);
+    if (kind != Lift::cloud && V > kMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > %d (one 64-bit mask per vertex)", what, V, kMaxVerts);
     if (V <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "%s: %d vertices per graph, max_dim %d needs %d", what, V, max_dim, max_dim + 1);
     if (a.n_graphs <= 0 || a.n_graphs >= (1ll << 31) / V) return csmpn_fail(CSMPN_ERR_INVALID, "bad sizes n_graphs=%lld verts_per_graph=%d", (long long)a.n_graphs, V);
     if (a.point_dim <= 0) return csmpn_fail(CSMPN_ERR_INVALID, "point_dim %d", (int)a.point_dim);
     if (hull && (a.point_dim < 2 || a.point_dim > 5)) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: points in R^%d (2 .. 5)", what, (int)a.point_dim);
     if (hull && V <= a.point_dim) return csmpn_fail(CSMPN_ERR_INVALID, "%s: %d vertices per graph in R^%d (a hull needs %d)", what, V, (int)a.point_dim, (int)a.point_dim + 1);
     if (!knn && !hull && !(dis >= 0.0)) return csmpn_fail(CSMPN_ERR_INVALID, "dis %g is negative or not a number", dis);
+    if (kind == Lift::cloud && vertex_block != 0 && vertex_block != 1) return csmpn_fail(CSMPN_ERR_INVALID, "%s: vertex_block %d (0 or 1)", what, vertex_block);
     if (knn && knn_k < 1) return csmpn_fail(CSMPN_ERR_INVALID, "%s: k = %d (at least 1)", what, knn_k);
     if (kind == Lift::clique) {
         if ((src->edge_list != nullptr) == (knn_k >= 1))
@@ -891,9 +1137,72 @@ int launch_lift(const char* what, const LiftArgs& a, const Capacity& cap, double
     return CSMPN_OK;
 }
 
+// csmpn_cloud_lift behind the argument checks: the workspace carved up (cloud_workspace_bytes_of), then five launches - four
+// for max_dim = 1, which has no triangle to count.
+int launch_cloud_lift(const char* what, const LiftArgs& a, const Capacity& cap, double dis, bool vertex_block) {
+    hipStream_t st = (hipStream_t)a.stream;
+    const int V = a.verts_per_graph, W = cloud_words(V), max_dim = a.max_dim, tiles = (V + kWaves - 1) / kWaves;
+    const size_t B = (size_t)a.n_graphs, BV = B * (size_t)V, BVW = BV * (size_t)W;
+    char* ws = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(a.workspace)));
+    const auto carve = [&ws](size_t bytes) {
+        char* p = ws;
+        ws += align256(bytes);
+        return p;
+    };
+    Header* hdr = reinterpret_cast<Header*>(carve(256));
+    u64* masks = reinterpret_cast<u64*>(carve(sizeof(u64) * BVW));
+    int* rank = reinterpret_cast<int*>(carve(sizeof(int) * BVW));
+    int* deg = reinterpret_cast<int*>(carve(sizeof(int) * BV));
+    int* up = reinterpret_cast<int*>(carve(sizeof(int) * BV));
+    int* tri = reinterpret_cast<int*>(carve(sizeof(int) * BV));
+    int* cof = reinterpret_cast<int*>(carve(sizeof(int) * BV));
+    int* n1 = reinterpret_cast<int*>(carve(sizeof(int) * B));
+    int* n2 = reinterpret_cast<int*>(carve(sizeof(int) * B));
+    long long* row_off = reinterpret_cast<long long*>(carve(sizeof(long long) * B));
+    long long* adj_off = reinterpret_cast<long long*>(carve(sizeof(long long) * B));
+    Outputs out{a.x_ind, a.node_types, a.batch, a.x_ind_batch, a.edge_index, a.edge_types, (int)a.x_ind_cols, cap.edges};
+    const long long fill_items = std::max(cap.rows[1] + cap.rows[2], cap.edges);
+    const long fill_blocks = (long)std::min<long long>(std::max<long long>((fill_items + kBlock - 1) / kBlock, 1), kMaxFillBlocks);
+    const dim3 per_vertex((unsigned)(B * (size_t)tiles)), per_graph((unsigned)B), one(1), scatter((unsigned)(B * (size_t)tiles + fill_blocks)),
+        block(kBlock);
+    hipLaunchKernelGGL(cloud_mask_kernel, per_vertex, block, 0, st, a.points, (int)a.point_dim, V, W, tiles, dis * dis, masks, rank, deg, up);
+    if (max_dim >= 2) hipLaunchKernelGGL(cloud_count_kernel, per_vertex, block, 0, st, V, W, tiles, (const u64*)masks, tri, cof);
+    hipLaunchKernelGGL(cloud_scan_kernel, per_graph, block, 0, st, V, max_dim, deg, up, tri, cof, n1, n2);
+#define CSMPN_CLOUD_TAIL(BLOCK)                                                                                                                   \
+    hipLaunchKernelGGL(lift_offsets_kernel<BLOCK>, one, block, 0, st, (const int*)n1, (const int*)n2, (long)B, V, max_dim, cap, hdr, row_off,    \
+                       adj_off, a.ptr, a.x_ind_ptr, a.counts, (unsigned*)a.status);                                                              \
+    hipLaunchKernelGGL(cloud_scatter_kernel<BLOCK>, scatter, block, 0, st, (long)B, V, W, tiles, max_dim, cap, (const Header*)hdr,                \
+                       (const u64*)masks, (const int*)rank, (const int*)deg, (const int*)up, (const int*)tri, (const int*)cof, (const int*)n1,   \
+                       (const int*)n2, (const long long*)row_off, (const long long*)adj_off, out)
+    if (vertex_block) {
+        CSMPN_CLOUD_TAIL(true);
+    } else {
+        CSMPN_CLOUD_TAIL(false);
+    }
+#undef CSMPN_CLOUD_TAIL
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return csmpn_fail(CSMPN_ERR_HIP, "%s kernels: %s", what, hipGetErrorString(e));
+    return CSMPN_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t csmpn_cloud_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim) {
+    return workspace_bytes_of(n_graphs, verts_per_graph, max_dim, Lift::cloud);
+}
+
+int csmpn_cloud_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, double dis, int32_t vertex_block,
+                     int32_t max_dim, const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols,
+                     int64_t* node_types, int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index,
+                     int64_t* edge_types, int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const LiftArgs a{points, point_dim, n_graphs, verts_per_graph, max_dim, capacity_rows, capacity_edges, x_ind, x_ind_cols, node_types,
+                     batch, x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status, workspace, workspace_bytes, stream};
+    Capacity cap{};
+    if (const int rc = check_lift_args("cloud lift", a, dis, 0, Lift::cloud, &cap, nullptr, (int)vertex_block)) return rc;
+    return launch_cloud_lift("cloud lift", a, cap, dis, vertex_block == 1);
+}
 
 size_t csmpn_rips_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim) {
     return workspace_bytes_of(n_graphs, verts_per_graph, max_dim);

@@ -543,6 +543,35 @@ int csmpn_clique_lift(const float* points, int32_t point_dim, int64_t n_graphs, 
                       int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
                       int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The Rips lift of point clouds of up to 4096 vertices per graph: the structure tensors of exactly the batch that
+ *   pad_batch(collate([rips_complex(points_g, dis, max_dim, vertex_block) for g]), BatchCapacity(capacity_rows, capacity_edges))
+ * builds on the host, written into buffers of the capacity's shapes: no allocation, no host round trip, every launch on
+ * `stream` (five; four for max_dim = 1), no atomic anywhere - every position is computed from popcounts of the neighbour
+ * masks (ceil(verts_per_graph / 64) 64-bit words per vertex), a table of per-word ranks and scans, so the outputs hold the
+ * same bits in every call. One wave per vertex: a single graph of 4096 vertices fills the device.
+ *   points, the rule (vertices a and b are close iff sum_k ((double)p_a[k] - (double)p_b[k])^2 <= dis^2, summed in double over
+ *     k ascending, every difference, product and sum rounded once, none contracted; a NaN vertex is close to nothing;
+ *     dis >= 0), capacity_rows, the outputs, a graph's real rows and the fillers are those of csmpn_rips_lift;
+ *   vertex_block = 1: a graph's adjacencies are those of csmpn_rips_lift, with the V (V - 1) - n1 entries of the 0_0 block
+ *     over the non-edges: V (V - 1) + 5 n1 + 12 n2 for n1 edges and n2 triangles; vertex_block = 0: the same order WITHOUT
+ *     that block, 6 n1 + 12 n2, the layout of csmpn_knn_lift (lift(..., vertex_block=False)); any other value:
+ *     CSMPN_ERR_INVALID. On verts_per_graph <= 64 (accepted too) vertex_block = 1 gives the bits of csmpn_rips_lift.
+ * A batch that does not fit leaves EVERY output as it was and ORs the bits 1..4 of csmpn_rips_lift into *status. A graph with
+ * more than 2^31 - 1 triangles is counted as one with 2^31 - 1, which no capacity admits (bit 2).
+ * Limits: max_dim in {1, 2} and verts_per_graph <= 4096 (kCloudMaxVerts in csrc/lift.hip: the workspace holds
+ * verts_per_graph^2 / 8 bytes of masks per graph and the pair test is quadratic; beyond it a cell grid is the tool), else
+ * CSMPN_ERR_UNSUPPORTED; every other check, its code and its place are those of csmpn_rips_lift, vertex_block being checked
+ * behind dis. Arguments are checked before the first HIP call.
+ * workspace: csmpn_cloud_lift_workspace_bytes(...) bytes of device memory (host-only query; 0 for sizes the entry point
+ * rejects): with B = n_graphs, V = verts_per_graph, W = ceil(V / 64): 512 + 8 B V W (masks) + 4 B V W (ranks) + 4 x 4 B V
+ * (degrees, upper degrees, triangle and coface counts per vertex, then their prefixes) + 24 B bytes, every part rounded up to
+ * 256; needs no initialisation. */
+size_t csmpn_cloud_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim);
+int csmpn_cloud_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, double dis, int32_t vertex_block,
+                     int32_t max_dim, const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols,
+                     int64_t* node_types, int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index,
+                     int64_t* edge_types, int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fused simplex feature embedding (round 3; hulls_cssmpnn.py:96-125: vertex features of every d-simplex in all (d+1)!
  * vertex orders -> CEMLP -> sum over the orders), for the shapes the wide parity-lane kernels serve as standalone CEMLPs
  * (Cl(5,0) / Cl(4,1), 16 / 24 / 28 / 32 output channels, at most 8 input channels = verts_per_row * channels_per_vertex);
