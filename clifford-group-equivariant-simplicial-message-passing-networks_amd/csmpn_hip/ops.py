@@ -319,9 +319,12 @@ class _EmbedCemlpFn(torch.autograd.Function):
 
 
 def embed_cemlp_supported(binding: CemlpBinding, verts_per_row: int, channels_per_vertex: int) -> bool:
-    """Shapes the fused embedding serves: Cl(5,0) / Cl(4,1), 16 / 24 / 28 / 32 output channels, <= 8 input channels."""
-    return (binding.n == 5 and binding.nblk in (1, 2) and binding.out_features in (16, 24, 28, 32)
-            and verts_per_row * channels_per_vertex == binding.in_features <= 8)
+    """Shapes the fused embedding serves - the two MODE_PLAIN programs of the wide parity-lane kernels (csrc/plw_inst.inc):
+    Cl(5,0) / Cl(4,1), 28 output channels, 2 input channels in one block or 3 in two blocks. Everything else composes
+    simplex_rows + CEMLP + sum (csmpn_embed_cemlp_forward returns CSMPN_ERR_UNSUPPORTED there)."""
+    return (binding.n == 5 and binding.out_features == 28 and (binding.in_features, binding.nblk) in ((2, 1), (3, 2))
+            and all(int(binding.params[k].out_features) == 28 for k in range(binding.nblk))
+            and verts_per_row * channels_per_vertex == binding.in_features)
 
 
 def embed_cemlp_apply(vertex_feat, verts_i32, n_orders, binding: CemlpBinding, params, validated=False):

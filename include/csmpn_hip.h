@@ -573,9 +573,11 @@ int csmpn_cloud_lift(const float* points, int32_t point_dim, int64_t n_graphs, i
                      int64_t* edge_types, int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Fused simplex feature embedding (round 3; hulls_cssmpnn.py:96-125: vertex features of every d-simplex in all (d+1)!
- * vertex orders -> CEMLP -> sum over the orders), for the shapes the wide parity-lane kernels serve as standalone CEMLPs
- * (Cl(5,0) / Cl(4,1), 16 / 24 / 28 / 32 output channels, at most 8 input channels = verts_per_row * channels_per_vertex);
- * every other shape returns CSMPN_ERR_UNSUPPORTED (the caller composes csmpn_simplex_rows + csmpn_cemlp_* + a sum).
+ * vertex orders -> CEMLP -> sum over the orders), for the two standalone programs the wide parity-lane kernels are
+ * instantiated for (Cl(5,0) / Cl(4,1), blocks of 28 output channels; in_features = verts_per_row * channels_per_vertex = 2
+ * with one block, or 3 with two blocks: the edge and triangle embeddings of the convex-hulls model);
+ * every other shape - 16 / 24 / 32 channels and other input widths included - returns CSMPN_ERR_UNSUPPORTED (the caller
+ * composes csmpn_simplex_rows + csmpn_cemlp_* + a sum).
  *   vertex_feat [n_feature_rows, channels_per_vertex, D]  the embedded (full multivector) features of every batch row;
  *   verts [n_rows, verts_per_row] int32: row r = vertex order r % n_orders of simplex r / n_orders (n_rows = n_simplices * n_orders);
  *   out [n_simplices, O, D]: out[s] = sum over its n_orders rows of CEMLP(concat_v vertex_feat[verts[r][v]]).
