@@ -365,8 +365,11 @@ class SimplicialBatch:
             setattr(self, k, v)
         self._csr = None
 
-    def to(self, device):
-        out = SimplicialBatch(**{k: getattr(self, k).to(device) for k in self._names})
+    def to(self, device, dtype=None):
+        """The batch on `device`; dtype: cast the floating feature tensors to it (the index tensors stay as they are)."""
+        def move(t):
+            return t.to(device, dtype=dtype) if (dtype is not None and t.is_floating_point()) else t.to(device)
+        out = SimplicialBatch(**{k: move(getattr(self, k)) for k in self._names})
         for k in ("n_real_rows", "n_real_edges"):      # set by pad_batch
             if hasattr(self, k):
                 setattr(out, k, getattr(self, k))

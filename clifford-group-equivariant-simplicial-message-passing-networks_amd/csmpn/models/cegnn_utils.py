@@ -5,8 +5,11 @@ constructor signatures, attribute names, initialisers and state_dict keys.
 
 CEMLP.forward and EGCL.forward do not run their sub-modules: they hand the
 sub-modules' parameters to the fused HIP kernels through the C-ABI
-(csmpn_hip.ops). They require float32 GPU tensors and raise otherwise: there is
+(csmpn_hip.ops). They require GPU tensors and raise otherwise: there is
 no CPU path in this package (the CPU restatement is oracle/, test-only).
+float32 tensors take the float32 kernel families; after .double(), float64
+tensors take the float64 family (csrc/cemlp_f64.hpp: widths up to 64 channels,
+fixed summation order); mixed dtypes raise.
 
 The five small layers keep a standalone forward (none of the reference's models
 calls MVSiLU / NormalizationLayer / SteerableGeometricProductLayer / MVLayerNorm

@@ -36,10 +36,18 @@ from csmpn.models.cegnn_utils import CEMLP, EGCL, MVLinear
 def _fused_traj_readout(head, x) -> bool:
     """The trajectory heads go through csmpn_readout_traj_* on the device (CSMPN_NO_FUSED_READOUT=1: composed ops)."""
     import os
-    if not x.is_cuda or os.environ.get("CSMPN_NO_FUSED_READOUT", "0") not in ("", "0"):
+    if not x.is_cuda or x.dtype != torch.float32 or os.environ.get("CSMPN_NO_FUSED_READOUT", "0") not in ("", "0"):
         return False
     from csmpn_hip import ops
     return ops.readout_traj_supported(head, x)
+
+
+def _embed_grade(algebra, tensor, grade):
+    """algebra.embed_grade, for a float64 tensor in float64: the algebra allocates in the default dtype, as the reference
+    does, which would round a float64 batch under a float32 default. Every other tensor goes through it unchanged."""
+    if tensor.dtype == torch.float64:
+        return algebra._scatter_blades(tensor, algebra.grade_to_slice[grade], torch.float64)
+    return algebra.embed_grade(tensor, grade)
 
 
 def _zero_grad_of(head):
@@ -156,8 +164,11 @@ class SimplexEmbedding(nn.Module):
         n = self.algebra.dim
         D = 2 ** n
         dev = batch.x_ind.device
-        out = torch.zeros(batch.x_ind.shape[0], self.hidden_features, D, device=dev)
-        fused = dev.type == "cuda" and not any(t.requires_grad for t, _ in vertex_blocks)
+        dtype = vertex_blocks[0][0].dtype
+        out = torch.zeros(batch.x_ind.shape[0], self.hidden_features, D, device=dev, dtype=dtype)
+        # the fused glue kernels (csmpn_simplex_rows, csmpn_embed_cemlp_*) are float32 only: a float64 batch composes torch ops
+        # around the float64 CEMLP kernels
+        fused = dev.type == "cuda" and dtype == torch.float32 and not any(t.requires_grad for t, _ in vertex_blocks)
         # Fused embedding (round 3, csmpn_embed_cemlp_*): for d >= 1 the vertex features are gathered in every vertex order
         # inside the CEMLP kernel and the sum over the orders is taken there - neither the [n_d (d+1)!, (d+1) K, D] input
         # rows nor the per-order outputs exist in memory. Served for one feature block on the wide parity-lane shapes (the
@@ -169,7 +180,7 @@ class SimplexEmbedding(nn.Module):
             t0, g0 = vertex_blocks[0]
             if all(ops.embed_cemlp_supported(self.cl_feature_embedding[d].binding(), d + 1, t0.shape[1])
                    for d in range(1, self.max_dim + 1)):
-                emb_feat = self.algebra.embed_grade(t0, g0).contiguous()      # [S, K, D]: no vertex-order blow-up
+                emb_feat = _embed_grade(self.algebra, t0, g0).contiguous()      # [S, K, D]: no vertex-order blow-up
                 batch.lazy_table(plan, "verts_i32", _verts_i32_builder(plan, int(emb_feat.shape[0])))
         # (Tried in round 4 and dropped: the modules of the dimensions as parallel branches on side streams - forward and,
         # through autograd's stream rule, backward. Two long independent chains overlap in a replayed HIP graph (1 618 ->
@@ -197,7 +208,7 @@ class SimplexEmbedding(nn.Module):
             for t, grade in vertex_blocks:
                 g = t[pv]                                   # [rows, d+1, K, n_g]
                 g = g.reshape(g.shape[0], (d + 1) * t.shape[1], t.shape[2])
-                feats.append(self.algebra.embed_grade(g, grade))
+                feats.append(_embed_grade(self.algebra, g, grade))
             x = (feats[0] if len(feats) == 1 else torch.cat(feats, dim=1)).contiguous()
         e = self.cl_feature_embedding[d](x)
         return e.reshape(rows.shape[0], nperm, self.hidden_features, D).sum(dim=1) if nperm > 1 else e
@@ -205,7 +216,7 @@ class SimplexEmbedding(nn.Module):
 
 def type_attributes(algebra: CliffordAlgebra, type_features: torch.Tensor, edge_index: torch.Tensor):
     """node_attr = per-simplex type features as scalar-blade multivectors, edge_attr = (source, target)."""
-    node_attr = algebra.embed_grade(type_features.unsqueeze(-1), 0)
+    node_attr = _embed_grade(algebra, type_features.unsqueeze(-1), 0)
     # index_select, not node_attr[index]: the backward of advanced indexing sorts the index (11 launches, 155 us per md17
     # step); index_select's is one index_add_
     edge_attr = torch.cat((node_attr.index_select(0, edge_index[0]), node_attr.index_select(0, edge_index[1])), dim=1)
@@ -262,12 +273,12 @@ class HullsSimplicialMPNN(nn.Module):
         centred = (pos - pos.mean(dim=1, keepdim=True)).reshape(-1, n)
         inp = inp.index_copy(0, vr, centred)
         x = self._embed(batch, [(inp.unsqueeze(1), 1)])
-        types = torch.nn.functional.one_hot(batch.node_types, self.num_node_type).float()
+        types = torch.nn.functional.one_hot(batch.node_types, self.num_node_type).to(inp.dtype)
         node_attr, edge_attr = type_attributes(self.algebra, types, batch.edge_index)
         for layer in self.layers:
             x = layer(x, batch.edge_index, node_attr=node_attr, edge_attr=edge_attr)
         head = self.projection[0]
-        if x.is_cuda and len(self.projection) == 1 and head.out_features == 1 and head.weight.dim() == 3:
+        if x.is_cuda and x.dtype == torch.float32 and len(self.projection) == 1 and head.out_features == 1 and head.weight.dim() == 3:
             # fused readout + loss (csmpn_readout_mse_*): blade 0 of the projection, mean per graph, squared error
             from csmpn_hip import ops
             ptr_i32 = batch.lazy_table(plan, "ptr_i32", _ptr_i32_builder(batch))
@@ -434,7 +445,7 @@ class NBASimplicialMPNN(nn.Module):
             feats = []
             for t in (pos, vel):
                 g = t[pv]                                                # [rows * nperm, d + 1, F, 2]
-                feats.append(self.algebra.embed_grade(g.reshape(g.shape[0], (d + 1) * t.shape[1], t.shape[2]), 1))
+                feats.append(_embed_grade(self.algebra, g.reshape(g.shape[0], (d + 1) * t.shape[1], t.shape[2]), 1))
             e = self.cl_feature_embedding[d](torch.cat(feats, dim=1).contiguous())
             out = out.index_copy(0, rows, e.reshape(rows.shape[0], nperm, self.num_input, -1).sum(dim=1))
         return out

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("CSMPN_LIB") or os.path.join(_HERE, "libcsmpn_hip.so")
 
 ABI_VERSION = 2     # include/csmpn_hip.h: csmpn_abi_version()
 MAX_BLOCKS = 4
+F64_MAX_WIDTH = 64  # out_features limit of the float64 kernel family (csrc/cemlp_f64.hpp)
 FLAG_WEIGHTS_PACKED = 1
 FLAG_NO_VALIDATE = 2
 FLAG_DETERMINISTIC = 4
@@ -81,6 +82,14 @@ EXPORTS = (
     "csmpn_readout_mse_backward",
     "csmpn_readout_traj_forward",
     "csmpn_readout_traj_backward",
+    "csmpn_cemlp_f64_workspace_bytes",
+    "csmpn_cemlp_forward_f64",
+    "csmpn_cemlp_backward_f64",
+    "csmpn_egcl_edge_forward_f64",
+    "csmpn_egcl_edge_backward_f64",
+    "csmpn_egcl_node_forward_f64",
+    "csmpn_egcl_node_backward_f64",
+    "csmpn_segment_reduce_f64",
     "csmpn_last_error",
     "csmpn_last_kernel",
     "csmpn_abi_version",
@@ -199,6 +208,18 @@ def _load():
     sig("csmpn_readout_traj_forward", C.c_int, [C.c_int, vp, i32, vp, i64, vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp])
     sig("csmpn_readout_traj_backward", C.c_int,
         [C.c_int, vp, i32, i64, vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    # float64 family: csmpn_block_params_f64 / csmpn_block_grads_f64 have the layout of the float32 structs (the pointers are
+    # void* here), so BlockParams / BlockGrads serve both
+    sig("csmpn_cemlp_f64_workspace_bytes", sz, [C.c_int, bp, C.c_int, i64])
+    sig("csmpn_cemlp_forward_f64", C.c_int, [fp, C.c_int, bp, C.c_int, vp, i64, vp, vp, sz, vp])
+    sig("csmpn_cemlp_backward_f64", C.c_int, [fp, C.c_int, bp, bg, C.c_int, vp, vp, i64, vp, vp, sz, vp])
+    sig("csmpn_egcl_edge_forward_f64", C.c_int, [fp, C.c_int, bp, C.c_int, vp, i32, vp, i32, vp, vp, vp, i64, i64, vp, vp, sz, vp])
+    sig("csmpn_egcl_edge_backward_f64", C.c_int,
+        [fp, C.c_int, bp, bg, C.c_int, vp, i32, vp, i32, vp, vp, vp, i64, i64, vp, vp, vp, vp, sz, vp])
+    sig("csmpn_egcl_node_forward_f64", C.c_int, [fp, C.c_int, bp, C.c_int, vp, i32, vp, i32, vp, i32, vp, i32, i32, i64, vp, vp, sz, vp])
+    sig("csmpn_egcl_node_backward_f64", C.c_int,
+        [fp, C.c_int, bp, bg, C.c_int, vp, i32, vp, i32, vp, i32, vp, i32, i32, i64, vp, vp, vp, vp, vp, sz, vp])
+    sig("csmpn_segment_reduce_f64", C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, i32, vp])
     sig("csmpn_last_error", C.c_char_p, [])
     sig("csmpn_last_kernel", C.c_char_p, [])
     sig("csmpn_abi_version", C.c_int, [])

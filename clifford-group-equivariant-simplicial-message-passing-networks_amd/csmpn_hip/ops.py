@@ -41,14 +41,14 @@ def _on_device_of(arg_index):
     return deco
 
 
-def _require_device(t: torch.Tensor, what: str):
+def _require_device(t: torch.Tensor, what: str, dtype=torch.float32):
     if not t.is_cuda:
         raise RuntimeError(
             f"{what} is on {t.device}: the csmpn HIP path runs on MI355X only and has no CPU fallback "
             f"(the CPU restatement lives in oracle/ and is test infrastructure)."
         )
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{what} must be float32, got {t.dtype}")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{what} must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -162,7 +162,7 @@ class CemlpBinding:
                     total += (p.numel() + 3) // 4 * 4
             self._grad_layout = (offs, total)
 
-    def new_grads(self, params: Sequence[Optional[torch.Tensor]], device, flat=None, fused_into=None):
+    def new_grads(self, params: Sequence[Optional[torch.Tensor]], device, flat=None, fused_into=None, dtype=torch.float32):
         """One zeroed flat buffer for all parameter gradients (a single memset; or the caller's
         already zeroed `flat` of grad_floats() elements); returns (flat, views) with views[i]
         shaped like params[i]."""
@@ -177,8 +177,8 @@ class CemlpBinding:
                     setattr(g, name, None if p is None else p.grad.data_ptr())
             return None, [None] * len(params)
         if flat is None:
-            flat = torch.zeros(max(total, 1), dtype=torch.float32, device=device)
-        base = flat.data_ptr()
+            flat = torch.zeros(max(total, 1), dtype=dtype, device=device)
+        base, itemsize = flat.data_ptr(), flat.element_size()
         views = []
         for k in range(self.nblk):
             g = self.grads[k]
@@ -188,7 +188,7 @@ class CemlpBinding:
                     setattr(g, name, None)
                     views.append(None)
                 else:
-                    setattr(g, name, base + 4 * o[0])
+                    setattr(g, name, base + itemsize * o[0])
                     views.append(flat[o[0]:o[0] + o[1]].view(o[2]))
         return flat, views
 
@@ -251,7 +251,188 @@ class _CemlpFn(torch.autograd.Function):
         return (gx, None, *views)
 
 
+# ------------------------------------------------------------------------- float64 (csrc/cemlp_f64.hpp)
+# CEMLP and EGCL on float64 device tensors: autograd functions of their own over the csmpn_*_f64 entry points. The workspace
+# comes from the query per call, nothing is saved but the inputs (the backward recomputes), the sums run in a fixed order:
+# bit-reproducible whatever set_deterministic says. Out of scope here: fused gradient accumulation, the captured step.
+
+
+def _on_device_like(x, others):
+    """Every attribute tensor on the device of the input: the check and the message of the float32 path (_require_device),
+    in front of any launch - a host pointer must never reach a kernel."""
+    for name, t in others:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(
+                f"{name} is on {t.device}: the csmpn HIP path runs on MI355X only and has no CPU fallback "
+                f"(the CPU restatement lives in oracle/ and is test infrastructure).")
+        if t.device != x.device:
+            raise RuntimeError(f"{name} is on {t.device}, the input on {x.device}: one device per call")
+
+
+def _same_dtype(x, others, what):
+    """One dtype for the input, every parameter and the attributes of a fused module (no launch otherwise)."""
+    for name, t in others:
+        if t is not None and t.dtype != x.dtype:
+            raise RuntimeError(f"{what}: mixed dtypes - the input is {x.dtype}, {name} is {t.dtype} (cast the module with "
+                               f".double() / .float() or the tensors to match)")
+
+
+def _f64_check(binding: CemlpBinding):
+    for k in range(binding.nblk):
+        if binding.params[k].out_features > native.F64_MAX_WIDTH:
+            raise native.CsmpnError(f"float64 CEMLP / EGCL: out_features {binding.params[k].out_features} of block {k} is above "
+                                    f"the limit of {native.F64_MAX_WIDTH} channels of the float64 kernels")
+
+
+def _f64_ws(binding: CemlpBinding, rows: int, device) -> torch.Tensor:
+    nbytes = int(native.lib().csmpn_cemlp_f64_workspace_bytes(binding.n, binding.params, binding.nblk, rows))
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+def segment_reduce_f64(rows, out, add=None, sub=None, accumulate=True):
+    """segment_reduce on float64 tables."""
+    ap, ao = add if add is not None else (None, None)
+    sp, so = sub if sub is not None else (None, None)
+    check(native.lib().csmpn_segment_reduce_f64(rows.data_ptr(), rows[0].numel(), out.shape[0], _ptr(ap), _ptr(ao), _ptr(sp),
+                                                _ptr(so), out.data_ptr(), 1 if accumulate else 0, _stream(out.device)))
+    return out
+
+
+class _CemlpF64Fn(torch.autograd.Function):
+    @staticmethod
+    @_on_device_of(1)
+    def forward(ctx, x, binding: CemlpBinding, *params):
+        _require_device(x, "CEMLP input", torch.float64)
+        _on_device_like(x, [(f"parameter {j}", p) for j, p in enumerate(params)])
+        if x.dim() != 3 or x.shape[1] != binding.in_features or x.shape[2] != binding.D:
+            raise RuntimeError(f"CEMLP input must be [rows, {binding.in_features}, {binding.D}], got {tuple(x.shape)}")
+        _f64_check(binding)
+        x = x.contiguous()
+        binding.bind(params)
+        rows = x.shape[0]
+        y = torch.empty(rows, binding.out_features, binding.D, dtype=torch.float64, device=x.device)
+        ws = _f64_ws(binding, rows, x.device)
+        check(native.lib().csmpn_cemlp_forward_f64(binding.metric_arr, binding.n, binding.params, binding.nblk, x.data_ptr(), rows,
+                                                   y.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x.device)))
+        ctx.binding = binding
+        ctx.save_for_backward(x, *[p for p in params if p is not None])
+        ctx.mask = [p is not None for p in params]
+        return y
+
+    @staticmethod
+    @_on_device_of(1)
+    def backward(ctx, gy):
+        binding = ctx.binding
+        x, *present = ctx.saved_tensors
+        it = iter(present)
+        params = [next(it) if m else None for m in ctx.mask]
+        gy = gy.contiguous()
+        binding.bind(params)
+        _flat, views = binding.new_grads(params, x.device, dtype=torch.float64)
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        ws = _f64_ws(binding, x.shape[0], x.device)
+        check(native.lib().csmpn_cemlp_backward_f64(binding.metric_arr, binding.n, binding.params, binding.grads, binding.nblk,
+                                                    x.data_ptr(), gy.data_ptr(), x.shape[0], _ptr(gx), ws.data_ptr(), ws.numel(),
+                                                    _stream(x.device)))
+        return (gx, None, *views)
+
+
+class _EgclF64Fn(torch.autograd.Function):
+    """The deterministic call sequence of HipBackend on the float64 entry points: edge rows -> fixed-order segment sum ->
+    node stage; backward: node stage, edge rows, segment sum (+ by target, - by source order)."""
+
+    @staticmethod
+    @_on_device_of(1)
+    def forward(ctx, h, edge_attr, node_attr, spec: EgclSpec, csr: Csr, *params):
+        _require_device(h, "EGCL input h", torch.float64)
+        _on_device_like(h, [("edge_attr", edge_attr), ("node_attr", node_attr)]
+                        + [(f"parameter {j}", p) for j, p in enumerate(params)])
+        _check_egcl_inputs(spec, csr, h, edge_attr, node_attr, csr.n_edges)
+        if not isinstance(csr, Csr):
+            raise native.CsmpnError("float64 EGCL needs the whole adjacency (no sliced launches)")
+        e, nd = spec.edge, spec.node
+        _f64_check(e)
+        _f64_check(nd)
+        h = h.contiguous()
+        edge_attr = edge_attr.contiguous() if edge_attr is not None else None
+        node_attr = node_attr.contiguous() if node_attr is not None else None
+        ne = e.nblk * NP
+        pe, pn = params[:ne], params[ne:]
+        e.bind(pe)
+        nd.bind(pn)
+        N, E, D, dev, lib = h.shape[0], csr.n_edges, e.D, h.device, native.lib()
+        f64 = dict(dtype=torch.float64, device=dev)
+        agg = torch.zeros(N, spec.O, D, **f64)
+        if E > 0:
+            rows = torch.empty(E, spec.O, D, **f64)
+            ws = _f64_ws(e, E, dev)
+            check(lib.csmpn_egcl_edge_forward_f64(e.metric_arr, e.n, e.params, e.nblk, h.data_ptr(), spec.C, _ptr(edge_attr), spec.A,
+                                                  csr.perm.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), E, N, rows.data_ptr(),
+                                                  ws.data_ptr(), ws.numel(), _stream(dev)))
+            segment_reduce_f64(rows, agg, add=(csr.row_ptr, None), accumulate=False)
+        out = torch.empty(N, nd.out_features, D, **f64)
+        ws = _f64_ws(nd, N, dev)
+        check(lib.csmpn_egcl_node_forward_f64(nd.metric_arr, nd.n, nd.params, nd.nblk, h.data_ptr(), spec.C, agg.data_ptr(), spec.O,
+                                              _ptr(node_attr), spec.T, csr.deg.data_ptr(), spec.mean, spec.residual, N, out.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _stream(dev)))
+        ctx.spec, ctx.csr = spec, csr
+        ctx.has_ea, ctx.has_na = edge_attr is not None, node_attr is not None
+        ctx.mask = [p is not None for p in params]
+        saved = [h, agg] + ([edge_attr] if ctx.has_ea else []) + ([node_attr] if ctx.has_na else [])
+        ctx.save_for_backward(*saved, *[p for p in params if p is not None])
+        return out
+
+    @staticmethod
+    @_on_device_of(1)
+    def backward(ctx, gout):
+        spec, csr = ctx.spec, ctx.csr
+        saved = list(ctx.saved_tensors)
+        h, agg = saved[0], saved[1]
+        pos = 2
+        edge_attr = node_attr = None
+        if ctx.has_ea:
+            edge_attr = saved[pos]; pos += 1
+        if ctx.has_na:
+            node_attr = saved[pos]; pos += 1
+        it = iter(saved[pos:])
+        params = [next(it) if m else None for m in ctx.mask]
+        e, nd = spec.edge, spec.node
+        ne = e.nblk * NP
+        pe, pn = params[:ne], params[ne:]
+        e.bind(pe)
+        nd.bind(pn)
+        gout = gout.contiguous()
+        N, E, D, dev, lib = h.shape[0], csr.n_edges, e.D, h.device, native.lib()
+        f64 = dict(dtype=torch.float64, device=dev)
+        _fn, views_n = nd.new_grads(pn, dev, dtype=torch.float64)
+        gh = torch.empty_like(h)
+        g_agg = torch.empty(N, spec.O, D, **f64)
+        g_na = torch.empty_like(node_attr) if (node_attr is not None and ctx.needs_input_grad[2]) else None
+        ws = _f64_ws(nd, N, dev)
+        check(lib.csmpn_egcl_node_backward_f64(nd.metric_arr, nd.n, nd.params, nd.grads, nd.nblk, h.data_ptr(), spec.C, agg.data_ptr(),
+                                               spec.O, _ptr(node_attr), spec.T, csr.deg.data_ptr(), spec.mean, spec.residual, N,
+                                               gout.data_ptr(), gh.data_ptr(), g_agg.data_ptr(), _ptr(g_na), ws.data_ptr(), ws.numel(),
+                                               _stream(dev)))
+        _fe, views_e = e.new_grads(pe, dev, dtype=torch.float64)
+        g_ea = torch.empty_like(edge_attr) if (edge_attr is not None and ctx.needs_input_grad[1]) else None
+        if E > 0:
+            rows = torch.empty(E, spec.C, D, **f64)
+            ws = _f64_ws(e, E, dev)
+            check(lib.csmpn_egcl_edge_backward_f64(e.metric_arr, e.n, e.params, e.grads, e.nblk, h.data_ptr(), spec.C, _ptr(edge_attr),
+                                                   spec.A, csr.perm.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), E, N,
+                                                   g_agg.data_ptr(), rows.data_ptr(), _ptr(g_ea), ws.data_ptr(), ws.numel(),
+                                                   _stream(dev)))
+            segment_reduce_f64(rows, gh, add=(csr.row_ptr, None), sub=csr.source_order())
+        return (gh, g_ea, g_na, None, None, *views_e, *views_n)
+
+
 def cemlp_apply(x, binding: CemlpBinding, params):
+    if x.is_cuda:   # (a CPU tensor: _CemlpFn raises "no CPU fallback", first of all)
+        _same_dtype(x, ((f"parameter {PARAM_FIELDS[j % NP]} of block {j // NP}", p) for j, p in enumerate(params)), "CEMLP")
+        if x.dtype == torch.float64:
+            return _CemlpF64Fn.apply(x, binding, *params)
     return _CemlpFn.apply(x, binding, *params)
 
 
@@ -823,6 +1004,17 @@ class _EgclFn(torch.autograd.Function):
 
 
 def egcl_apply(h, edge_attr, node_attr, spec: EgclSpec, csr: Csr, params):
+    if h.is_cuda:   # (a CPU tensor: _EgclFn raises "no CPU fallback", first of all)
+        ne = spec.edge.nblk * NP
+        if h.dtype == torch.float64:
+            _on_device_like(h, (("edge_attr", edge_attr), ("node_attr", node_attr)))
+        _same_dtype(h, (("edge_attr", edge_attr), ("node_attr", node_attr)), "EGCL")
+        _same_dtype(h, ((f"parameter {PARAM_FIELDS[j % NP]} of block {j // NP} of the edge model", p) for j, p in enumerate(params[:ne])),
+                    "EGCL")
+        _same_dtype(h, ((f"parameter {PARAM_FIELDS[j % NP]} of block {j // NP} of the node model", p) for j, p in enumerate(params[ne:])),
+                    "EGCL")
+        if h.dtype == torch.float64:
+            return _EgclF64Fn.apply(h, edge_attr, node_attr, spec, csr, *params)
     return _EgclFn.apply(h, edge_attr, node_attr, spec, csr, *params)
 
 

@@ -664,6 +664,100 @@ int csmpn_readout_mse_forward(int n, const float* x, const float* weight, int32_
 int csmpn_readout_mse_backward(int n, const float* weight, int32_t weight_stride, int64_t n_rows, int32_t channels,
                                const int32_t* graph_ptr, int64_t n_graphs, const float* coef, float* gx, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------- float64
+ * CEMLP and the EGCL stages on contiguous float64 device tensors (parameters, attributes and gradients float64 too; the
+ * metric stays a host array of floats, the index tables int32): one kernel family of its own (csrc/cemlp_f64.hpp,
+ * "f64" in the CSMPN_DEBUG dispatch log), built for correctness and a fixed summation order. The arithmetic is that of
+ * the C++ twin (oracle/cpu_twin/csmpn_cpu.cpp) in double, with the reference's float64 constants 1e-16 and 1e-6.
+ * Bit-reproducible: no float atomic on any output or gradient - tiles map to workgroups statically, every workgroup
+ * adds its parameter gradients into its own slice of the workspace, a second launch adds the slices in ascending order
+ * INTO the gradient tensors (+=), and the edge stage writes row tables in sorted edge order which the fixed-order segment
+ * sum below turns into agg / gh (the call sequence of CSMPN_FLAG_DETERMINISTIC). No flags, no saved buffers: the backward
+ * recomputes the forward from its inputs.
+ * Limits: the six compiled algebras (the check of csmpn_metric_supported, else CSMPN_ERR_UNSUPPORTED), 1..CSMPN_MAX_BLOCKS
+ * blocks, out_features of every block 1..64 (one row of a block must fit the LDS; above: CSMPN_ERR_UNSUPPORTED),
+ * in_features unbounded (input rows are streamed).
+ * Workspace: with D = 2^n, G = n + 1, P grade paths, per block s_k = O I (G | 1) + 3 O + 3 O G + O P + 2 O O G doubles of
+ * gradient slice, maxO the widest out_features, maxW the widest in_ or out_features, r = 8 (7 maxO D + 5 maxO G + 3 maxO + 2)
+ * bytes of LDS per row: tile rows R = min(32, 65536 / r), or 163840 / r where that is 0; tiles = ceil(rows / R);
+ * grid = min(tiles, 512), or min(tiles, 256) where R r > 65536;
+ *   bytes = 8 grid (sum_k s_k + R D sum_k I_k + 2 R D maxW)
+ * (0 for rows = 0 and for arguments the entry points reject). Needs no initialisation.
+ * Argument checks (all in front of the first HIP call - a rejected call launches nothing and writes nothing): null
+ * pointers, block count, chained widths, a workspace smaller than the query, negative rows / n_edges / n_nodes:
+ * CSMPN_ERR_INVALID; n or the metric not compiled, a width above 64: CSMPN_ERR_UNSUPPORTED. Data pointers may be null where
+ * the row count is 0. Every entry point is capturable (no allocation, no host synchronisation). */
+typedef struct csmpn_block_params_f64 {
+    int32_t in_features;
+    int32_t out_features;
+    int32_t lin_subspaces;
+    int32_t reserved;
+    const double* lin_w;
+    const double* lin_b;     /* or NULL */
+    const double* silu_a;
+    const double* silu_b;
+    const double* gp_w;
+    const double* norm_a;
+    const double* right_w;
+    const double* left_w;
+    const double* left_b;
+    const double* ln_a;
+} csmpn_block_params_f64;
+
+typedef struct csmpn_block_grads_f64 {   /* any pointer may be NULL: that gradient is not wanted */
+    double* lin_w;
+    double* lin_b;
+    double* silu_a;
+    double* silu_b;
+    double* gp_w;
+    double* norm_a;
+    double* right_w;
+    double* left_w;
+    double* left_b;
+    double* ln_a;
+} csmpn_block_grads_f64;
+
+size_t csmpn_cemlp_f64_workspace_bytes(int n, const csmpn_block_params_f64* blocks, int n_blocks, int64_t rows);
+
+/* y [rows, O, D] = CEMLP of x [rows, I, D]; backward: gx (or NULL) and the parameter gradients (+=) from x and gy. */
+int csmpn_cemlp_forward_f64(const float* metric_host, int n, const csmpn_block_params_f64* blocks, int n_blocks, const double* x,
+                            int64_t rows, double* y, void* workspace, size_t workspace_bytes, void* stream);
+int csmpn_cemlp_backward_f64(const float* metric_host, int n, const csmpn_block_params_f64* blocks,
+                             const csmpn_block_grads_f64* grads, int n_blocks, const double* x, const double* gy, int64_t rows,
+                             double* gx, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Edge stage, workspace for n_edges rows. Forward: msg_rows [E, O, D], row e = the message of sorted edge e (sum it over
+ * row_ptr with the segment sum below to get agg). Backward: g_edge_rows [E, C, D], row e = d/d(h_i - h_j) of sorted edge e
+ * (gh += segment sum: + by target over row_ptr, - by source order), g_edge_attr [E, A, D] in ORIGINAL edge order or NULL. */
+int csmpn_egcl_edge_forward_f64(const float* metric_host, int n, const csmpn_block_params_f64* blocks, int n_blocks,
+                                const double* h, int32_t channels, const double* edge_attr, int32_t attr_channels,
+                                const int32_t* perm, const int32_t* src_sorted, const int32_t* dst_sorted, int64_t n_edges,
+                                int64_t n_nodes, double* msg_rows, void* workspace, size_t workspace_bytes, void* stream);
+int csmpn_egcl_edge_backward_f64(const float* metric_host, int n, const csmpn_block_params_f64* blocks,
+                                 const csmpn_block_grads_f64* grads, int n_blocks, const double* h, int32_t channels,
+                                 const double* edge_attr, int32_t attr_channels, const int32_t* perm, const int32_t* src_sorted,
+                                 const int32_t* dst_sorted, int64_t n_edges, int64_t n_nodes, const double* g_agg,
+                                 double* g_edge_rows, double* g_edge_attr, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Node stage, workspace for n_nodes rows; semantics of the float32 stage: input (h, agg / max(in_degree, 1) under
+ * mean_aggr, node_attr), out = CEMLP (+ h under residual). Backward: gh = d/dh of the node model (+ g_out under residual),
+ * g_agg (mean scale applied), g_node_attr or NULL. */
+int csmpn_egcl_node_forward_f64(const float* metric_host, int n, const csmpn_block_params_f64* blocks, int n_blocks,
+                                const double* h, int32_t channels, const double* agg, int32_t agg_channels,
+                                const double* node_attr, int32_t attr_channels, const int32_t* in_degree, int32_t mean_aggr,
+                                int32_t residual, int64_t n_nodes, double* out, void* workspace, size_t workspace_bytes, void* stream);
+int csmpn_egcl_node_backward_f64(const float* metric_host, int n, const csmpn_block_params_f64* blocks,
+                                 const csmpn_block_grads_f64* grads, int n_blocks, const double* h, int32_t channels,
+                                 const double* agg, int32_t agg_channels, const double* node_attr, int32_t attr_channels,
+                                 const int32_t* in_degree, int32_t mean_aggr, int32_t residual, int64_t n_nodes,
+                                 const double* g_out, double* gh, double* g_agg, double* g_node_attr, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
+/* The contract of csmpn_segment_reduce on doubles (no alignment requirement; row_doubles >= 1). */
+int csmpn_segment_reduce_f64(const double* rows, int64_t row_doubles, int64_t n_nodes, const int32_t* add_ptr,
+                             const int32_t* add_order, const int32_t* sub_ptr, const int32_t* sub_order, double* out,
+                             int32_t accumulate, void* stream);
+
 /* Last error message of the calling thread (never NULL). */
 const char* csmpn_last_error(void);
 
