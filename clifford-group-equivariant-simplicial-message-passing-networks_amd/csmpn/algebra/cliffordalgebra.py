@@ -51,6 +51,10 @@ class CliffordAlgebra(nn.Module):
         diag = torch.from_numpy(tables["cayley"])[torch.arange(self.n_blades), 0, torch.arange(self.n_blades)]
         self._qsign_host = (beta * diag).to(dflt)   # beta_d * cayley[d, 0, d]
         self.hip_supported = bool(native.lib().csmpn_metric_supported(native.metric_array(self.metric_tuple), self.dim))
+        # every signature of +1 / -1 entries on 2..5 generators: CEMLP and EGCL run on the device (the run-time-signature
+        # kernels where the algebra is not one of the six compiled ones); hip_supported stays the six, which the geometric
+        # product and the small layers need
+        self.hip_signature = bool(native.lib().csmpn_signature_supported(native.metric_array(self.metric_tuple), self.dim))
 
     # ------------------------------------------------------------------ products
     def geometric_product(self, a, b, blades=None):

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("CSMPN_LIB") or os.path.join(_HERE, "libcsmpn_hip.so")
 
 ABI_VERSION = 2     # include/csmpn_hip.h: csmpn_abi_version()
 MAX_BLOCKS = 4
-F64_MAX_WIDTH = 64  # out_features limit of the float64 kernel family (csrc/cemlp_f64.hpp)
+F64_MAX_WIDTH = 64  # out_features limit of the float64 and run-time-signature kernel families (csrc/cemlp_f64.hpp, cemlp_sig.hpp)
 FLAG_WEIGHTS_PACKED = 1
 FLAG_NO_VALIDATE = 2
 FLAG_DETERMINISTIC = 4
@@ -90,6 +90,14 @@ EXPORTS = (
     "csmpn_egcl_node_forward_f64",
     "csmpn_egcl_node_backward_f64",
     "csmpn_segment_reduce_f64",
+    "csmpn_signature_supported",
+    "csmpn_cemlp_sig_workspace_bytes",
+    "csmpn_cemlp_forward_sig",
+    "csmpn_cemlp_backward_sig",
+    "csmpn_egcl_edge_forward_sig",
+    "csmpn_egcl_edge_backward_sig",
+    "csmpn_egcl_node_forward_sig",
+    "csmpn_egcl_node_backward_sig",
     "csmpn_last_error",
     "csmpn_last_kernel",
     "csmpn_abi_version",
@@ -220,6 +228,17 @@ def _load():
     sig("csmpn_egcl_node_backward_f64", C.c_int,
         [fp, C.c_int, bp, bg, C.c_int, vp, i32, vp, i32, vp, i32, vp, i32, i32, i64, vp, vp, vp, vp, vp, sz, vp])
     sig("csmpn_segment_reduce_f64", C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, i32, vp])
+    # run-time-signature family (csrc/cemlp_sig.hpp), float32: the argument lists of the _f64 siblings
+    sig("csmpn_signature_supported", C.c_int, [fp, C.c_int])
+    sig("csmpn_cemlp_sig_workspace_bytes", sz, [C.c_int, bp, C.c_int, i64])
+    sig("csmpn_cemlp_forward_sig", C.c_int, [fp, C.c_int, bp, C.c_int, vp, i64, vp, vp, sz, vp])
+    sig("csmpn_cemlp_backward_sig", C.c_int, [fp, C.c_int, bp, bg, C.c_int, vp, vp, i64, vp, vp, sz, vp])
+    sig("csmpn_egcl_edge_forward_sig", C.c_int, [fp, C.c_int, bp, C.c_int, vp, i32, vp, i32, vp, vp, vp, i64, i64, vp, vp, sz, vp])
+    sig("csmpn_egcl_edge_backward_sig", C.c_int,
+        [fp, C.c_int, bp, bg, C.c_int, vp, i32, vp, i32, vp, vp, vp, i64, i64, vp, vp, vp, vp, sz, vp])
+    sig("csmpn_egcl_node_forward_sig", C.c_int, [fp, C.c_int, bp, C.c_int, vp, i32, vp, i32, vp, i32, vp, i32, i32, i64, vp, vp, sz, vp])
+    sig("csmpn_egcl_node_backward_sig", C.c_int,
+        [fp, C.c_int, bp, bg, C.c_int, vp, i32, vp, i32, vp, i32, vp, i32, i32, i64, vp, vp, vp, vp, vp, sz, vp])
     sig("csmpn_last_error", C.c_char_p, [])
     sig("csmpn_last_kernel", C.c_char_p, [])
     sig("csmpn_abi_version", C.c_int, [])

@@ -110,9 +110,17 @@ class CemlpBinding:
         self._grad_layout = None
         self._ws_bytes = None
         self._saved_per_row = None
+        self._sig_only = None
 
     def supported(self) -> bool:
         return bool(native.lib().csmpn_metric_supported(self.metric_arr, self.n))
+
+    def sig_only(self) -> bool:
+        """A signature the device serves through the run-time-signature kernels alone: not one of the six compiled algebras,
+        but n in 2..5 and every entry +1 or -1 (csmpn_signature_supported)."""
+        if self._sig_only is None:
+            self._sig_only = (not self.supported()) and bool(native.lib().csmpn_signature_supported(self.metric_arr, self.n))
+        return self._sig_only
 
     def bind(self, params: Sequence[Optional[torch.Tensor]]):
         assert len(params) == NP * self.nblk
@@ -251,8 +259,9 @@ class _CemlpFn(torch.autograd.Function):
         return (gx, None, *views)
 
 
-# ------------------------------------------------------------------------- float64 (csrc/cemlp_f64.hpp)
-# CEMLP and EGCL on float64 device tensors: autograd functions of their own over the csmpn_*_f64 entry points. The workspace
+# ---------------------------------------------- float64 (csrc/cemlp_f64.hpp) and run-time signature (csrc/cemlp_sig.hpp)
+# CEMLP and EGCL on float64 device tensors, and on float32 device tensors of a signature that is not one of the six compiled
+# algebras: autograd functions of their own over the csmpn_*_f64 / csmpn_*_sig entry points (_RowFamily). The workspace
 # comes from the query per call, nothing is saved but the inputs (the backward recomputes), the sums run in a fixed order:
 # bit-reproducible whatever set_deterministic says. Out of scope here: fused gradient accumulation, the captured step.
 
@@ -279,16 +288,42 @@ def _same_dtype(x, others, what):
                                f".double() / .float() or the tensors to match)")
 
 
-def _f64_check(binding: CemlpBinding):
-    for k in range(binding.nblk):
-        if binding.params[k].out_features > native.F64_MAX_WIDTH:
-            raise native.CsmpnError(f"float64 CEMLP / EGCL: out_features {binding.params[k].out_features} of block {k} is above "
-                                    f"the limit of {native.F64_MAX_WIDTH} channels of the float64 kernels")
+class _RowFamily:
+    """The entry points of one dtype that _CemlpF64Fn / _EgclF64Fn call: float64 -> csmpn_*_f64 (csrc/cemlp_f64.hpp, and
+    cemlp_sig.hpp behind them for the signatures that are not compiled), float32 -> csmpn_*_sig (csrc/cemlp_sig.hpp). Same
+    argument lists, same call sequence, same contracts."""
+
+    def __init__(self, dtype, suffix, ws_query, what, kernels):
+        self.dtype, self.suffix, self.ws_query, self.what, self.kernels = dtype, suffix, ws_query, what, kernels
+
+    def fn(self, stem):
+        return getattr(native.lib(), stem + self.suffix)
+
+    def check_widths(self, binding: CemlpBinding):
+        for k in range(binding.nblk):
+            if binding.params[k].out_features > native.F64_MAX_WIDTH:
+                raise native.CsmpnError(f"{self.what} CEMLP / EGCL: out_features {binding.params[k].out_features} of block {k} is above "
+                                        f"the limit of {native.F64_MAX_WIDTH} channels of the {self.kernels} kernels")
+
+    def ws(self, binding: CemlpBinding, rows: int, device) -> torch.Tensor:
+        nbytes = int(getattr(native.lib(), self.ws_query)(binding.n, binding.params, binding.nblk, rows))
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+    def segment_reduce(self, rows, out, add=None, sub=None, accumulate=True):
+        return (segment_reduce_f64 if self.dtype == torch.float64 else segment_reduce)(rows, out, add, sub, accumulate)
 
 
-def _f64_ws(binding: CemlpBinding, rows: int, device) -> torch.Tensor:
-    nbytes = int(native.lib().csmpn_cemlp_f64_workspace_bytes(binding.n, binding.params, binding.nblk, rows))
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+_FAMILY = {torch.float64: _RowFamily(torch.float64, "_f64", "csmpn_cemlp_f64_workspace_bytes", "float64", "float64"),
+           torch.float32: _RowFamily(torch.float32, "_sig", "csmpn_cemlp_sig_workspace_bytes", "run-time-signature",
+                                     "run-time-signature")}
+
+
+def _family_of(t: torch.Tensor, what: str) -> _RowFamily:
+    if not t.is_cuda:
+        _require_device(t, what)
+    if t.dtype not in _FAMILY:
+        raise RuntimeError(f"{what} must be float32 or float64, got {t.dtype}")
+    return _FAMILY[t.dtype]
 
 
 def segment_reduce_f64(rows, out, add=None, sub=None, accumulate=True):
@@ -304,17 +339,17 @@ class _CemlpF64Fn(torch.autograd.Function):
     @staticmethod
     @_on_device_of(1)
     def forward(ctx, x, binding: CemlpBinding, *params):
-        _require_device(x, "CEMLP input", torch.float64)
+        fam = _family_of(x, "CEMLP input")
         _on_device_like(x, [(f"parameter {j}", p) for j, p in enumerate(params)])
         if x.dim() != 3 or x.shape[1] != binding.in_features or x.shape[2] != binding.D:
             raise RuntimeError(f"CEMLP input must be [rows, {binding.in_features}, {binding.D}], got {tuple(x.shape)}")
-        _f64_check(binding)
+        fam.check_widths(binding)
         x = x.contiguous()
         binding.bind(params)
         rows = x.shape[0]
-        y = torch.empty(rows, binding.out_features, binding.D, dtype=torch.float64, device=x.device)
-        ws = _f64_ws(binding, rows, x.device)
-        check(native.lib().csmpn_cemlp_forward_f64(binding.metric_arr, binding.n, binding.params, binding.nblk, x.data_ptr(), rows,
+        y = torch.empty(rows, binding.out_features, binding.D, dtype=fam.dtype, device=x.device)
+        ws = fam.ws(binding, rows, x.device)
+        check(fam.fn("csmpn_cemlp_forward")(binding.metric_arr, binding.n, binding.params, binding.nblk, x.data_ptr(), rows,
                                                    y.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x.device)))
         ctx.binding = binding
         ctx.save_for_backward(x, *[p for p in params if p is not None])
@@ -326,14 +361,15 @@ class _CemlpF64Fn(torch.autograd.Function):
     def backward(ctx, gy):
         binding = ctx.binding
         x, *present = ctx.saved_tensors
+        fam = _FAMILY[x.dtype]
         it = iter(present)
         params = [next(it) if m else None for m in ctx.mask]
         gy = gy.contiguous()
         binding.bind(params)
-        _flat, views = binding.new_grads(params, x.device, dtype=torch.float64)
+        _flat, views = binding.new_grads(params, x.device, dtype=fam.dtype)
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        ws = _f64_ws(binding, x.shape[0], x.device)
-        check(native.lib().csmpn_cemlp_backward_f64(binding.metric_arr, binding.n, binding.params, binding.grads, binding.nblk,
+        ws = fam.ws(binding, x.shape[0], x.device)
+        check(fam.fn("csmpn_cemlp_backward")(binding.metric_arr, binding.n, binding.params, binding.grads, binding.nblk,
                                                     x.data_ptr(), gy.data_ptr(), x.shape[0], _ptr(gx), ws.data_ptr(), ws.numel(),
                                                     _stream(x.device)))
         return (gx, None, *views)
@@ -346,15 +382,15 @@ class _EgclF64Fn(torch.autograd.Function):
     @staticmethod
     @_on_device_of(1)
     def forward(ctx, h, edge_attr, node_attr, spec: EgclSpec, csr: Csr, *params):
-        _require_device(h, "EGCL input h", torch.float64)
+        fam = _family_of(h, "EGCL input h")
         _on_device_like(h, [("edge_attr", edge_attr), ("node_attr", node_attr)]
                         + [(f"parameter {j}", p) for j, p in enumerate(params)])
         _check_egcl_inputs(spec, csr, h, edge_attr, node_attr, csr.n_edges)
         if not isinstance(csr, Csr):
-            raise native.CsmpnError("float64 EGCL needs the whole adjacency (no sliced launches)")
+            raise native.CsmpnError(f"{fam.what} EGCL needs the whole adjacency (no sliced launches)")
         e, nd = spec.edge, spec.node
-        _f64_check(e)
-        _f64_check(nd)
+        fam.check_widths(e)
+        fam.check_widths(nd)
         h = h.contiguous()
         edge_attr = edge_attr.contiguous() if edge_attr is not None else None
         node_attr = node_attr.contiguous() if node_attr is not None else None
@@ -363,18 +399,18 @@ class _EgclF64Fn(torch.autograd.Function):
         e.bind(pe)
         nd.bind(pn)
         N, E, D, dev, lib = h.shape[0], csr.n_edges, e.D, h.device, native.lib()
-        f64 = dict(dtype=torch.float64, device=dev)
+        f64 = dict(dtype=fam.dtype, device=dev)
         agg = torch.zeros(N, spec.O, D, **f64)
         if E > 0:
             rows = torch.empty(E, spec.O, D, **f64)
-            ws = _f64_ws(e, E, dev)
-            check(lib.csmpn_egcl_edge_forward_f64(e.metric_arr, e.n, e.params, e.nblk, h.data_ptr(), spec.C, _ptr(edge_attr), spec.A,
+            ws = fam.ws(e, E, dev)
+            check(fam.fn("csmpn_egcl_edge_forward")(e.metric_arr, e.n, e.params, e.nblk, h.data_ptr(), spec.C, _ptr(edge_attr), spec.A,
                                                   csr.perm.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), E, N, rows.data_ptr(),
                                                   ws.data_ptr(), ws.numel(), _stream(dev)))
-            segment_reduce_f64(rows, agg, add=(csr.row_ptr, None), accumulate=False)
+            fam.segment_reduce(rows, agg, add=(csr.row_ptr, None), accumulate=False)
         out = torch.empty(N, nd.out_features, D, **f64)
-        ws = _f64_ws(nd, N, dev)
-        check(lib.csmpn_egcl_node_forward_f64(nd.metric_arr, nd.n, nd.params, nd.nblk, h.data_ptr(), spec.C, agg.data_ptr(), spec.O,
+        ws = fam.ws(nd, N, dev)
+        check(fam.fn("csmpn_egcl_node_forward")(nd.metric_arr, nd.n, nd.params, nd.nblk, h.data_ptr(), spec.C, agg.data_ptr(), spec.O,
                                               _ptr(node_attr), spec.T, csr.deg.data_ptr(), spec.mean, spec.residual, N, out.data_ptr(),
                                               ws.data_ptr(), ws.numel(), _stream(dev)))
         ctx.spec, ctx.csr = spec, csr
@@ -390,6 +426,7 @@ class _EgclF64Fn(torch.autograd.Function):
         spec, csr = ctx.spec, ctx.csr
         saved = list(ctx.saved_tensors)
         h, agg = saved[0], saved[1]
+        fam = _FAMILY[h.dtype]
         pos = 2
         edge_attr = node_attr = None
         if ctx.has_ea:
@@ -405,33 +442,33 @@ class _EgclF64Fn(torch.autograd.Function):
         nd.bind(pn)
         gout = gout.contiguous()
         N, E, D, dev, lib = h.shape[0], csr.n_edges, e.D, h.device, native.lib()
-        f64 = dict(dtype=torch.float64, device=dev)
-        _fn, views_n = nd.new_grads(pn, dev, dtype=torch.float64)
+        f64 = dict(dtype=fam.dtype, device=dev)
+        _fn, views_n = nd.new_grads(pn, dev, dtype=fam.dtype)
         gh = torch.empty_like(h)
         g_agg = torch.empty(N, spec.O, D, **f64)
         g_na = torch.empty_like(node_attr) if (node_attr is not None and ctx.needs_input_grad[2]) else None
-        ws = _f64_ws(nd, N, dev)
-        check(lib.csmpn_egcl_node_backward_f64(nd.metric_arr, nd.n, nd.params, nd.grads, nd.nblk, h.data_ptr(), spec.C, agg.data_ptr(),
+        ws = fam.ws(nd, N, dev)
+        check(fam.fn("csmpn_egcl_node_backward")(nd.metric_arr, nd.n, nd.params, nd.grads, nd.nblk, h.data_ptr(), spec.C, agg.data_ptr(),
                                                spec.O, _ptr(node_attr), spec.T, csr.deg.data_ptr(), spec.mean, spec.residual, N,
                                                gout.data_ptr(), gh.data_ptr(), g_agg.data_ptr(), _ptr(g_na), ws.data_ptr(), ws.numel(),
                                                _stream(dev)))
-        _fe, views_e = e.new_grads(pe, dev, dtype=torch.float64)
+        _fe, views_e = e.new_grads(pe, dev, dtype=fam.dtype)
         g_ea = torch.empty_like(edge_attr) if (edge_attr is not None and ctx.needs_input_grad[1]) else None
         if E > 0:
             rows = torch.empty(E, spec.C, D, **f64)
-            ws = _f64_ws(e, E, dev)
-            check(lib.csmpn_egcl_edge_backward_f64(e.metric_arr, e.n, e.params, e.grads, e.nblk, h.data_ptr(), spec.C, _ptr(edge_attr),
+            ws = fam.ws(e, E, dev)
+            check(fam.fn("csmpn_egcl_edge_backward")(e.metric_arr, e.n, e.params, e.grads, e.nblk, h.data_ptr(), spec.C, _ptr(edge_attr),
                                                    spec.A, csr.perm.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), E, N,
                                                    g_agg.data_ptr(), rows.data_ptr(), _ptr(g_ea), ws.data_ptr(), ws.numel(),
                                                    _stream(dev)))
-            segment_reduce_f64(rows, gh, add=(csr.row_ptr, None), sub=csr.source_order())
+            fam.segment_reduce(rows, gh, add=(csr.row_ptr, None), sub=csr.source_order())
         return (gh, g_ea, g_na, None, None, *views_e, *views_n)
 
 
 def cemlp_apply(x, binding: CemlpBinding, params):
     if x.is_cuda:   # (a CPU tensor: _CemlpFn raises "no CPU fallback", first of all)
         _same_dtype(x, ((f"parameter {PARAM_FIELDS[j % NP]} of block {j // NP}", p) for j, p in enumerate(params)), "CEMLP")
-        if x.dtype == torch.float64:
+        if x.dtype == torch.float64 or (x.dtype == torch.float32 and binding.sig_only()):
             return _CemlpF64Fn.apply(x, binding, *params)
     return _CemlpFn.apply(x, binding, *params)
 
@@ -1006,14 +1043,15 @@ class _EgclFn(torch.autograd.Function):
 def egcl_apply(h, edge_attr, node_attr, spec: EgclSpec, csr: Csr, params):
     if h.is_cuda:   # (a CPU tensor: _EgclFn raises "no CPU fallback", first of all)
         ne = spec.edge.nblk * NP
-        if h.dtype == torch.float64:
+        row_family = h.dtype == torch.float64 or (h.dtype == torch.float32 and spec.edge.sig_only())
+        if row_family:
             _on_device_like(h, (("edge_attr", edge_attr), ("node_attr", node_attr)))
         _same_dtype(h, (("edge_attr", edge_attr), ("node_attr", node_attr)), "EGCL")
         _same_dtype(h, ((f"parameter {PARAM_FIELDS[j % NP]} of block {j // NP} of the edge model", p) for j, p in enumerate(params[:ne])),
                     "EGCL")
         _same_dtype(h, ((f"parameter {PARAM_FIELDS[j % NP]} of block {j // NP} of the node model", p) for j, p in enumerate(params[ne:])),
                     "EGCL")
-        if h.dtype == torch.float64:
+        if row_family:
             return _EgclF64Fn.apply(h, edge_attr, node_attr, spec, csr, *params)
     return _EgclFn.apply(h, edge_attr, node_attr, spec, csr, *params)
 

@@ -1,5 +1,6 @@
 // C-ABI of the float64 kernel family (include/csmpn_hip.h, "float64"): argument checks, the tile / workspace plan, the
-// launches of cemlp_f64.hpp's kernels (one unit per algebra: k_f64_<tag>.hip) and the two fixed-order sums. A rejected call
+// launches of cemlp_f64.hpp's kernels (one unit per algebra: k_f64_<tag>.hip) - or, for a signature that is none of the six
+// compiled algebras, of cemlp_sig.hpp's double kernel on the same plan - and the two fixed-order sums. A rejected call
 // launches nothing and writes nothing: every check stands in front of the first HIP call.
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include "../../include/csmpn_hip.h"
 #include "capi_common.hpp"
 #include "cemlp_f64.hpp"
+#include "cemlp_sig.hpp"
 
 #define fail csmpn_fail
 
@@ -151,9 +153,13 @@ int fill_blocks(const csmpn_block_params_f64* b, int nb, const Plan& p, Args& a)
 // segments and row pointers set.
 int run(const float* metric, int n, const csmpn_block_params_f64* blocks, const csmpn_block_grads_f64* grads, int nb, int mode, bool bwd,
         int64_t rows, Args& a, void* ws, size_t ws_bytes, hipStream_t st) {
-    AlgInfo alg;
+    AlgInfo alg = {nullptr, 0, ""};
+    unsigned neg = 0;
     if (!metric) return fail(CSMPN_ERR_INVALID, "float64: metric is null");
-    if (!find_alg(metric, n, alg)) return fail(CSMPN_ERR_UNSUPPORTED, "metric not supported by the HIP path");
+    if (!sig::parse_signature(metric, n, neg)) return fail(CSMPN_ERR_UNSUPPORTED, "metric not supported by the HIP path");
+    // the six compiled algebras keep their kernel; every other signature (and all of them under CSMPN_FORCE_SIG=1) runs the
+    // run-time-signature kernel (cemlp_sig.hpp) on the same plan
+    const bool use_sig = !find_alg(metric, n, alg) || sig::force_sig();
     Plan p;
     int rc = make_plan(n, blocks, nb, rows, p);
     if (rc) return rc;
@@ -165,12 +171,19 @@ int run(const float* metric, int n, const csmpn_block_params_f64* blocks, const 
     if (ws_bytes < p.bytes || (p.bytes && !ws))
         return fail(CSMPN_ERR_INVALID, "float64: workspace of %zu bytes, %zu needed (csmpn_cemlp_f64_workspace_bytes)", ws_bytes, p.bytes);
     a.rows = rows; a.ws = static_cast<double*>(ws);
-    note_kernel("csmpn::f64::cemlp_f64_kernel<%s, %s> (mode %d, %d blocks, %d channels)", alg.name, bwd ? "bwd" : "fwd", mode, nb, p.maxO);
-    if (debug_on())
+    if (use_sig)
+        note_kernel("csmpn::sig::cemlp_sig_kernel<%d, double, %s> (signature 0x%x, mode %d, %d blocks, %d channels)", n, bwd ? "bwd" : "fwd",
+                    neg, mode, nb, p.maxO);
+    else
+        note_kernel("csmpn::f64::cemlp_f64_kernel<%s, %s> (mode %d, %d blocks, %d channels)", alg.name, bwd ? "bwd" : "fwd", mode, nb, p.maxO);
+    if (debug_on() && use_sig)
+        fprintf(stderr, "[csmpn] sig dtype=f64 n=%d neg=0x%x mode=%d bwd=%d channels=%d i0=%d grid=%u tile_rows=%d tiles=%ld lds=%zu rows=%ld\n",
+                n, neg, mode, (int)bwd, p.maxO, blocks[0].in_features, p.grid, p.R, p.tiles, p.lds + sig::table_bytes(1 << n), (long)rows);
+    else if (debug_on())
         fprintf(stderr, "[csmpn] f64 mode=%d bwd=%d channels=%d i0=%d grid=%u tile_rows=%d tiles=%ld lds=%zu rows=%ld\n", mode, (int)bwd, p.maxO,
                 blocks[0].in_features, p.grid, p.R, p.tiles, p.lds, (long)rows);
     if (p.grid == 0) return CSMPN_OK;
-    hipError_t e = alg.launch(bwd, p.grid, p.lds, st, a);
+    hipError_t e = use_sig ? sig::launch_f64(n, neg, bwd, p.grid, p.lds, st, a) : alg.launch(bwd, p.grid, p.lds, st, a);
     if (e != hipSuccess) return fail(CSMPN_ERR_HIP, "float64 row kernel: %s", hipGetErrorString(e));
     if (bwd) {
         SumArgs s;
@@ -181,7 +194,7 @@ int run(const float* metric, int n, const csmpn_block_params_f64* blocks, const 
             const long O = blocks[k].out_features, I = blocks[k].in_features;
             double* const dst[kTensors] = {grads[k].lin_w, grads[k].lin_b, grads[k].silu_a, grads[k].silu_b, grads[k].gp_w,
                                            grads[k].norm_a, grads[k].right_w, grads[k].left_w, grads[k].left_b, grads[k].ln_a};
-            const long size[kTensors] = {O * I * (blocks[k].lin_subspaces ? G : 1), O, O * G, O * G, O * alg.P, O * G, O * O * G, O * O * G, O, O};
+            const long size[kTensors] = {O * I * (blocks[k].lin_subspaces ? G : 1), O, O * G, O * G, O * (long)paths_of(n), O * G, O * O * G, O * O * G, O, O};
             for (int t = 0; t < kTensors; ++t) { s.dst[s.n] = dst[t]; s.off[s.n] = off; off += size[t]; ++s.n; }
         }
         s.off[s.n] = off;

@@ -674,7 +674,8 @@ int csmpn_readout_mse_backward(int n, const float* weight, int32_t weight_stride
  * INTO the gradient tensors (+=), and the edge stage writes row tables in sorted edge order which the fixed-order segment
  * sum below turns into agg / gh (the call sequence of CSMPN_FLAG_DETERMINISTIC). No flags, no saved buffers: the backward
  * recomputes the forward from its inputs.
- * Limits: the six compiled algebras (the check of csmpn_metric_supported, else CSMPN_ERR_UNSUPPORTED), 1..CSMPN_MAX_BLOCKS
+ * Limits: every signature csmpn_signature_supported accepts ("run-time signature" below says which kernel serves which;
+ * else CSMPN_ERR_UNSUPPORTED), 1..CSMPN_MAX_BLOCKS
  * blocks, out_features of every block 1..64 (one row of a block must fit the LDS; above: CSMPN_ERR_UNSUPPORTED),
  * in_features unbounded (input rows are streamed).
  * Workspace: with D = 2^n, G = n + 1, P grade paths, per block s_k = O I (G | 1) + 3 O + 3 O G + O P + 2 O O G doubles of
@@ -685,7 +686,7 @@ int csmpn_readout_mse_backward(int n, const float* weight, int32_t weight_stride
  * (0 for rows = 0 and for arguments the entry points reject). Needs no initialisation.
  * Argument checks (all in front of the first HIP call - a rejected call launches nothing and writes nothing): null
  * pointers, block count, chained widths, a workspace smaller than the query, negative rows / n_edges / n_nodes:
- * CSMPN_ERR_INVALID; n or the metric not compiled, a width above 64: CSMPN_ERR_UNSUPPORTED. Data pointers may be null where
+ * CSMPN_ERR_INVALID; n outside 2..5, a metric entry other than +1 / -1, a width above 64: CSMPN_ERR_UNSUPPORTED. Data pointers may be null where
  * the row count is 0. Every entry point is capturable (no allocation, no host synchronisation). */
 typedef struct csmpn_block_params_f64 {
     int32_t in_features;
@@ -757,6 +758,56 @@ int csmpn_egcl_node_backward_f64(const float* metric_host, int n, const csmpn_bl
 int csmpn_segment_reduce_f64(const double* rows, int64_t row_doubles, int64_t n_nodes, const int32_t* add_ptr,
                              const int32_t* add_order, const int32_t* sub_ptr, const int32_t* sub_order, double* out,
                              int32_t accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------------- run-time signature
+ * CEMLP and the EGCL stages on EVERY signature Cl(p,q) with p + q = n in 2..5 (60 metrics of +1 / -1 entries, in any
+ * order of the generators): one kernel family (csrc/cemlp_sig.hpp, "sig" in the CSMPN_DEBUG dispatch log) that takes the
+ * signature as a kernel argument. Design, order of summation, limits, contracts and call sequence are those of the float64
+ * family above (no atomics, no flags, no saved buffers, the backward recomputes the forward, parameter gradients +=, row
+ * tables summed by the fixed-order segment sum, capturable, bit-reproducible); only the sign of a blade product and of the
+ * quadratic form are looked up from a table that each workgroup expands from the signature.
+ *   float64: the seven *_f64 entry points above serve every such signature - the six compiled algebras on their own kernel
+ *     (on the sig kernel too when the environment has CSMPN_FORCE_SIG=1, read once per process: a test and A/B switch, the
+ *     bits are the same), every other signature on the sig kernel. Plan and workspace are the float64 formula, unchanged.
+ *   float32: the seven *_sig entry points below, on contiguous float tensors; they accept all 60 signatures, the six
+ *     compiled ones included. csmpn_segment_reduce sums their row tables. The float32 entry points further up
+ *     (csmpn_cemlp_forward, ...) are unchanged and still reject a signature that is not compiled.
+ * csmpn_signature_supported: 1 when n is in 2..5 and every entry of the host array is exactly +1 or -1, else 0 (NULL: 0).
+ * csmpn_metric_supported keeps its meaning: the six compiled algebras, which every other entry point needs.
+ * Workspace of the float32 family: with D, G, P, s_k, maxO, maxW as in the float64 formula, t = 16 ceil((D D + D) / 16) bytes
+ * of sign table, r = 4 (7 maxO D + 5 maxO G + 3 maxO + 2) bytes of LDS per row: tile rows R = min(32, (65536 - t) / r), or
+ * (163840 - t) / r where that is 0; tiles = ceil(rows / R); grid = min(tiles, 512), or min(tiles, 256) where R r + t > 65536;
+ *   bytes = 4 grid (sum_k s_k + R D sum_k I_k + 2 R D maxW)
+ * (0 for rows = 0 and for arguments the entry points reject). Needs no initialisation.
+ * Argument checks, codes and their place in front of the first HIP call: those of the float64 family; a metric that
+ * csmpn_signature_supported rejects: CSMPN_ERR_UNSUPPORTED. */
+int csmpn_signature_supported(const float* metric_host, int n);
+
+size_t csmpn_cemlp_sig_workspace_bytes(int n, const csmpn_block_params* blocks, int n_blocks, int64_t rows);
+
+int csmpn_cemlp_forward_sig(const float* metric_host, int n, const csmpn_block_params* blocks, int n_blocks, const float* x,
+                            int64_t rows, float* y, void* workspace, size_t workspace_bytes, void* stream);
+int csmpn_cemlp_backward_sig(const float* metric_host, int n, const csmpn_block_params* blocks, const csmpn_block_grads* grads,
+                             int n_blocks, const float* x, const float* gy, int64_t rows, float* gx, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int csmpn_egcl_edge_forward_sig(const float* metric_host, int n, const csmpn_block_params* blocks, int n_blocks, const float* h,
+                                int32_t channels, const float* edge_attr, int32_t attr_channels, const int32_t* perm,
+                                const int32_t* src_sorted, const int32_t* dst_sorted, int64_t n_edges, int64_t n_nodes,
+                                float* msg_rows, void* workspace, size_t workspace_bytes, void* stream);
+int csmpn_egcl_edge_backward_sig(const float* metric_host, int n, const csmpn_block_params* blocks, const csmpn_block_grads* grads,
+                                 int n_blocks, const float* h, int32_t channels, const float* edge_attr, int32_t attr_channels,
+                                 const int32_t* perm, const int32_t* src_sorted, const int32_t* dst_sorted, int64_t n_edges,
+                                 int64_t n_nodes, const float* g_agg, float* g_edge_rows, float* g_edge_attr, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int csmpn_egcl_node_forward_sig(const float* metric_host, int n, const csmpn_block_params* blocks, int n_blocks, const float* h,
+                                int32_t channels, const float* agg, int32_t agg_channels, const float* node_attr,
+                                int32_t attr_channels, const int32_t* in_degree, int32_t mean_aggr, int32_t residual,
+                                int64_t n_nodes, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int csmpn_egcl_node_backward_sig(const float* metric_host, int n, const csmpn_block_params* blocks, const csmpn_block_grads* grads,
+                                 int n_blocks, const float* h, int32_t channels, const float* agg, int32_t agg_channels,
+                                 const float* node_attr, int32_t attr_channels, const int32_t* in_degree, int32_t mean_aggr,
+                                 int32_t residual, int64_t n_nodes, const float* g_out, float* gh, float* g_agg,
+                                 float* g_node_attr, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Last error message of the calling thread (never NULL). */
 const char* csmpn_last_error(void);
