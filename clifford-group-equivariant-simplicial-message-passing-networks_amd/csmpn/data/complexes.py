@@ -492,7 +492,9 @@ class SimplicialBatch:
 
         A batch of cloud_batch_device (up to 4096 vertices per graph) takes dis=... alone: it is re-lifted by ops.cloud_lift
         (csmpn_cloud_lift) with the vertex_block it was built with and its own workspace; knn, hull, edges and the thresholds
-        are a ValueError there - those lifts hold at most 64 vertices per graph."""
+        are a ValueError there - those lifts hold at most 64 vertices per graph. A batch of knn_cloud_batch_device takes
+        knn=k alone: it is re-lifted by ops.cloud_knn_lift (csmpn_cloud_knn_lift) with its own workspace; dis, hull, edges and
+        the thresholds are a ValueError there."""
         from csmpn_hip import ops
         if (dis is not None) + (knn is not None) + bool(hull) + (edges is not None) != 1:
             raise ValueError("relift_: pass exactly one of dis=... (Rips), knn=... (k-nearest-neighbour cliques), hull=True "
@@ -503,6 +505,10 @@ class SimplicialBatch:
         if cloud is not None and (dis is None or thresholded):
             raise ValueError("relift_: a cloud batch (cloud_batch_device) is re-lifted with dis=... alone - the kNN, hull and "
                              "thresholded clique lifts (knn, hull, edges, edge_th, tri_th) hold at most 64 vertices per graph")
+        cloud_knn = plan is not None and plan.get("cloud_knn") is not None
+        if cloud_knn and (knn is None or thresholded):
+            raise ValueError("relift_: a kNN cloud batch (knn_cloud_batch_device) is re-lifted with knn=... alone - its workspace "
+                             "serves csmpn_cloud_knn_lift; dis, hull, edges, edge_th and tri_th go with the other batches")
         if thresholded and (dis is not None or hull):
             raise ValueError("relift_: edge_th / tri_th go with edges=... or knn=..., not with dis or hull")
         if plan is None or self._csr is None:
@@ -528,6 +534,8 @@ class SimplicialBatch:
             plan["lift_counts"] = torch.zeros(max_dim + 2, dtype=torch.int64, device=dev)
         if cloud is not None:
             run = lambda *args: ops.cloud_lift(*args, vertex_block=cloud["vertex_block"])
+        elif cloud_knn:
+            run = ops.cloud_knn_lift
         elif edges is not None or thresholded:
             if "clique_lift_ws" not in plan:
                 plan["clique_lift_ws"] = ops.clique_lift_workspace(B, rows[0] // B, max_dim, dev)
@@ -765,7 +773,8 @@ def pad_batch(batch: "SimplicialBatch", capacity: BatchCapacity, simplex_feature
 # clique_batch_device, relift_(points, edges=... | knn=k, edge_th=..., tri_th=...).
 # Those four hold at most 64 vertices per graph (hulls: 16). The Rips complex of a point cloud of up to 4096 vertices per graph -
 # one cloud of a few thousand points is a batch of one graph - is lifted by csmpn_cloud_lift, with or without the 0-0 block
-# over the non-edges: cloud_capacity, cloud_batch_device, relift_(points, dis=...) on such a batch.
+# over the non-edges: cloud_capacity, cloud_batch_device, relift_(points, dis=...) on such a batch; the clique complex of its
+# k-nearest-neighbour graph by csmpn_cloud_knn_lift: knn_capacity, knn_cloud_batch_device, relift_(points, knn=k).
 
 
 def _lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, device) -> torch.Tensor:
@@ -928,11 +937,22 @@ def cloud_batch_device(points: torch.Tensor, n_graphs: int, dis: float, capacity
                                 vertex_features, x_ind_cols)
 
 
+def knn_cloud_batch_device(points: torch.Tensor, n_graphs: int, k: int, capacity: BatchCapacity,
+                           features: Optional[Dict[str, torch.Tensor]] = None, vertex_features: Optional[Dict[str, torch.Tensor]] = None,
+                           x_ind_cols: Optional[int] = None) -> SimplicialBatch:
+    """knn_batch_device for point clouds of up to 4096 vertices per graph (knn_clique_complex(points, k, max_dim);
+    csmpn_cloud_knn_lift), at a capacity of knn_capacity, whose formula holds for any V. The batch's plan records that it is a
+    kNN cloud batch: relift_(points, knn=k) then goes to ops.cloud_knn_lift, and nothing else re-lifts it."""
+    return _lifted_batch_device("knn_cloud_batch_device", "cloud_knn_lift", points, n_graphs, int(k), capacity, features, vertex_features,
+                                x_ind_cols)
+
+
 def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, vertex_features, x_ind_cols) -> SimplicialBatch:
     """The body of rips_batch_device (op = "rips_lift", param = dis), knn_batch_device (op = "knn_lift", param = k),
     hull_batch_device (op = "hull_lift", no parameter; the volumes become `target`), clique_batch_device (op =
     "clique_lift", param = (the list or k, edge_th, tri_th); its larger workspace serves the other lifts as well) and
-    cloud_batch_device (op = "cloud_lift", param = (dis, vertex_block); its workspace serves that lift alone)."""
+    cloud_batch_device (op = "cloud_lift", param = (dis, vertex_block); its workspace serves that lift alone), as does that of
+    knn_cloud_batch_device (op = "cloud_knn_lift", param = k)."""
     from csmpn_hip import ops
     if not points.is_cuda:
         raise RuntimeError(f"{what} needs device points (no CPU fallback)")
@@ -942,9 +962,10 @@ def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, 
                    edge_types=i64(E, 2), batch=i64(S), ptr=i64(B + 1), x_ind_batch=i64(S), x_ind_ptr=i64(B + 1))
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     counts = i64(max_dim + 2)
-    clique, cloud = op == "clique_lift", op == "cloud_lift"
+    clique, cloud, cloud_knn = op == "clique_lift", op == "cloud_lift", op == "cloud_knn_lift"
     ws = ops.clique_lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev) if clique else \
         ops.cloud_lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev) if cloud else \
+        ops.cloud_knn_lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev) if cloud_knn else \
         _lift_workspace(B, int(points.shape[0]) // max(B, 1), max_dim, dev)
     volume = torch.zeros(B, dtype=torch.float32, device=dev) if op == "hull_lift" else None
     run = getattr(ops, op) if volume is None else (lambda p, b, _, *rest: ops.hull_lift(p, b, *rest, volume=volume))
@@ -977,4 +998,6 @@ def _lifted_batch_device(what, op, points, n_graphs, param, capacity, features, 
         plan["clique_lift_ws"] = ws
     if cloud:
         plan["cloud"] = {"vertex_block": param[1]}
+    if cloud_knn:
+        plan["cloud_knn"] = {"k": param}
     return out

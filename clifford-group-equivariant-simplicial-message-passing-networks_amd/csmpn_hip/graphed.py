@@ -130,7 +130,8 @@ class GraphedTrainStep:
     A `batch` built by csmpn.data.complexes.cloud_batch_device (the Rips complexes of point clouds of up to 4096 vertices per
     graph; csmpn_cloud_lift) is taken as it is - it lives on the device at `capacity` already, and its plan says which lift
     re-lifts it: step(points=..., dis=...) is the only device lift of such a step; knn, hull, edges and the thresholds are a
-    ValueError there."""
+    ValueError there. A batch of knn_cloud_batch_device (the clique complexes of their k-nearest-neighbour graphs;
+    csmpn_cloud_knn_lift) is taken the same way: step(points=..., knn=k), or the step's `knn`, is its only device lift."""
 
     hull = False
     edges = False
@@ -159,9 +160,11 @@ class GraphedTrainStep:
                 simplex_features = [k for k in feature_names if hasattr(batch, k) and getattr(batch, k).dim() >= 1
                                     and int(getattr(batch, k).shape[0]) == rows]
             self.simplex_features = tuple(simplex_features)
-            if (getattr(batch, "_plan", None) or {}).get("cloud") is not None:
-                # a batch of cloud_batch_device is on the device at its capacity already, and its plan says which lift
-                # re-lifts it (csmpn_cloud_lift: more than 64 vertices per graph) - padding would make a plain batch of it
+            batch_plan = getattr(batch, "_plan", None) or {}
+            if batch_plan.get("cloud") is not None or batch_plan.get("cloud_knn") is not None:
+                # a batch of cloud_batch_device or knn_cloud_batch_device is on the device at its capacity already, and its plan
+                # says which lift re-lifts it (csmpn_cloud_lift / csmpn_cloud_knn_lift: more than 64 vertices per graph) -
+                # padding would make a plain batch of it
                 if int(batch.node_types.shape[0]) != capacity.rows or int(batch.edge_index.shape[1]) != capacity.edges:
                     raise ValueError("GraphedTrainStep: the cloud batch was not built at `capacity`")
             else:

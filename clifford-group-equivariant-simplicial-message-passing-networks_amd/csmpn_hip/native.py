@@ -72,6 +72,8 @@ EXPORTS = (
     "csmpn_clique_lift",
     "csmpn_cloud_lift_workspace_bytes",
     "csmpn_cloud_lift",
+    "csmpn_cloud_knn_lift_workspace_bytes",
+    "csmpn_cloud_knn_lift",
     "csmpn_embed_cemlp_forward",
     "csmpn_embed_cemlp_backward",
     "csmpn_type_attr_forward",
@@ -205,6 +207,8 @@ def _load():
                                        vp, vp, vp, vp, sz, vp])
     sig("csmpn_cloud_lift_workspace_bytes", sz, [i64, i32, i32])
     sig("csmpn_cloud_lift", C.c_int, [vp, i32, i64, i32, C.c_double, i32, i32, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp])
+    sig("csmpn_cloud_knn_lift_workspace_bytes", sz, [i64, i32, i32])
+    sig("csmpn_cloud_knn_lift", C.c_int, [vp, i32, i64, i32, i32, i32, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp])
     sig("csmpn_embed_cemlp_forward", C.c_int, [fp, C.c_int, bp, C.c_int, vp, i64, i32, vp, i32, i32, i64, vp, vp, vp, sz, u32, vp])
     sig("csmpn_embed_cemlp_backward", C.c_int, [fp, C.c_int, bp, bg, C.c_int, vp, i64, i32, vp, i32, i32, i64, vp, vp, vp, sz, u32, vp])
     sig("csmpn_type_attr_forward", C.c_int, [C.c_int, vp, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp])

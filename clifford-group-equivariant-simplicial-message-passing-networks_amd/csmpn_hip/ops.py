@@ -1662,7 +1662,7 @@ def rips_lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, devic
 
 def _lift_arguments(what, points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch, x_ind_batch, ptr,
                     x_ind_ptr, edge_index, edge_types, counts, status):
-    """The tensor validation rips_lift, knn_lift and hull_lift share; returns (B, V, E, the capacity rows as a C array)."""
+    """The tensor validation rips_lift, knn_lift, hull_lift, clique_lift, cloud_lift and cloud_knn_lift share; returns (B, V, E, the capacity rows as a C array)."""
     if not points.is_cuda:
         raise RuntimeError(f"{what} needs device tensors (no CPU fallback)")
     if points.dtype != torch.float32 or points.dim() != 2 or not points.is_contiguous():
@@ -1806,6 +1806,28 @@ def cloud_lift(points, n_graphs, dis, max_dim, capacity_rows, capacity_edges, x_
     with torch.cuda.device(dev):
         check(native.lib().csmpn_cloud_lift(
             points.data_ptr(), int(points.shape[1]), B, V, float(dis), int(vertex_block), int(max_dim), C.addressof(cap), E,
+            x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), batch.data_ptr(), x_ind_batch.data_ptr(), ptr.data_ptr(),
+            x_ind_ptr.data_ptr(), edge_index.data_ptr(), _ptr(edge_types), _ptr(counts), _ptr(status), workspace.data_ptr(),
+            workspace.numel(), _stream(dev)))
+
+
+def cloud_knn_lift_workspace(n_graphs: int, verts_per_graph: int, max_dim: int, device) -> torch.Tensor:
+    """Workspace of cloud_knn_lift (uninitialised device bytes): that of cloud_lift and V^2 / 8 bytes per graph more, the
+    neighbour masks before they are made symmetric."""
+    return torch.empty(max(int(native.lib().csmpn_cloud_knn_lift_workspace_bytes(int(n_graphs), int(verts_per_graph), int(max_dim))), 16),
+                       dtype=torch.uint8, device=device)
+
+
+def cloud_knn_lift(points, n_graphs, k, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch, x_ind_batch, ptr,
+                   x_ind_ptr, edge_index, edge_types, counts, status, workspace):
+    """csmpn_cloud_knn_lift: knn_lift for point clouds of up to 4096 vertices per graph - the structure tensors of
+    pad_batch(collate([knn_clique_complex(points of graph g, k, max_dim)]), capacity), same buffers, same status bits."""
+    B, V, E, cap = _lift_arguments("cloud_knn_lift", points, n_graphs, max_dim, capacity_rows, capacity_edges, x_ind, node_types, batch,
+                                   x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status)
+    dev = points.device
+    with torch.cuda.device(dev):
+        check(native.lib().csmpn_cloud_knn_lift(
+            points.data_ptr(), int(points.shape[1]), B, V, int(k), int(max_dim), C.addressof(cap), E,
             x_ind.data_ptr(), int(x_ind.shape[1]), node_types.data_ptr(), batch.data_ptr(), x_ind_batch.data_ptr(), ptr.data_ptr(),
             x_ind_ptr.data_ptr(), edge_index.data_ptr(), _ptr(edge_types), _ptr(counts), _ptr(status), workspace.data_ptr(),
             workspace.numel(), _stream(dev)))

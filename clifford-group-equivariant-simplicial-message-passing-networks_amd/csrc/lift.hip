@@ -18,8 +18,9 @@
 // so the scatter reads T as the hull's does (kFacetTable = true, kTableStride = 64, no vertex block).
 //
 // csmpn_cloud_lift is the Rips lift of graphs of up to 4096 vertices, with or without the vertex block: several mask words per
-// vertex, one wave per vertex and kernels of its own - the section "the Rips lift of point clouds" below. Everything up to
-// there is the four lifts of small graphs:
+// vertex, one wave per vertex and kernels of its own - the section "the Rips lift of point clouds" below;
+// csmpn_cloud_knn_lift is the kNN clique lift of the same graphs: two kernels of its own make the mask words, the rest of that
+// section follows unchanged. Everything up to there is the four lifts of small graphs:
 //
 // A graph has at most 64 vertices, so ONE 64-bit neighbour mask per vertex (a wave ballot over the other vertices) carries
 // it, and every index is a popcount of masks plus a scan: with upper[a] = mask[a] restricted to b > a,
@@ -796,6 +797,130 @@ __global__ __launch_bounds__(kBlock) void cloud_mask_kernel(const float* points,
     }
 }
 
+// csmpn_cloud_knn_lift: the kNN rule of lift_knn_kernel on the same graphs. Two kernels stand where cloud_mask_kernel
+// stands, both a wave per vertex, and the count, scan, offsets and scatter kernels follow unchanged (no vertex block):
+//   select   dir[g][a][w] bit i = vertex 64 w + i is one of the k nearest neighbours of a. Counting ranks costs V^2 comparisons
+//            per vertex; instead the wave finds T, the k-th smallest s(a, .), by bisection on its bits - a non-negative double
+//            and +infinity order as the 64-bit integers their bits spell - two bits in a pass: with c_j = T | j << bit
+//            (j = 1, 2, 3) and n_j = #{b : s(a, b) < c_j} (a ballot and a popcount per word), T becomes the largest c_j with
+//            n_j < k. 32 passes, bit = 62, 60 .. 0, bit 63 never taken: both candidates that carry it lie above every s and
+//            count V - 1 > k. Behind them #{s < T} < k <= #{s <= T}, so T is the k-th smallest, and a last pass takes every b
+//            with s < T and, of the b with s == T, the first k - #{s < T} in ascending index (a popcount prefix carried over
+//            the words): rank(a, b) < k exactly. A candidate with n_j == k ends the bisection at once - the k sums below it
+//            are the neighbours and no tie is left to take - which, where the k-th and (k + 1)-th sums differ, happens at
+//            the first bit that parts them: 8 passes or so instead of 32. The row s(a, .) stays in registers, one 64-bit
+//            value per word and lane: the kernel is a template over the row's length (1, 2, 4, 16 or 64 words, the
+//            smallest that holds W) with every loop over it unrolled - no LDS, no index taken at run time, no scratch; the
+//            passes are compares, ballots and popcounts alone. k >= V - 1: every other vertex, no pass.
+//   mask     m[a] = dir[a] | (bit a of dir[b], every b): for word w, lane i reads the one word of dir[64 w + i] that holds
+//            bit a, and a ballot gives the word; beside it the rank, deg and up of cloud_mask_kernel.
+
+// one wave per vertex a of graph g = blockIdx.x / tiles: the words of its k nearest neighbours -> dir. kWords >= W is the
+// length of the row in registers: every loop over it is unrolled, so no index is taken at run time (no scratch).
+template <int kWords>
+__global__ __launch_bounds__(kBlock) void cloud_knn_select_kernel(const float* points, int P, int V, int W, int tiles, int k, u64* dir) {
+    const long g = blockIdx.x / (unsigned)tiles;
+    const int lane = threadIdx.x & 63, a = (int)(blockIdx.x % (unsigned)tiles) * kWaves + (threadIdx.x >> 6);
+    if (a >= V) return;                                       // the whole wave
+    const float* pg = points + g * V * (long)P;
+    u64* da = dir + ((long long)g * V + a) * W;
+    if (k >= V - 1) {                                         // every other vertex
+        for (int w = lane; w < W; w += 64) {
+            const int left = V - w * 64;                      // >= 1
+            u64 word = left >= 64 ? ~0ull : below(left);
+            if (w == (a >> 6)) word &= ~(1ull << (a & 63));
+            da[w] = word;
+        }
+        return;
+    }
+    // the row: s[w] = s(a, 64 w + lane) of lift_knn_kernel as the integer its bits spell, a NaN as +infinity; a lane at or
+    // past V, and the lane of a itself, reads no point and holds ~0, which lies above every candidate and equals no T: it
+    // never counts and never sets a bit. j is the outer loop, so the loads of one coordinate are all in flight together.
+    double acc[kWords];
+#pragma unroll
+    for (int w = 0; w < kWords; ++w) acc[w] = 0.0;
+    for (int j = 0; j < P; ++j) {
+        const double pa = (double)pg[a * P + j];
+#pragma unroll
+        for (int w = 0; w < kWords; ++w) {
+            const int b = w * 64 + lane;
+            if (b < V) {
+                const double d = sub_rn(pa, (double)pg[b * P + j]);
+                acc[w] = add_rn(acc[w], mul_rn(d, d));        // no contraction: the sum the host takes
+            }
+        }
+    }
+    u64 s[kWords];
+#pragma unroll
+    for (int w = 0; w < kWords; ++w) {
+        const int b = w * 64 + lane;
+        s[w] = b >= V || b == a ? ~0ull : acc[w] == acc[w] ? (u64)__double_as_longlong(acc[w]) : 0x7ff0000000000000ull;
+    }
+    u64 T = 0ull;
+    int less = 0;                                             // #{b : s(a, b) < T}, below k until a candidate counts k
+    for (int bit = 62; bit >= 0; bit -= 2) {
+        const u64 c1 = T | 1ull << bit, c2 = T | 2ull << bit, c3 = T | 3ull << bit;
+        int n1 = 0, n2 = 0, n3 = 0;
+#pragma unroll
+        for (int w = 0; w < kWords; ++w) {
+            n1 += __popcll(__ballot(s[w] < c1));
+            n2 += __popcll(__ballot(s[w] < c2));
+            n3 += __popcll(__ballot(s[w] < c3));
+        }
+        if (n1 == k || n2 == k || n3 == k) {                  // exactly k sums lie below this candidate: they are the neighbours
+            T = n1 == k ? c1 : n2 == k ? c2 : c3;
+            less = k;
+            break;
+        }
+        if (n3 < k) {
+            T = c3;
+            less = n3;
+        } else if (n2 < k) {
+            T = c2;
+            less = n2;
+        } else if (n1 < k) {
+            T = c1;
+            less = n1;
+        }
+    }
+    int ties = k - less;                                      // the b with s == T still to take, smallest index first
+#pragma unroll
+    for (int w = 0; w < kWords; ++w) {
+        const u64 eq = __ballot(s[w] == T);
+        const u64 word = __ballot(s[w] < T || (s[w] == T && __popcll(eq & below(lane)) < ties));
+        ties -= min(ties, __popcll(eq));
+        if (lane == 0 && w < W) da[w] = word;
+    }
+}
+
+// one wave per vertex a: the words of the undirected graph, and what cloud_mask_kernel writes beside them -> workspace
+__global__ __launch_bounds__(kBlock) void cloud_knn_mask_kernel(int V, int W, int tiles, const u64* dir, u64* masks, int* rank, int* deg,
+                                                                 int* up) {
+    const long g = blockIdx.x / (unsigned)tiles;
+    const int lane = threadIdx.x & 63, a = (int)(blockIdx.x % (unsigned)tiles) * kWaves + (threadIdx.x >> 6);
+    if (a >= V) return;                                       // the whole wave
+    const long long va = (long long)g * V + a;
+    const u64* dg = dir + (long long)g * V * W;
+    u64* ma = masks + va * W;
+    int* ra = rank + va * W;
+    int nd = 0, nu = 0;
+    for (int w = 0; w < W; ++w) {
+        const int b = w * 64 + lane;
+        const bool named = b < V && ((dg[(long long)b * W + (a >> 6)] >> (a & 63)) & 1ull);   // b names a; dir[a] never holds bit a
+        const u64 word = dg[(long long)a * W + w] | __ballot(named);
+        if (lane == 0) {
+            ma[w] = word;
+            ra[w] = nu;
+        }
+        nd += __popcll(word);
+        nu += __popcll(word & above_in(w, a));
+    }
+    if (lane == 0) {
+        deg[va] = nd;
+        up[va] = nu;
+    }
+}
+
 // one wave per vertex a; lane = word: tri[a] = the triangles (a, b, c), a < b < c, cof[a] = the cofaces of the edges (a, b), a < b
 __global__ __launch_bounds__(kBlock) void cloud_count_kernel(int V, int W, int tiles, const u64* masks, int* tri, int* cof) {
     const long g = blockIdx.x / (unsigned)tiles;
@@ -963,7 +1088,7 @@ inline bool sizes_ok(int64_t n_graphs, int32_t V, int32_t max_dim, int32_t max_v
     return (max_dim == 1 || max_dim == 2) && V > max_dim && V <= max_verts && n_graphs > 0 && n_graphs < (1ll << 31) / V;
 }
 
-enum class Lift { rips, knn, hull, clique, cloud };
+enum class Lift { rips, knn, hull, clique, cloud, cloud_knn };
 
 // csmpn_cloud_lift: alignment slack + header | masks [B, V, W] | rank [B, V, W] | deg, up, tri, cof [B, V] | n1 | n2 |
 // row offsets | adjacency offsets, W = ceil(V / 64) - V^2 / 8 bytes of masks and V^2 / 16 of ranks per graph
@@ -974,8 +1099,15 @@ inline size_t cloud_workspace_bytes_of(int64_t n_graphs, int32_t V, int32_t max_
            2 * align256(sizeof(int) * B) + 2 * align256(sizeof(long long) * B);
 }
 
+// csmpn_cloud_knn_lift: the same, then | dir [B, V, W], the masks before they are made symmetric
+inline size_t cloud_knn_workspace_bytes_of(int64_t n_graphs, int32_t V, int32_t max_dim) {
+    const size_t cloud = cloud_workspace_bytes_of(n_graphs, V, max_dim);
+    return cloud ? cloud + align256(sizeof(u64) * (size_t)n_graphs * (size_t)V * (size_t)cloud_words(V)) : 0;
+}
+
 inline size_t workspace_bytes_of(int64_t n_graphs, int32_t V, int32_t max_dim, Lift kind = Lift::rips) {
     if (kind == Lift::cloud) return cloud_workspace_bytes_of(n_graphs, V, max_dim);
+    if (kind == Lift::cloud_knn) return cloud_knn_workspace_bytes_of(n_graphs, V, max_dim);
     if (!sizes_ok(n_graphs, V, max_dim) || (kind == Lift::hull && V > kHullMaxVerts)) return 0;
     const size_t B = (size_t)n_graphs;
     // alignment slack + header | masks | n1 | n2 | row offsets | adjacency offsets; the hull lift: | T tables | volumes;
@@ -1011,17 +1143,18 @@ struct CliqueSource {            // what csmpn_clique_lift adds: the graph (a li
 // threshold, knn_k: the k of the kNN entry (0 for the others) - each checked where csmpn_rips_lift has always checked dis; the
 // hull entry checks its point dimension there, and its 16 vertices where the others check their 64; the clique entry checks
 // its graph source and its thresholds there; the cloud entry checks its kCloudMaxVerts vertices where the others check their
-// 64, and its vertex_block behind dis.
+// 64, and its vertex_block behind dis; the kNN cloud entry checks its vertices with the cloud entry and its k with the kNN entry.
 int check_lift_args(const char* what, const LiftArgs& a, double dis, int knn_k, Lift kind, Capacity* cap, const CliqueSource* src = nullptr,
                     int vertex_block = 0) {
     const int V = a.verts_per_graph, max_dim = a.max_dim;
-    const bool knn = kind == Lift::knn, hull = kind == Lift::hull;
+    const bool knn = kind == Lift::knn || kind == Lift::cloud_knn, hull = kind == Lift::hull;
+    const bool cloud = kind == Lift::cloud || kind == Lift::cloud_knn;
     if (max_dim < 0) return csmpn_fail(CSMPN_ERR_INVALID, "max_dim %d is negative", max_dim);
     if (max_dim != 1 && max_dim != 2) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: max_dim %d (1 or 2)", what, max_dim);
     if (hull && V > kHullMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > %d (every subset of point_dim vertices is tried)", what, V, kHullMaxVerts);
-    if (kind == Lift::cloud && V > kCloudMaxVerts)
+    if (cloud && V > kCloudMaxVerts)
         return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > kCloudMaxVerts = %d (V^2 / 8 bytes of masks and V^2 pair tests per graph)", what, V, kCloudMaxVerts);
-    if (kind != Lift::cloud && V > kMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > %d (one 64-bit mask per vertex)", what, V, kMaxVerts);
+    if (!cloud && V > kMaxVerts) return csmpn_fail(CSMPN_ERR_UNSUPPORTED, "%s: %d vertices per graph > %d (one 64-bit mask per vertex)", what, V, kMaxVerts);
     if (V <= max_dim) return csmpn_fail(CSMPN_ERR_INVALID, "%s: %d vertices per graph, max_dim %d needs %d", what, V, max_dim, max_dim + 1);
     if (a.n_graphs <= 0 || a.n_graphs >= (1ll << 31) / V) return csmpn_fail(CSMPN_ERR_INVALID, "bad sizes n_graphs=%lld verts_per_graph=%d", (long long)a.n_graphs, V);
     if (a.point_dim <= 0) return csmpn_fail(CSMPN_ERR_INVALID, "point_dim %d", (int)a.point_dim);
@@ -1138,8 +1271,9 @@ int launch_lift(const char* what, const LiftArgs& a, const Capacity& cap, double
 }
 
 // csmpn_cloud_lift behind the argument checks: the workspace carved up (cloud_workspace_bytes_of), then five launches - four
-// for max_dim = 1, which has no triangle to count.
-int launch_cloud_lift(const char* what, const LiftArgs& a, const Capacity& cap, double dis, bool vertex_block) {
+// for max_dim = 1, which has no triangle to count. knn_k >= 1: csmpn_cloud_knn_lift - the select and mask kernels in the place
+// of cloud_mask_kernel (one launch more), dir behind the cloud entry's parts, no vertex block.
+int launch_cloud_lift(const char* what, const LiftArgs& a, const Capacity& cap, double dis, bool vertex_block, int knn_k = 0) {
     hipStream_t st = (hipStream_t)a.stream;
     const int V = a.verts_per_graph, W = cloud_words(V), max_dim = a.max_dim, tiles = (V + kWaves - 1) / kWaves;
     const size_t B = (size_t)a.n_graphs, BV = B * (size_t)V, BVW = BV * (size_t)W;
@@ -1160,12 +1294,25 @@ int launch_cloud_lift(const char* what, const LiftArgs& a, const Capacity& cap, 
     int* n2 = reinterpret_cast<int*>(carve(sizeof(int) * B));
     long long* row_off = reinterpret_cast<long long*>(carve(sizeof(long long) * B));
     long long* adj_off = reinterpret_cast<long long*>(carve(sizeof(long long) * B));
+    u64* dir = knn_k > 0 ? reinterpret_cast<u64*>(carve(sizeof(u64) * BVW)) : nullptr;   // the kNN workspace alone has these bytes
     Outputs out{a.x_ind, a.node_types, a.batch, a.x_ind_batch, a.edge_index, a.edge_types, (int)a.x_ind_cols, cap.edges};
     const long long fill_items = std::max(cap.rows[1] + cap.rows[2], cap.edges);
     const long fill_blocks = (long)std::min<long long>(std::max<long long>((fill_items + kBlock - 1) / kBlock, 1), kMaxFillBlocks);
     const dim3 per_vertex((unsigned)(B * (size_t)tiles)), per_graph((unsigned)B), one(1), scatter((unsigned)(B * (size_t)tiles + fill_blocks)),
         block(kBlock);
-    hipLaunchKernelGGL(cloud_mask_kernel, per_vertex, block, 0, st, a.points, (int)a.point_dim, V, W, tiles, dis * dis, masks, rank, deg, up);
+    if (knn_k > 0) {
+#define CSMPN_CLOUD_SELECT(WORDS) \
+    hipLaunchKernelGGL(cloud_knn_select_kernel<WORDS>, per_vertex, block, 0, st, a.points, (int)a.point_dim, V, W, tiles, knn_k, dir)
+        if (W <= 1) CSMPN_CLOUD_SELECT(1);
+        else if (W <= 2) CSMPN_CLOUD_SELECT(2);
+        else if (W <= 4) CSMPN_CLOUD_SELECT(4);
+        else if (W <= 16) CSMPN_CLOUD_SELECT(16);
+        else CSMPN_CLOUD_SELECT(64);
+#undef CSMPN_CLOUD_SELECT
+        hipLaunchKernelGGL(cloud_knn_mask_kernel, per_vertex, block, 0, st, V, W, tiles, (const u64*)dir, masks, rank, deg, up);
+    } else {
+        hipLaunchKernelGGL(cloud_mask_kernel, per_vertex, block, 0, st, a.points, (int)a.point_dim, V, W, tiles, dis * dis, masks, rank, deg, up);
+    }
     if (max_dim >= 2) hipLaunchKernelGGL(cloud_count_kernel, per_vertex, block, 0, st, V, W, tiles, (const u64*)masks, tri, cof);
     hipLaunchKernelGGL(cloud_scan_kernel, per_graph, block, 0, st, V, max_dim, deg, up, tri, cof, n1, n2);
 #define CSMPN_CLOUD_TAIL(BLOCK)                                                                                                                   \
@@ -1202,6 +1349,21 @@ int csmpn_cloud_lift(const float* points, int32_t point_dim, int64_t n_graphs, i
     Capacity cap{};
     if (const int rc = check_lift_args("cloud lift", a, dis, 0, Lift::cloud, &cap, nullptr, (int)vertex_block)) return rc;
     return launch_cloud_lift("cloud lift", a, cap, dis, vertex_block == 1);
+}
+
+size_t csmpn_cloud_knn_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim) {
+    return workspace_bytes_of(n_graphs, verts_per_graph, max_dim, Lift::cloud_knn);
+}
+
+int csmpn_cloud_knn_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, int32_t k, int32_t max_dim,
+                         const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                         int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                         int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const LiftArgs a{points, point_dim, n_graphs, verts_per_graph, max_dim, capacity_rows, capacity_edges, x_ind, x_ind_cols, node_types,
+                     batch, x_ind_batch, ptr, x_ind_ptr, edge_index, edge_types, counts, status, workspace, workspace_bytes, stream};
+    Capacity cap{};
+    if (const int rc = check_lift_args("cloud knn lift", a, 0.0, (int)k, Lift::cloud_knn, &cap)) return rc;
+    return launch_cloud_lift("cloud knn lift", a, cap, 0.0, false, (int)k);
 }
 
 size_t csmpn_rips_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim) {

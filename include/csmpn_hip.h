@@ -572,6 +572,35 @@ int csmpn_cloud_lift(const float* points, int32_t point_dim, int64_t n_graphs, i
                      int64_t* node_types, int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index,
                      int64_t* edge_types, int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The kNN clique lift of point clouds of up to 4096 vertices per graph: the structure tensors of exactly the batch that
+ *   pad_batch(collate([knn_clique_complex(points_g, k, max_dim) for g]), BatchCapacity(capacity_rows, capacity_edges))
+ * builds on the host, written into buffers of the capacity's shapes. The rule is word for word that of csmpn_knn_lift:
+ * s(a, b) summed in double over j ascending, every difference, product and sum rounded once, none contracted, a NaN sum
+ * counting as +infinity; rank(a, b) = the number of c outside {a, b} with s(a, c) < s(a, b), or s(a, c) == s(a, b) and c < b; b
+ * is a neighbour of a iff rank(a, b) < k (k >= verts_per_graph - 1: every other vertex); {a, b} is an edge iff either names
+ * the other; the 2-simplices are the triples whose three pairs are edges; the adjacencies are those of
+ * lift(..., vertex_block=False), 6 n1 + 12 n2. On verts_per_graph <= 64 (accepted too) the call writes the very bits of
+ * csmpn_knn_lift.
+ *   The neighbours are selected, not ranked: a wave per vertex finds the k-th smallest s(a, .) by bisection on its bit
+ *   pattern (32 counting passes of two bits each) and takes the ties at that value in ascending index; a second kernel makes
+ *   the masks symmetric by reading, for every b, the one word of b's mask that holds bit a. From there on the kernels are those
+ *   of csmpn_cloud_lift with vertex_block = 0.
+ * Contracts, those of csmpn_cloud_lift: every launch on `stream` (six; five for max_dim = 1), no allocation, no host round
+ * trip, no atomic anywhere - the outputs hold the same bits in every call and the call can be captured in a HIP graph. A batch
+ * that does not fit leaves EVERY output as it was and ORs the bits 1..4 of csmpn_rips_lift into *status; a graph's triangle
+ * count saturates at 2^31 - 1, which no capacity admits (bit 2).
+ * Limits: max_dim in {1, 2} and verts_per_graph <= 4096 (kCloudMaxVerts), else CSMPN_ERR_UNSUPPORTED; k < 1:
+ * CSMPN_ERR_INVALID, checked where csmpn_knn_lift checks it; every other check, its code and its place are those of
+ * csmpn_cloud_lift. Arguments are checked before the first HIP call.
+ * workspace: csmpn_cloud_knn_lift_workspace_bytes(...) bytes of device memory (host-only query; 0 for sizes the entry point
+ * rejects): that of csmpn_cloud_lift plus 8 B V W bytes, rounded up to 256, for the masks before they are made symmetric;
+ * needs no initialisation. */
+size_t csmpn_cloud_knn_lift_workspace_bytes(int64_t n_graphs, int32_t verts_per_graph, int32_t max_dim);
+int csmpn_cloud_knn_lift(const float* points, int32_t point_dim, int64_t n_graphs, int32_t verts_per_graph, int32_t k, int32_t max_dim,
+                         const int64_t* capacity_rows, int64_t capacity_edges, int64_t* x_ind, int32_t x_ind_cols, int64_t* node_types,
+                         int64_t* batch, int64_t* x_ind_batch, int64_t* ptr, int64_t* x_ind_ptr, int64_t* edge_index, int64_t* edge_types,
+                         int64_t* counts, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fused simplex feature embedding (round 3; hulls_cssmpnn.py:96-125: vertex features of every d-simplex in all (d+1)!
  * vertex orders -> CEMLP -> sum over the orders), for the two standalone programs the wide parity-lane kernels are
  * instantiated for (Cl(5,0) / Cl(4,1), blocks of 28 output channels; in_features = verts_per_row * channels_per_vertex = 2
